@@ -13,9 +13,16 @@ GPU (weak scaling), synthetic walkers and random-init weights, float32.
 
 The walkers of an N-GPU run are the reference's split of ONE global batch of N x `--walkers` walkers
 (`electron_batch_size // device_count`, sampling_utils.py:253-262 -> parallel.shard_bounds).  The timed
-region is `--steps` VMC steps bracketed by barrier + synchronize, repeated back to back until >= 10 s of
-steady state have been measured (at least 10 blocks); `ms_per_step` is the median block (max over ranks
-per block), min / max are reported beside it.
+region is `--steps` VMC steps bracketed by barrier + synchronize (max over ranks); `ms_per_step` is its
+time divided by `--steps`.  `--repeats R` times R such blocks back to back and reports the median block
+(min / max beside it); `--repeats 0` repeats until `--min-seconds` of steady state have been measured.
+Untimed, before the `--warmup` steps: `--equilibrate` Metropolis sub-steps move the walkers towards |psi|^2, and
+`--spinup-seconds` of sub-steps on a copy of them bring the GPU to its steady clocks.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned to its caller
+(walker positions, psi, per-walker local energies and their terms, the reduced energy statistics) as
+DIR/<name>.npy in float32 / float64, plus DIR/manifest.json.  Inputs are seeded and the number of
+steps before the dump is fixed by the arguments, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the forward-Laplacian
 linear layer) against the exact-f32 MFMA peak; `cpu_baseline` is the PyTorch-CPU oracle timed
@@ -99,17 +106,31 @@ def _cpu_worker(args):
     return batch / t_e, batch / t_w, n_e, n_w
 
 
+def cpu_budget():
+    """Host CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it (a
+    shared host can show far more cores than a job is given)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get('OMP_NUM_THREADS', '')))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+CPU_BASELINE_MAX_PROCS = 4      # worker processes of the multi-process layout (each one imports torch)
+
+
 def cpu_baseline_measure(molname, spec_name, n_sub, dtype_name='f32', batch=256, budget_s=8.0):
     """The oracle ("port": the reference's per-walker algorithm restated in PyTorch -- NOT the reference JAX-CPU
-    path, which cannot run in this image) timed on this box's host cores in the reference's production dtype,
-    batched with torch.func.vmap.  Two layouts are timed on a bounded sample and the faster one is reported:
-    one process with up to 16 intra-op threads, and one process per 8 cores (at most 24) with 8 threads each
-    (hundreds of intra-op threads on these small tensors only thrash)."""
+    path, which cannot run in this image) timed on the host CPUs this process may use (`cpu_budget`) in the
+    reference's production dtype, batched with torch.func.vmap.  Two layouts are timed on a bounded sample and the
+    faster one is reported: one process with up to 16 intra-op threads, and one process per 8 CPUs (at most
+    CPU_BASELINE_MAX_PROCS) with 8 threads each (hundreds of intra-op threads on these small tensors only thrash)."""
     import multiprocessing as mp
-    cores = os.cpu_count() or 1
+    cores = cpu_budget()
     layouts = [(1, min(cores, 16))]
     if cores >= 16:
-        layouts.append((min(cores // 8, 24), 8))
+        layouts.append((min(cores // 8, CPU_BASELINE_MAX_PROCS), 8))
     best = None
     for n_proc, threads in layouts:
         jobs = [(molname, spec_name, dtype_name, batch, threads, budget_s, w) for w in range(n_proc)]
@@ -130,7 +151,7 @@ def cpu_baseline_measure(molname, spec_name, n_sub, dtype_name='f32', batch=256,
     return {
         'value': 1.0 / per_walker_step, 'unit': 'walker*E_loc evals/s (VMC step incl. %d sub-steps)' % n_sub,
         'eloc_only_evals_per_s': best['eloc_rate'], 'psi_evals_per_s': best['wf_rate'],
-        'cores': best['n_proc'] * best['threads'], 'host_logical_cores': cores, 'kind': 'port',
+        'cores': best['n_proc'] * best['threads'], 'cpu_budget': cores, 'host_logical_cores': os.cpu_count(), 'kind': 'port',
         'sample': f"oracle-CPU stand-in (not the reference JAX-CPU path): torch.func.vmap over {batch} walkers of the per-walker "
                   f"local energy (jacfwd(grad) Laplacian) and of psi, {dtype_name}, {best['n_proc']} process(es) x {best['threads']} "
                   f"threads, median of {best['n_eloc_calls']} E_loc + {best['n_psi_calls']} psi batched calls "
@@ -171,6 +192,55 @@ def committed_traffic(kernel, workload):
     return None, None
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, last, rank, world, n_walkers):
+    """--dump-outputs: the arrays the last timed step returned to its caller, walker axis first, as
+    `<out_dir>/<name>.npy` (floats in the engine's dtype, integers as float64) plus manifest.json.  Over
+    DUMP_BUDGET_BYTES in all, every per-walker array keeps the same fixed, seeded sample of walkers (walker_index.npy).
+    With several ranks, rank k writes `rank<k>_<name>.npy` (its shard of the walkers)."""
+    def host(t):
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+    per_walker = {}
+    states = last['state'] if isinstance(last['state'], list) else [last['state']]
+    for s_, st in enumerate(states):
+        pre = f'state{s_}_' if len(states) > 1 else ''
+        per_walker[pre + 'r'] = host(st['r'])
+        per_walker[pre + 'psi_sign'] = host(st['psi'].sign)
+        per_walker[pre + 'psi_log'] = host(st['psi'].log)
+        per_walker[pre + 'age'] = host(st['age'])
+    e = host(last['e'])
+    if e.ndim == 1:                                   # single state: E_loc[B] and its terms {key: [B]}
+        per_walker['e_loc'] = e
+        for k, v in last.get('e_terms', {}).items():
+            per_walker['e_loc_' + k.replace('/', '_')] = host(v)
+    else:                                             # states: E_loc[1, S, B], psi ratios [1, S, S, B]
+        per_walker['e_loc'] = np.moveaxis(e[0], -1, 0)
+        per_walker['psi_ratio'] = np.moveaxis(host(last['psi_ratio'])[0], -1, 0)
+    assert all(a.shape[0] == n_walkers for a in per_walker.values()), {k: a.shape for k, a in per_walker.items()}
+    stats = {k: float(v) for k, v in (last.get('stats') or {}).items()}
+    scalars = {'energy_stats': np.array([stats[k] for k in sorted(stats)], np.float64)}
+
+    budget = DUMP_BUDGET_BYTES // world - sum(a.nbytes for a in scalars.values())
+    per_walker_bytes = sum(a.nbytes for a in per_walker.values()) / n_walkers
+    if per_walker_bytes * n_walkers > budget:
+        keep = max(1, int(budget // (per_walker_bytes + 8)))
+        idx = np.sort(np.random.default_rng(12345).choice(n_walkers, keep, replace=False))
+        per_walker = {k: a[idx] for k, a in per_walker.items()}
+        scalars['walker_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    pre = f'rank{rank}_' if world > 1 else ''
+    arrays = {**per_walker, **scalars}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, pre + k + '.npy'), np.ascontiguousarray(a))
+    with open(os.path.join(out_dir, pre + 'manifest.json'), 'w') as f:
+        json.dump({'arrays': {k: {'shape': list(a.shape), 'dtype': str(a.dtype)} for k, a in arrays.items()},
+                   'energy_stats_keys': sorted(stats), 'walkers': n_walkers, 'rank': rank, 'world': world}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -182,8 +252,13 @@ def main():
     ap.add_argument('--ansatz', default='paulinet')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f64'])
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--equilibrate', type=int, default=400, help='untimed Metropolis sub-steps before the warm-up steps, so that the timed '
-                    'steps see |psi|^2-distributed walkers (the reference equilibrates its sampler before training, sampling_utils.py:133-170); 0: off')
+    ap.add_argument('--equilibrate', type=int, default=3000, help='untimed Metropolis sub-steps before the warm-up steps, so that the timed '
+                    'steps see |psi|^2-distributed walkers (the reference equilibrates its sampler before training, sampling_utils.py:133-170); '
+                    'after fewer, the share of walkers the float64 refinement re-evaluates is still falling (LiH: 19 %% of them after 400 '
+                    'sub-steps, 15.5 %% after 3000); 0: off')
+    ap.add_argument('--spinup-seconds', type=float, default=1.0, help='untimed Metropolis sub-steps on a COPY of the walkers for this '
+                    'long before the warm-up steps, so that the timed steps find the GPU at its steady clocks (the walkers and the '
+                    'library state the timed steps see do not depend on it); 0: off')
     ap.add_argument('--ecp', action='store_true', help='Gaussian-type ECP on every atom heavier than He with SYNTHETIC '
                     'coefficients (pyscf tables are not available offline): exercises the 12 N n_ecp psi-ratio quadrature')
     ap.add_argument('--fused', type=int, default=1, help='0: one launch per op for psi evaluation')
@@ -202,8 +277,11 @@ def main():
     ap.add_argument('--refine', type=int, default=-1, help='float64 refinement of ill-conditioned walkers: 0 off, 1 flagged walkers '
                     '(library default), 2 whole E_loc pass in float64')
     ap.add_argument('--opt', action='append', default=[], help='library option name=value (dqmc_set_option), repeatable')
-    ap.add_argument('--repeats', type=int, default=0, help='timed blocks of --steps steps (0: as many as fill --min-seconds, at least 10)')
-    ap.add_argument('--min-seconds', type=float, default=10.0, help='steady-state time the timed blocks must cover')
+    ap.add_argument('--repeats', type=int, default=1, help='timed blocks of --steps steps, median reported (0: as many as fill '
+                    '--min-seconds, at least 10 -- the number of steps then depends on the timing)')
+    ap.add_argument('--min-seconds', type=float, default=10.0, help='with --repeats 0: steady-state time the timed blocks must cover')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last timed step '
+                    'returned (walkers, psi, per-walker E_loc and its terms, energy statistics) as DIR/<name>.npy')
     ap.add_argument('--torch-reduce', action='store_true', help='reduce the energy statistics through torch.distributed on the host '
                     '(default: one ncclAllGather inside the library on the context\'s stream)')
     ap.add_argument('--emulated', action='store_true', help='TEST ONLY: CPU SIMT emulation of the kernels + gloo (exercises the '
@@ -216,6 +294,8 @@ def main():
         return
     if args.gpus < 1:
         sys.exit('bench.py: --gpus must be >= 1')
+    if args.steps < 1:
+        sys.exit('bench.py: --steps must be >= 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # launched as plain `python bench.py --gpus N`: become N ranks (one process per GPU) under torch.distributed.run
         n_dev = args.gpus if args.emulated else (torch.cuda.device_count() if torch.cuda.is_available() else 0)
@@ -360,6 +440,9 @@ def main():
             torch.distributed.barrier()
         sync()
 
+    # what the most recent step handed back to its caller (references to that step's own result tensors; --dump-outputs)
+    last = {}
+
     def vmc_step_states(step, state):
         """Multi-state step: sample every state, E_loc[1,S,B], psi ratios [1,S,S,B], overlap penalty (one all-reduce)."""
         state, pc, _ = ms_sampler.sample(step * world + rank, state, params_s)
@@ -369,6 +452,7 @@ def main():
         pen, info = loss.compute_mean_overlap(ratio, ones)
         stats = reduce_stats(eng, E[0, 0].contiguous())
         stats['overlap/penalty'] = float(pen)
+        last.update(state=state, e=E, psi_ratio=ratio, stats=stats)
         return state, stats
 
     refined = []           # walkers re-evaluated in float64 per step (host-side counter of the library, no sync)
@@ -381,9 +465,10 @@ def main():
             r = state['r']
         else:
             r = state['r']
-        e, _ = loc_ene(step, params, r)
+        e, e_terms = loc_ene(step, params, r)
         refined.append(eng.last_refined())
         stats = reduce_stats(eng, e)
+        last.update(state=state, e=e, e_terms=e_terms, stats=stats)
         return state, stats
 
     # ---- software-pipelined variant: E_loc(k) runs on a second stream while the sub-steps of step k+1 run ----
@@ -405,13 +490,15 @@ def main():
             ev = s_main.record_event()
             with torch.cuda.stream(s_e):
                 s_e.wait_event(ev)
-                pipe['e'], _ = eng_e.local_energy(r_snap)
+                pipe['e'], e_terms = eng_e.local_energy(r_snap)
+            last.update(state=state, e=pipe['e'], e_terms=e_terms, stats=pipe['stats'])
             return state, pipe['stats']
 
         def drain():
             with torch.cuda.stream(s_e):
                 pipe['stats'] = reduce_stats(eng_e, pipe['e'])
             pipe['e'] = None
+            last['stats'] = pipe['stats']        # the statistics of the E_loc the last step launched
             return pipe['stats']
 
     step_fn = vmc_step_pipelined if args.overlap else vmc_step
@@ -430,6 +517,18 @@ def main():
                 state = burn.sample(900_000 + k, state, params)[0]
         sync()
         log(f'equilibrated with {args.equilibrate} sub-steps')
+    if args.spinup_seconds > 0 and args.n_sub > 0 and device.type == 'cuda':
+        # the sampler returns new tensors and leaves the walkers it is given untouched; no local energy runs here, so the
+        # float64-refinement state of the library (call counters, calibrated threshold) is not advanced either
+        spin = DecorrSampler(hamil, wf, length=args.n_sub)
+        spin_state = state if S == 1 else state[0]
+        t_end, k = time.perf_counter() + args.spinup_seconds, 0
+        while time.perf_counter() < t_end:
+            spin_state = spin.sample(800_000 + k, spin_state, params if S == 1 else params_s[0])[0]
+            sync()
+            k += 1
+        del spin_state
+        log(f'spin-up: {k} untimed steps of {args.n_sub} sub-steps on a copy of the walkers')
     for s in range(args.warmup):
         state, stats = step_fn(s, state)
     if args.overlap:
@@ -462,7 +561,11 @@ def main():
         n_blocks = int(t.item())
     for k in range(1, n_blocks):
         blocks.append(timed_block(args.warmup + k * args.steps))
-    log(f'{len(blocks)} timed blocks done')
+    log(f'{len(blocks)} timed block(s) of {args.steps} steps done')
+    if args.dump_outputs:
+        sync()
+        dump_outputs(args.dump_outputs, last, rank, world, B)     # before anything else advances the (in-place) state
+        log(f'outputs of the last timed step written to {args.dump_outputs}')
     elapsed = float(np.median(blocks))
     ms_per_step = 1e3 * elapsed / args.steps
     refined_timed = list(refined[args.warmup:]) if S == 1 and not args.overlap else []
@@ -477,8 +580,8 @@ def main():
     ms_refine_off = None
     if not args.emulated and args.refine < 0 and args.dtype == 'f32' and S == 1 and not args.overlap:
         eng.set_option('refine', 0)
-        timed_block(10_000)
-        off = [timed_block(10_000 + (k + 1) * args.steps) for k in range(max(3, min(len(blocks), 10)))]
+        state, _ = step_fn(10_000, state)    # one untimed step after the switch
+        off = [timed_block(10_001 + k * args.steps) for k in range(len(blocks))]
         ms_refine_off = 1e3 * float(np.median(off)) / args.steps
         eng.set_option('refine', 1)
     eloc_only, roofline = None, None

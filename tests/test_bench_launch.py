@@ -46,3 +46,28 @@ def test_too_many_gpus_is_a_clear_error():
     env['WORLD_SIZE'] = '3'
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'], capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode != 0 and 'WORLD_SIZE=3' in p.stderr and 'Traceback' not in p.stderr
+
+
+def test_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs: the last timed step's walkers, psi, per-walker local energies and energy statistics as .npy files in
+    float32 / float64; `--steps` sets the timed steps, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    from simt_util import emu_lib
+    emu_lib()
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        p = run_bench('--gpus', '1', '--walkers', '8', '--steps', '2', '--dump-outputs', str(d), env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+        assert out['steps'] == 2 and out['timed_blocks'] == 1 and out['ms_per_step'] > 0
+        manifest = json.load(open(d / 'manifest.json'))
+        arrays = {name: np.load(d / f'{name}.npy') for name in manifest['arrays']}
+        assert {'r', 'psi_sign', 'psi_log', 'e_loc', 'energy_stats'} <= set(arrays)
+        assert arrays['r'].shape == (8, 4, 3) and arrays['e_loc'].shape == (8,)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert np.all(np.isfinite(arrays['e_loc']))
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][name], err_msg=name)

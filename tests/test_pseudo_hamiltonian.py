@@ -1,8 +1,11 @@
 """Pseudo-Hamiltonians (reference ecp/pseudo_hamiltonian.py): properties of the oracle restatement, the XML table
 parser, and the HIP path (through the SIMT emulator) against the oracle on the same walkers.  The reference has no
 test of this module, so parity is unpinned (oracle/pseudo_hamiltonian.py header); the tables used against the HIP
-path are synthetic smooth functions on the reference's kind of grid."""
+path are synthetic smooth functions on the reference's kind of grid.  The reference's own XML tables are stored
+xz-compressed under tests/golden/ph_data and unpacked into a temporary directory for the tests that read them."""
+import lzma
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -17,8 +20,19 @@ from oracle import pseudo_hamiltonian as oph
 from oracle import wf as owf
 from simt_util import emu_lib
 
-REF_PH_DATA = '/root/reference/src/deepqmc/ecp/ph_data'
+PH_DATA_XZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ph_data')
 N_GRID, R_MAX = 2001, 10.0
+
+
+@pytest.fixture(scope='module')
+def ref_ph_data(tmp_path_factory):
+    """A directory of the reference's `<El>.<suffix>.xml` tables, unpacked from tests/golden/ph_data/*.xml.xz."""
+    out = tmp_path_factory.mktemp('ph_data')
+    for name in sorted(os.listdir(PH_DATA_XZ)):
+        if name.endswith('.xml.xz'):
+            with lzma.open(os.path.join(PH_DATA_XZ, name), 'rb') as src, open(out / name[:-3], 'wb') as dst:
+                shutil.copyfileobj(src, dst)
+    return str(out)
 
 
 def synthetic_tables():
@@ -80,14 +94,12 @@ def test_table_container_and_reference_lookup_rules():
         MolecularHamiltonian(mol=Molecule.from_name('LiH'), ecp_type='PHcc')
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PH_DATA), reason='reference pseudo-Hamiltonian tables not present')
-def test_reference_xml_tables_parse_and_satisfy_the_ph_relation():
+def test_reference_xml_tables_parse_and_satisfy_the_ph_relation(ref_ph_data):
     """pseudo_hamiltonian.py:59-62: the files are built such that 2 (s - d) = 3 (p - d); the parser relies on it."""
     from xml.etree import ElementTree
     for z, (name, suffix) in ELEMENTS_WITH_EXISTING_PH.items():
-        path = os.path.join(REF_PH_DATA, f'{name}.{suffix}.xml')
-        if not os.path.exists(path):
-            continue
+        path = os.path.join(ref_ph_data, f'{name}.{suffix}.xml')
+        assert os.path.exists(path), path
         loc, l2, zval = parse_ph_xml(path)
         assert loc.shape == l2.shape == (10001,) and zval > 0
         root = ElementTree.parse(path).getroot()
@@ -141,22 +153,20 @@ def test_hip_pseudo_hamiltonian_f32_and_refinement_twin():
     _hip_vs_oracle('paulinet', [True, True], dtype=torch.float32, refine=2, tol=2e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PH_DATA), reason='reference pseudo-Hamiltonian tables not present')
-def test_reference_tables_through_the_facade(monkeypatch):
+def test_reference_tables_through_the_facade(monkeypatch, ref_ph_data):
     """`ecp_type='PHcc'` with the reference's own XML directory (environment variable, as a maintainer without the
     deepqmc package on the path would set it): HCl keeps 7 + 1 valence electrons, the tables land on the reference's grid."""
-    monkeypatch.setenv('DEEPQMC_PH_DATA', REF_PH_DATA)
+    monkeypatch.setenv('DEEPQMC_PH_DATA', ref_ph_data)
     mol = Molecule(coords=np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 2.4]]), charges=np.array([17, 1]), charge=0, spin=0)
     h = MolecularHamiltonian(mol=mol, ecp_type='PHcc')
     assert h.ecp_mask.tolist() == [True, False] and h.ns_valence.tolist() == [7.0, 1.0] and (h.n_up, h.n_down) == (4, 4)
     assert h.pot.rv_loc.shape == (2, 10001) and h.pot.r_max == 10.0 and not h.pot.rv_l2[1].any()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PH_DATA), reason='reference pseudo-Hamiltonian tables not present')
-def test_hip_hcl_with_the_reference_chlorine_table(monkeypatch):
+def test_hip_hcl_with_the_reference_chlorine_table(monkeypatch, ref_ph_data):
     """End to end on a molecule the reference's tables cover: HCl with the OPH23 chlorine pseudo-Hamiltonian (7 valence
     electrons on Cl), 8 electrons, float64, HIP path (emulated) against the oracle restatement on the reference's grid."""
-    monkeypatch.setenv('DEEPQMC_PH_DATA', REF_PH_DATA)
+    monkeypatch.setenv('DEEPQMC_PH_DATA', ref_ph_data)
     mol = Molecule(coords=np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 2.4]]), charges=np.array([17, 1]), charge=0, spin=0)
     h = MolecularHamiltonian(mol=mol, ecp_type='PHcc')
     wf = NeuralNetworkWaveFunction(h, 'paulinet', dtype=torch.float64, device='cpu', lib=emu_lib(), norm_eps=geom.F32_EPS)
