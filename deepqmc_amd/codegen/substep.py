@@ -32,26 +32,8 @@ OP_ORBITALS, OP_SLOGDET, OP_FINAL, OP_ATTENTION, OP_CONST = 8, 9, 10, 11, 12
 
 STAGE_FRAGS = 16          # 1 KB fragments per ring stage
 RING = 3
-DEFAULTS = dict(
-    pf=6,                 # tape fragments read ahead of their first use
-    fold_tanh=1,          # 1: the factor 2 log2(e) of tanh(x) = 1 - 2 / (1 + exp2(x 2 log2 e)) is folded into the packed weights and bias
-    barrier='asm',       # 'sync': __syncthreads() per ring stage; 'asm': s_waitcnt lgkmcnt(k) + s_barrier (the wave's own ring
-                          #   stores are older than its last k LDS reads: no drain of the prefetched fragments)
-    wpos=(1, 4, 7, 9),    # fragment positions inside a stage at which a quarter of the next stage is stored / the one after requested
-    lazy_ring=1,          # 1: the first ring stage is stored and awaited at the first tape read, not in the prologue
-    dpp_fold=0,           # 1: sender gathers / sums over electrons as v_fmac_f32_dpp / v_add_f32_dpp (one instruction) instead of v_mov_b32_dpp + op
-    sgb=0,                # > 0: every scheduling region (between the sched_barriers of group_barrier) ends with a
-                          #   sched_group_barrier pipeline {1 MFMA, sgb VALU} x its MFMAs
-    defer_epi=0,          # 1: the epilogue (activation, residual, bf16 split) of a layer is interleaved with the MFMAs of the NEXT linear layer
-                          #   when nothing in between reads its output (measured: 57.1 vs 57.0 us -- the wave is bound by instruction issue, not by order)
-    share_means=1,        # 1: the per-walker (spin-mean) pieces of a wide layer are multiplied ONCE for the 16 walkers of a workgroup --
-                          #   each wave takes a quarter of the output blocks with the walkers as the 16 MFMA columns -- instead of 4 x per tile
-    producer=0,           # 1: a fifth wave per workgroup fills the weight ring (global -> registers -> LDS, one stage per barrier interval);
-                          #   the four computing waves only read it
-    waves=4,              # waves (= tiles of 4 walkers) per workgroup: 4 (one per SIMD) or 8 (two per SIMD)
-    sched='',             # -amdgpu-sched-strategy of the translation unit ('' = the compiler's default)
-    group_barrier=1,      # 1: __builtin_amdgcn_sched_barrier(0) in front of every batch of tape reads
-)
+PF = 6                    # tape fragments read ahead of their first use
+WPOS = (1, 4, 7, 9)       # fragment positions inside a stage at which a quarter of the next stage is stored / the one after requested
 N_OP_I = 28
 
 
@@ -109,13 +91,8 @@ class GBuf:
 
 
 class Gen:
-    def __init__(self, name, n_up, n_down, n_nuc, n_det, bufs, ops, itable, **opts):
+    def __init__(self, name, n_up, n_down, n_nuc, n_det, bufs, ops, itable):
         self.name = name
-        self.opt = dict(DEFAULTS)
-        for k_, v_ in opts.items():
-            if k_ not in self.opt:
-                raise KeyError(k_)
-            self.opt[k_] = v_
         self.n_up, self.n_down, self.n_nuc, self.K = n_up, n_down, n_nuc, n_det
         self.N = n_up + n_down
         self.bufs, self.ops, self.itable = bufs, ops, [int(v) for v in itable]
@@ -246,7 +223,7 @@ class Gen:
                     x = f'{src}[{bb}][{s}]'
                     acc = f'quad_bcast<{e0}>({x})'        # (0 + x_e0) + x_e1 ... as the generic kernel's loop
                     for e in range(e0 + 1, e1):
-                        acc = f'quad_add<{e}, {e}, {e}, {e}>({acc}, {x})' if self.opt['dpp_fold'] else f'({acc} + quad_bcast<{e}>({x}))'
+                        acc = f'({acc} + quad_bcast<{e}>({x}))'
                     vals.append(f'({acc} * {inv!r}f)' if e1 > e0 else '0.0f')
             for j in range(4):
                 if vals[2 * j] == '0.0f':
@@ -272,7 +249,6 @@ class Gen:
                 self.op_feat_ee(op)
             elif op.kind == OP_LINEAR:
                 self.op_linear(k, op)
-                self.stream.append(('ee', k))
             elif op.kind == OP_SPIN_MEAN:
                 self.op_spin_mean(op)
             elif op.kind == OP_CONV:
@@ -447,7 +423,8 @@ class Gen:
                 raise Unsupported('residual source without f32 registers')
         self.c(f'// op {k} LINEAR -> buffer {dst}: {len(chunks)} k-chunks x {nb} blocks x {len(rbs)} row block(s), act {act}' + (f', residual {res}' if res >= 0 else ''))
         tag = f'L{k}'
-        wscale = 2.8853900817779268 if (act == 1 and self.opt['fold_tanh']) else 1.0      # 2 log2(e): tanh(x) = 1 - 2 / (1 + 2^(x 2 log2 e))
+        # the factor 2 log2(e) of tanh(x) = 1 - 2 / (1 + 2^(x 2 log2 e)) is folded into the packed weights and bias
+        wscale = 2.8853900817779268 if act == 1 else 1.0
         # ---- bias fragments ----
         bias_frag = []
         if bias_off >= 0:
@@ -474,10 +451,10 @@ class Gen:
                     self.c(f'{tag}b_{rb}[{bb}] = f32x4{{0, 0, 0, 0}};')
                 if dual:
                     self.c(f'{tag}s_{rb}[{bb}] = f32x4{{0, 0, 0, 0}};')
-        self.stream.append(('lb', k))
-        # ---- per-walker pieces shared by the four tiles of the workgroup (option share_means) ----
+        # ---- per-walker (spin-mean) pieces of a wide layer, multiplied ONCE for the 16 walkers of the workgroup: each wave takes
+        # a quarter of the output blocks with the walkers as the 16 MFMA columns ----
         shared = [ch for ch in chunks if ch[0] == 'blk' and ch[1].lazy_mean is not None]
-        do_share = bool(self.opt['share_means']) and self.opt['waves'] == 4 and rbs == ('n',) and nb % 4 == 0 and len(shared) >= 4
+        do_share = rbs == ('n',) and nb % 4 == 0 and len(shared) >= 4
         if do_share:
             chunks = [ch for ch in chunks if not (ch[0] == 'blk' and ch[1].lazy_mean is not None)]
             nbw = nb // 4                                      # output blocks per wave
@@ -559,7 +536,6 @@ class Gen:
                         for rb in rbs:
                             acc = f'{tag}s_{rb}[{bb}]' if (dual and wp + xp == 2) else f'{tag}b_{rb}[{bb}]'
                             self.c(f'{acc} = mfma_bf16(t{fr[bb] + wp}, {ops_b[rb][xp]}, {acc});')
-        self.stream.append(('le', k))
         if do_share:
             self.c('{ const int xr_ = ((wave * 4 + (c >> 2)) + 16 * g) * 16;')
             for bb in range(nb):
@@ -568,7 +544,6 @@ class Gen:
         if len(chunks) * nb >= 64:
             self.stamp(f'op {k} epilogue')
         # ---- epilogue ----
-        self.stream.append(('eb', k))
         scale = '0.70710678118654752440f' if normalize else None
         for rb in rbs:
             drb = rb
@@ -577,7 +552,7 @@ class Gen:
                 for s in range(4):
                     e = f'({tag}s_{rb}[{bb}][{s}] + {tag}b_{rb}[{bb}][{s}])' if dual else f'({tag}b_{rb}[{bb}][{s}])'
                     if act == 1:
-                        e = f'tanh_scaled{e}' if wscale != 1.0 else f'tanh_value{e}'
+                        e = f'tanh_scaled{e}'
                     elif act == 2:
                         e = f'silu_value{e}'
                     if gres is not None:
@@ -612,8 +587,6 @@ class Gen:
                                 self.c(f'{gd.name}p_{drb}[0][{tt}].w[{j}] = 0u; {gd.name}p_{drb}[1][{tt}].w[{j}] = 0u; {gd.name}p_{drb}[2][{tt}].w[{j}] = 0u;')
                             else:
                                 self.c(f'split2({src[2 * j]}, {src[2 * j + 1]}, {gd.name}p_{drb}[0][{tt}].w[{j}], {gd.name}p_{drb}[1][{tt}].w[{j}], {gd.name}p_{drb}[2][{tt}].w[{j}]);')
-
-    # (the marker that closes the epilogue is appended by run())
 
     def op_spin_mean(self, op):
         src, dst = op.i[0], op.i[1]
@@ -680,9 +653,6 @@ class Gen:
             for s in range(4):
                 e = None
                 for d in ds:
-                    if self.opt['dpp_fold']:
-                        e = f'quad_fmac<{0 ^ d}, {1 ^ d}, {2 ^ d}, {3 ^ d}>({e if e is not None else "0.0f"}, {gw.name}_e{d}[{bb}][{s}], {gh.name}_n[{bb}][{s}])'
-                        continue
                     term = f'{gw.name}_e{d}[{bb}][{s}] * quad_xor<{d}>({gh.name}_n[{bb}][{s}])'
                     e = f'(0.0f + {term})' if e is None else f'({e} + {term})'
                 self.c(f'{gd.name}_n[{db}][{s}] = {e};')
@@ -709,7 +679,7 @@ class Gen:
                 x = f'{gs.name}_n[{bb}][{s}]'
                 acc = f'(0.0f + quad_bcast<0>({x}))'
                 for e in range(1, self.N):
-                    acc = f'quad_add<{e}, {e}, {e}, {e}>({acc}, {x})' if self.opt['dpp_fold'] else f'({acc} + quad_bcast<{e}>({x}))'
+                    acc = f'({acc} + quad_bcast<{e}>({x}))'
                 self.c(f'{gd.name}_n[{bb}][{s}] = {acc};')
         if n_lin:
             self.c(f'BfFrag {gd.name}p_n[3][{gd.nch}];')
@@ -830,115 +800,15 @@ class Gen:
             self.c(f'logpsi += (double)__shfl({gj.name}_n[0][0], (threadIdx.x & 63) & 15, 64);')
         self.tail = True
 
-    @staticmethod
-    def op_rw(op):
-        i = op.i
-        if op.kind in (OP_FEAT_EN, OP_FEAT_EE, OP_CONST):
-            return set(), {i[0]}
-        if op.kind == OP_LINEAR:
-            rd = {i[1 + 4 * p] for p in range(i[0])}
-            if i[25] >= 0:
-                rd.add(i[25])
-            return rd, {i[17]}
-        if op.kind in (OP_SPIN_MEAN, OP_ROW_SUM):
-            return {i[0]}, {i[1]}
-        if op.kind == OP_CONV:
-            return {i[0], i[1]}, {i[2]}
-        if op.kind == OP_EDGE_SUM:
-            return {i[0]}, {i[2]}
-        if op.kind == OP_ORBITALS:
-            return {i[0]}, {i[1]}
-        if op.kind == OP_FINAL:
-            return ({i[0]} if i[0] >= 0 else set()), set()
-        return set(), set()
-
-    def can_defer(self, k, k2):
-        """may the epilogue of LINEAR op k run inside the product loop of LINEAR op k2 > k?"""
-        rd_k, wr_k = self.op_rw(self.ops[k])
-        dst = self.ops[k].i[17]
-        for j in range(k + 1, k2 + 1):
-            rd, wr = self.op_rw(self.ops[j])
-            if dst in rd:
-                return False
-            if j < k2 and (wr & (rd_k | {dst})):
-                return False
-            # spin means are produced where they are consumed: a consumer of a mean of dst reads dst
-            if self.ops[j].kind == OP_LINEAR:
-                for p in range(self.ops[j].i[0]):
-                    sb = self.ops[j].i[1 + 4 * p]
-                    for o2 in self.ops[:j]:
-                        if o2.kind == OP_SPIN_MEAN and o2.i[1] == sb and o2.i[0] == dst:
-                            return False
-        return True
-
-    def defer_epilogues(self):
-        st = self.stream
-        out = []
-        i = 0
-        while i < len(st):
-            it = st[i]
-            if it[0] == 'eb':
-                k = it[1]
-                j = next(n for n in range(i, len(st)) if st[n] == ('ee', k))
-                E = st[i + 1:j]
-                n = next((q for q in range(j + 1, len(st)) if st[q][0] == 'lb'), None)
-                if self.opt['defer_epi'] and n is not None and self.can_defer(k, st[n][1]):
-                    k2 = st[n][1]
-                    m = next(q for q in range(n, len(st)) if st[q] == ('le', k2))
-                    body = st[n + 1:m]
-                    mf = [q for q, b in enumerate(body) if b[0] == 'c' and 'mfma_bf16(' in b[1]]
-                    if mf and E:
-                        out.extend(st[j + 1:n])
-                        per = -(-len(E) // len(mf))
-                        nb_, e0 = [], 0
-                        for q, b in enumerate(body):
-                            nb_.append(b)
-                            if q in mf and e0 < len(E):
-                                nb_.extend(E[e0:e0 + per])
-                                e0 += per
-                        nb_.extend(E[e0:])
-                        out.extend(nb_)
-                        i = m
-                        continue
-                out.extend(E)
-                i = j + 1
-                continue
-            out.append(it)
-            i += 1
-        self.stream = [x for x in out if x[0] not in ('lb', 'le', 'eb', 'ee')]
-
-    def add_group_pipelines(self, lines):
-        res, region = [], []
-
-        def flush():
-            m = sum(1 for l in region if 'mfma_bf16(' in l)
-            v = sum(5 * l.count('tanh_') + 11 * l.count('split2(') + 2 * l.count('quad_') for l in region)
-            res.extend(region)
-            if m >= 2 and v >= 4:
-                q = min(int(self.opt['sgb']), -(-v // m))
-                for _ in range(m):
-                    res.append(f'  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, {q}, 0);')
-            region.clear()
-        for l in lines:
-            if '__builtin_amdgcn_sched_barrier(0);' in l:
-                flush()
-                res.append(l)
-            else:
-                region.append(l)
-        res.extend(region)
-        return res
-
     # ---- final assembly ----
     def source(self):
         self.run()
-        self.defer_epilogues()
         n_stage = (self.n_frag + STAGE_FRAGS - 1) // STAGE_FRAGS
         tape_bytes = n_stage * STAGE_FRAGS * 1024
         lds_bytes = RING * STAGE_FRAGS * 1024 + self.xch_bytes
         out: List[str] = []
         A = out.append
         kname = f'k_substep_{self.name}'
-        A('// hipcc-flags:' + (f' -mllvm -amdgpu-sched-strategy={self.opt["sched"]}' if self.opt['sched'] else ''))
         A(f'// GENERATED by deepqmc_amd/codegen/substep.py for program hash 0x{self.hash:016x} -- do not edit; regenerate with')
         A('//   python -m deepqmc_amd.codegen')
         A('// One Metropolis sub-step (propose -> psi -> accept) of a tile of 4 walkers per wave, activations in registers, weights from')
@@ -948,22 +818,17 @@ class Gen:
         A('namespace dqmc {')
         A('namespace {')
         A('using namespace dqmc::spec;')
-        nw = self.opt['waves']
-        prod = bool(self.opt['producer'])
-        nthr = 64 * nw
-        npc = (STAGE_FRAGS * 64) // nthr      # 16-byte pieces per thread and ring stage
-        nthr_launch = nthr + (64 if prod else 0)
-        wpos = list(self.opt['wpos'])[:npc] if len(self.opt['wpos']) >= npc else list(self.opt['wpos'])
-        if len(wpos) != npc:
-            raise ValueError('wpos must name one position per piece')
-        A(f'template <bool PROF> __global__ void __launch_bounds__({nthr_launch}) {kname}(const SpecArgs a) {{')
+        nthr = 256                            # 4 waves (= tiles of 4 walkers) per workgroup, one per SIMD
+        npc = len(WPOS)                       # 16-byte pieces per thread and ring stage
+        assert npc * nthr == STAGE_FRAGS * 64
+        A(f'template <bool PROF> __global__ void __launch_bounds__({nthr}) {kname}(const SpecArgs a) {{')
         A('  HIP_DYNAMIC_SHARED(char, smem_raw)')
         A('  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;')
         A('  const int c = lane & 15, g = lane >> 4, wl = c >> 2, el = c & 3;')
         A('  const int wave_s = __builtin_amdgcn_readfirstlane(wave);')
         A('  (void)wave_s;')
         A('  (void)wl;')
-        A(f'  const long bw = (long)blockIdx.x * {4 * nw} + wave * 4 + (c >> 2);      // this lane\'s walker')
+        A('  const long bw = (long)blockIdx.x * 16 + wave * 4 + (c >> 2);      // this lane\'s walker')
         A('  const bool live = bw < a.B;')
         A('  const long bc = live ? bw : (long)a.B - 1;')
         A('  const char* ring_lane = smem_raw + lane * 16;')
@@ -971,14 +836,12 @@ class Gen:
         A('  V16* ring_t = reinterpret_cast<V16*>(smem_raw) + tid;')
         A(f'  const TapeRsrc tape = tape_rsrc(a.tape, {tape_bytes});')
         A('  const int tid16 = tid * 16;')
-        A('@@PRODUCER@@')
         A('  const bool stamp_ = PROF && a.prof != nullptr && blockIdx.x == 0 && lane == 0;')
         A('  if (stamp_) a.prof[wave * 256] = clock64();')
-        if not prod:
-            A('  // ring prologue: stage 0 -> LDS, stage 1 -> registers')
-            A('  V16 ' + ', '.join(f'rq{q}' for q in range(npc)) + ';')
-            for q in range(npc):
-                A(f'  rq{q} = tape_load<{q * nthr * 16}>(tape, tid16);')
+        A('  // ring prologue: stage 0 -> LDS, stage 1 -> registers')
+        A('  V16 ' + ', '.join(f'rq{q}' for q in range(npc)) + ';')
+        for q in range(npc):
+            A(f'  rq{q} = tape_load<{q * nthr * 16}>(tape, tid16);')
         # sampler state + proposal while the first stage is in flight
         A('  // step size of this sub-step from the previous one\'s acceptance (the arithmetic of k_tau_update)')
         A('  float tau;')
@@ -1006,13 +869,8 @@ class Gen:
         A('  const float u_b = reinterpret_cast<const float*>(a.mc.unif)[bc];')
         A('  const int age_b = a.mc.age[bc];')
         A('  const float px = __shfl(rp, c, 64), py = __shfl(rp, c + 16, 64), pz = __shfl(rp, c + 32, 64);')
-        events = []      # the workgroup barriers of the computing waves, in order: what the producer wave has to match
-
+        # the first ring stage is stored and awaited at the first tape read, not here: the proposal above overlaps its load
         def ring_start():
-            if prod:
-                events.append(('start',))
-                A('  __syncthreads();')
-                return
             for q in range(npc):
                 A(f'  ring_t[{q * nthr}] = rq{q};')
             if n_stage > 1:
@@ -1020,31 +878,28 @@ class Gen:
                     A(f'  rq{q} = tape_load<{(STAGE_FRAGS * 64 + q * nthr) * 16}>(tape, tid16);')
             A('  __syncthreads();')
         started = False
-        if not self.opt['lazy_ring']:
-            ring_start(); started = True
         # body with the tape reads hoisted PF fragments ahead
         emitted = 0
 
         # LDS reads a wave issues between its last ring store of a stage and the barrier that ends the stage
         def reads_after_last_store(s):
-            return sum(1 for f2 in range(s * STAGE_FRAGS + wpos[-1], min(self.n_frag, (s + 1) * STAGE_FRAGS)) if self.frag_kind[f2] == 0)
+            return sum(1 for f2 in range(s * STAGE_FRAGS + WPOS[-1], min(self.n_frag, (s + 1) * STAGE_FRAGS)) if self.frag_kind[f2] == 0)
 
         def emit_read(f):
             nonlocal started
             if not started:
                 ring_start(); started = True
             s, o = divmod(f, STAGE_FRAGS)
-            if o == 0 and s >= 1 and prod:
-                events.append(('ring', s))
-                A('  ring_barrier0();')
-            elif o == 0 and s >= 1:
+            if o == 0 and s >= 1:
+                # s_waitcnt lgkmcnt(kk) + s_barrier: the wave's own ring stores are older than its last kk LDS reads, so the
+                # prefetched fragments need not drain
                 kk = min(6, reads_after_last_store(s - 1))
-                if self.opt['barrier'] == 'asm' and kk >= 1:
+                if kk >= 1:
                     A(f'  ring_barrier<{kk}>();')
                 else:
                     A('  __syncthreads();')
-            if o in wpos and not prod:
-                q = wpos.index(o)
+            if o in WPOS:
+                q = WPOS.index(o)
                 if s + 1 < n_stage:
                     A(f'  ring_t[{((s + 1) % RING) * STAGE_FRAGS * 64 + q * nthr}] = rq{q};')
                 if s + 2 < n_stage:
@@ -1059,15 +914,13 @@ class Gen:
                 self.stamp_labels.append(v)
                 A(f'  if (stamp_) a.prof[wave * 256 + {n_stamp}] = clock64();      // before {v}')
             elif kind in ('u', 'x'):
-                target = min(self.n_frag, int(v) + 1 + (self.opt['pf'] if kind == 'u' else 0))
-                if self.opt['group_barrier'] and emitted < target:
+                target = min(self.n_frag, int(v) + 1 + (PF if kind == 'u' else 0))
+                if emitted < target:        # a scheduling fence in front of every batch of tape reads
                     A('  __builtin_amdgcn_sched_barrier(0);')
                 while emitted < target:
                     emit_read(emitted)
                     emitted += 1
             else:
-                if '__syncthreads();' in v:
-                    events.append(('x',))
                 A('  ' + v)
         while emitted < self.n_frag:
             emit_read(emitted)
@@ -1096,44 +949,12 @@ class Gen:
         A('  if (lane == 0 && n_acc) atomicAdd(a.mc.counters + a.mc.s % 3, n_acc);')
         A(f'  if (stamp_) a.prof[wave * 256 + {n_stamp + 1}] = clock64();')
         A('}')
-        pl = []
-        if prod:
-            P = pl.append
-            P(f'  if (wave == {nw}) {{      // the producer wave: stage s + 1 goes into the ring while the computing waves read stage s')
-            P('    char* ring_w = smem_raw + lane * 16;')
-            P('    const int l16 = lane * 16;')
-
-            def copy_stage(st_):
-                if st_ >= n_stage:
-                    return
-                P(f'    {{ V16 v_[{STAGE_FRAGS}];')
-                for q in range(STAGE_FRAGS):
-                    P(f'      v_[{q}] = tape_load<{(st_ * STAGE_FRAGS + q) * 1024}>(tape, l16);')
-                for q in range(STAGE_FRAGS):
-                    P(f'      *reinterpret_cast<V16*>(ring_w + {(st_ % RING) * STAGE_FRAGS * 1024 + q * 1024}) = v_[{q}];')
-                P('    }')
-            for ev in events:
-                if ev[0] == 'start':
-                    copy_stage(0)
-                    copy_stage(1)
-                    P('    __syncthreads();')
-                elif ev[0] == 'ring':
-                    P('    __syncthreads();')
-                    copy_stage(ev[1] + 1)
-                else:
-                    P('    __syncthreads();')
-            P('    return;')
-            P('  }')
-        k_ = out.index('@@PRODUCER@@')
-        out[k_:k_ + 1] = pl
-        if self.opt['sgb']:
-            out[:] = self.add_group_pipelines(out)
         A(f'void launch_{self.name}(hipStream_t st, const SpecArgs& a, int n_blocks) {{')
         A(f'  static const bool lds_ok_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&{kname}<true>), hipFuncAttributeMaxDynamicSharedMemorySize, {lds_bytes}) == hipSuccess &&')
         A(f'                             hipFuncSetAttribute(reinterpret_cast<const void*>(&{kname}<false>), hipFuncAttributeMaxDynamicSharedMemorySize, {lds_bytes}) == hipSuccess;')
         A('  (void)lds_ok_;')
-        A(f'  if (a.prof) hipLaunchKernelGGL(HIP_KERNEL_NAME({kname}<true>), dim3((unsigned)n_blocks), dim3({nthr_launch}), {lds_bytes}, st, a);')
-        A(f'  else hipLaunchKernelGGL(HIP_KERNEL_NAME({kname}<false>), dim3((unsigned)n_blocks), dim3({nthr_launch}), {lds_bytes}, st, a);')
+        A(f'  if (a.prof) hipLaunchKernelGGL(HIP_KERNEL_NAME({kname}<true>), dim3((unsigned)n_blocks), dim3({nthr}), {lds_bytes}, st, a);')
+        A(f'  else hipLaunchKernelGGL(HIP_KERNEL_NAME({kname}<false>), dim3((unsigned)n_blocks), dim3({nthr}), {lds_bytes}, st, a);')
         A('}')
         A(f'const SpecTapeEntry entries_{self.name}[] = {{')
         for e in self.entries:
@@ -1146,14 +967,14 @@ class Gen:
         A(f'const char* const stamps_{self.name} = "' + '|'.join(self.stamp_labels) + '";')
         A('}  // namespace')
         A(f'const SpecKernel* spec_kernel_{self.name}() {{')
-        A(f'  static const SpecKernel k = {{0x{self.hash:016x}ull, "{self.name}", {4 * nw}, {lds_bytes}, {tape_bytes}, {len(self.entries)}, entries_{self.name}, maps_{self.name}, launch_{self.name}, stamps_{self.name}}};')
+        A(f'  static const SpecKernel k = {{0x{self.hash:016x}ull, "{self.name}", 16, {lds_bytes}, {tape_bytes}, {len(self.entries)}, entries_{self.name}, maps_{self.name}, launch_{self.name}, stamps_{self.name}}};')
         A('  return &k;')
         A('}')
         A('}  // namespace dqmc')
         return '\n'.join(out) + '\n'
 
 
-def generate(name, program, **opts) -> str:
+def generate(name, program) -> str:
     """HIP source of the specialised sub-step kernel of `program` (deepqmc_amd.program.Program)."""
-    g = Gen(name, program.n_up, program.n_down, program.n_nuc, program.spec.n_determinants, program.bufs, program.ops, program.itable, **opts)
+    g = Gen(name, program.n_up, program.n_down, program.n_nuc, program.spec.n_determinants, program.bufs, program.ops, program.itable)
     return g.source()

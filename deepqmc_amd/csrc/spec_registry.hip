@@ -2,7 +2,6 @@
 // deepqmc_amd/codegen) and the host-side packer of their weight tapes.
 #include "spec_device.h"
 
-#include <cstdlib>
 #include <cstring>
 
 namespace dqmc {
@@ -19,15 +18,11 @@ static const SpecGetter kSpecKernels[] = {
     nullptr};
 
 const SpecKernel* find_spec_kernel(uint64_t hash) {
-  const char* want = getenv("DQMC_SPEC_VARIANT");      // development: several generated variants of one program
-  const SpecKernel* first = nullptr;
   for (const SpecGetter* k = kSpecKernels; *k; ++k) {
     const SpecKernel* sk = (*k)();
-    if (sk->hash != hash) continue;
-    if (!first) first = sk;
-    if (want && strcmp(want, sk->name) == 0) return sk;
+    if (sk->hash == hash) return sk;
   }
-  return first;
+  return nullptr;
 }
 
 // piece pl (0..2) of the three-bf16 split of a float (round to nearest even, exact residuals: common.h bf_split8)
