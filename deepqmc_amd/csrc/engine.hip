@@ -59,6 +59,7 @@ struct dqmc_ctx {
   virtual int local_energy(const void* r, const void* R, int B, void* e_loc, void* stats, void* grad, void* logpsi,
                            int32_t* sign) = 0;
   virtual int psi_grad(const void* r, const void* R, int B, void* logpsi, int32_t* sign, void* grad) = 0;
+  virtual int log_psi_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* logpsi, int32_t* sign) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -475,6 +476,7 @@ struct Engine : dqmc_ctx {
 #include "engine_refine.inl"
 #include "engine_ecp.inl"
 #include "engine_mcmc.inl"
+#include "engine_grad.inl"
 };
 
 }  // namespace
@@ -536,6 +538,12 @@ int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logp
   if (!ctx || !r || !R || !grad) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->psi_grad(r, R, B, logpsi, sign, grad);
+}
+int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, void* logpsi,
+                     int32_t* sign) {
+  if (!ctx || !r || !R || !grad) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->log_psi_vjp(r, R, B, cot, grad, logpsi, sign);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

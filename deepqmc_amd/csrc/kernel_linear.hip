@@ -1234,3 +1234,5 @@ template void launch_linear_chain<float>(hipStream_t, const LinArgs<float>&);
 template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 
 }  // namespace dqmc
+
+#include "kernels_grad.inl"

@@ -341,4 +341,86 @@ void launch_refine_scatter(hipStream_t st, const int32_t* idx, const int32_t* co
                            const double* g64, const double* lp64, const int32_t* sg64, float* e_loc, float* stats,
                            long stats_ld, float* grad, float* logpsi, int32_t* sign);
 
+// ---- kernels_grad.inl (included by kernel_linear.hip): reverse pass of the value-only program (dqmc_log_psi_vjp) ----
+template <typename real> struct LinBwdPiece {
+  const real* X;      // the piece's source buffer (forward activations)
+  real* dX;           // its adjoint (same layout), or nullptr
+  int ld, rpw, r0, K, bcast;   // K: unpadded width
+  int w_row;          // first row of the piece's block in W
+};
+template <typename real> struct LinBwdArgs {
+  int n_pieces;
+  LinBwdPiece<real> piece[4];
+  const real* W;      // [sum pad4(K)][ldw]
+  int ldw, nout, nrows, B, act;
+  const real* Z;      // recomputed pre-activations real[B][nrows][ldw]
+  real* dZ;           // scratch of the same shape
+  real* dZs;          // scratch real[B][ldw] (broadcast pieces)
+  const real* dY;     // adjoint of the destination buffer
+  int ld_dst, rpw_dst, r0_dst, col0_dst;
+  real* dres;         // adjoint of the residual input, or nullptr
+  int ld_res, rpw_res, r0_res;
+  real res_scale;
+  double* dW;         // gradient of W (double, flat weight layout), accumulated
+  double* dbias;      // gradient of the bias, or nullptr
+  double* part;       // split-K scratch: grad_dw_part_doubles of the largest block
+};
+// Split-K of the weight-gradient GEMMs: about GRAD_DW_WAVES waves (16 x 16 tiles x splits) per launch, at most GRAD_DW_MAX_SPLIT
+// splits (the fixed-order second pass reads every split of an entry serially) and at least 64 rows per split
+constexpr long GRAD_DW_WAVES = 4096, GRAD_DW_MAX_SPLIT = 64;
+inline long grad_dw_splits(int kt, int nt, long M) {
+  const long tiles = (long)kt * nt;
+  long s = (GRAD_DW_WAVES + tiles - 1) / tiles;
+  if (s > GRAD_DW_MAX_SPLIT) s = GRAD_DW_MAX_SPLIT;
+  const long cap = (M + 63) / 64;
+  if (s > cap) s = cap;
+  return s < 1 ? 1 : s;
+}
+// doubles of split partials a block of kt x nt tiles needs at most (any M)
+inline size_t grad_dw_part_doubles(int kt, int nt) {
+  const long tiles = (long)kt * nt;
+  long s = (GRAD_DW_WAVES + tiles - 1) / tiles;
+  if (s > GRAD_DW_MAX_SPLIT) s = GRAD_DW_MAX_SPLIT;
+  return (size_t)s * tiles * 256;
+}
+template <typename real> void launch_linear_bwd(hipStream_t st, const LinBwdArgs<real>& a);
+// out[m] += sum_c in[c * stride + m] (c < count, m < n_out), fixed summation order
+template <typename real> void launch_colsum(hipStream_t st, const real* in, long count, long stride, int n_out, double* out);
+void launch_colsum_f64(hipStream_t st, const double* in, long count, long stride, int n_out, double* out);
+template <typename real> void launch_spin_mean_bwd(hipStream_t st, real* dx, const real* dm, int B, int N, int n_up, int width);
+template <typename real> void launch_row_sum_bwd(hipStream_t st, real* dx, const real* ds, int B, int rows, int width);
+// edge-row adjoint of CONV (hx given) / EDGE_SUM (hx == nullptr, factor `scale`) through rtab[row][Sr][2] = (receiver, sender)
+template <typename real>
+void launch_edge_rows_bwd(hipStream_t st, real* dwe, int we_rows, int we_w, const real* hx, int hx_rows, int hx_w, const real* dout,
+                          int out_w, int col0, const int32_t* rtab, int Sr, int W, int B, int N, double scale);
+// sender adjoint of CONV through stab[sender row][Ss][2] = (receiver, edge row)
+template <typename real>
+void launch_conv_send_bwd(hipStream_t st, real* dhx, int hx_rows, int hx_w, const real* we, int we_rows, int we_w, const real* dout,
+                          int out_w, int col0, const int32_t* stab, int Ss, int W, int B, int N);
+template <typename real> struct FinalBwdArgs {
+  const real* r;
+  const double* logdet;   // [B][K] (TP = 1)
+  const int32_t* sign_k;
+  const real* cc;         // conf_coeff [K] or nullptr
+  const real* alphas;     // [2]
+  int cusp_kind;
+  double same_scale, anti_scale, eps;
+  const real* logpsi;
+  const int32_t* sign;
+  const real* cot;        // [B] or nullptr (ones)
+  real* djas;             // adjoint of the Jastrow buffer or nullptr
+  int jas_ld;
+  double* dL;             // out [B][K]: cot * p_k
+  double* pw;             // out [B][K + 2]: per-walker gradient of conf_coeff and of {same_alpha, anti_alpha}
+  int B, N, n_up, K;
+};
+template <typename real> void launch_final_bwd(hipStream_t st, const FinalBwdArgs<real>& a);
+constexpr int GRAD_GJ_NMAX = 44;      // largest N of the Gauss-Jordan inverse of k_slogdet_bwd (as the forward slogdet)
+template <typename real> void launch_slogdet_bwd(hipStream_t st, const real* orb, int orb_w, const double* dL, real* dorb, int B, int K, int N);
+// pw: per-walker partials double[B][4][K*N][n_nuc*n_env] of the pi_up / pi_down / zeta_up / zeta_down tables
+template <typename real>
+void launch_orbitals_bwd(hipStream_t st, const real* r, const real* R, const real* bf, int bf_w, real* dbf, const real* dorb, int orb_w,
+                         const real* pi_up, const real* pi_dn, const real* ze_up, const real* ze_dn, double* pw, int B, int N, int n_up,
+                         int n_env, int n_nuc, int K, double eps);
+
 }  // namespace dqmc

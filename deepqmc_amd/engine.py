@@ -141,6 +141,26 @@ class Engine:
                                           sign.data_ptr()))
         return sign, logpsi
 
+    # ---- jax.vjp of the batched log|psi| with respect to the parameters ----
+    def log_psi_vjp(self, r, cot=None, R=None):
+        """sum_b cot[b] d log|psi(r_b)| / d w over the flat weight buffer (loss/loss_function.py:59-75).
+        Returns (sign, logpsi, grad_flat): grad_flat is float64 [n_weights] on the engine's device; map it onto the
+        parameter tree with `self.program.unflatten_grad`.  cot None = all ones."""
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+        c = None
+        if cot is not None:
+            c = self._t(cot).reshape(-1)
+            self.check_walker_vector('cot', c, B)
+        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
+        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+        grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_log_psi_vjp(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B,
+                                              c.data_ptr() if c is not None else None, grad.data_ptr(),
+                                              logpsi.data_ptr(), sign.data_ptr()))
+        return sign, logpsi, grad
+
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None):
         """`rng` (an int seed or None) keys the random quadrature rotation of the non-local ECP term

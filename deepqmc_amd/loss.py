@@ -1,5 +1,6 @@
 """Batch-level callers of the hot path: `compute_local_energy` (reference
-src/deepqmc/loss/energy.py:19-60) and `compute_psi_ratio` (loss/overlap.py:19-99), with the
+src/deepqmc/loss/energy.py:19-60), `compute_psi_ratio` (loss/overlap.py:19-99) and the training gradient of the
+energy loss `compute_energy_loss_and_grad` (loss/loss_function.py:191-226), with the
 reference's `[molecule, electronic state, walker]` batch axes.  The molecule and state axes are
 host loops over HIP contexts (one per state's parameter set; the geometry of a molecule is an argument
 of the call); the walker axis is the GPU batch.  `phys_conf` is either the electron tensor r[M,S,B,N,3]
@@ -106,3 +107,53 @@ def compute_mean_overlap(psi_ratio: torch.Tensor, weight: torch.Tensor):
     iu = torch.triu_indices(S, S, offset=1, device=symm.device)
     loss = (symm[:, iu[0], iu[1]] ** 2).sum(-1).mean()
     return loss, {'overlap/pairwise/mean': symm}
+
+
+def median_clip_and_mask(x: torch.Tensor, clip_width: float = 5.0, median_center: bool = True,
+                         exclude_width: float = float('inf')):
+    """loss/clip.py:73-98 for one [B] batch: clip to center +- clip_width x mean absolute deviation (center = the median,
+    the mean of the two middle values for even B as jnp.median, or the mean); mask = deviation < exclude_width."""
+    if median_center:
+        xs = torch.sort(x).values
+        n = xs.shape[0]
+        center = 0.5 * (xs[(n - 1) // 2] + xs[n // 2])
+    else:
+        center = x.mean()
+    abs_diff = (x - center).abs()
+    mad = abs_diff.mean()
+    return torch.clamp(x, center - clip_width * mad, center + clip_width * mad), abs_diff < exclude_width
+
+
+def compute_energy_loss_and_grad(rng, hamil, ansatz, params: Sequence, phys_conf, weight=None, clip_mask_fn=median_clip_and_mask):
+    """The energy part of the reference's training step for a [1, S, B] batch: loss/loss_function.py:191-226 with
+    compute_mean_energy / compute_mean_energy_tangent (loss/energy.py:63-102) and clip_local_energy (loss/clip.py:31-47).
+    Per state s the loss gradient is one vector-Jacobian product of log|psi| (dqmc_log_psi_vjp),
+        grad_s = sum_b c_sb d log|psi_s(r_sb)| / d theta_s,   c_sb = mask_sb w_sb (clip(E)_sb - mean_b(clip(E)_s w_s)) / sum_sb mask_sb,
+    the mask count taken over all states and walkers, as the reference's masked_mean over [M, S, B].
+    Returns (loss = mean(E_loc w) over [1, S, B], [grad tree per state], stats: the hamiltonian statistics of
+    compute_local_energy and 'E_loc' [1, S, B]).  The overlap and spin penalties are not included."""
+    from .types import PhysicalConfiguration
+    r, Rs = _unpack(phys_conf)
+    if r.shape[0] != 1:
+        raise ValueError('compute_energy_loss_and_grad: one molecule per batch ([1, S, B])')
+    e_loc, stats = compute_local_energy(rng, hamil, ansatz, params, phys_conf)
+    S, B = r.shape[1], r.shape[2]
+    e64 = e_loc.double()
+    w = torch.ones_like(e64) if weight is None else torch.as_tensor(weight, dtype=torch.float64, device=e64.device).reshape(e64.shape)
+    loss = (e64 * w).mean()
+    # masked_mean over the whole [1, S, B] batch (loss/energy.py:101, utils.py:51-54): ONE mask count for all states
+    clipped = [clip_mask_fn(e64[0, s]) for s in range(S)]
+    n_mask = sum(mask.to(torch.float64).sum() for _, mask in clipped)
+    grads = []
+    for s, (e_clip, mask) in enumerate(clipped):
+        mean_e = (e_clip * w[0, s]).mean()
+        cot = mask.to(torch.float64) * w[0, s] * (e_clip - mean_e) / n_mask
+        rr = r[0, s].contiguous()
+        pc = rr if Rs[0] is None else PhysicalConfiguration(Rs[0], rr, None)
+        eng = ansatz.engine(params[s], Rs[0])
+        _, grad = ansatz.log_psi_vjp(params[s], pc, cot.to(eng.dtype).to(eng.device).contiguous())
+        grads.append(grad)
+    stats = dict(stats)
+    stats['E_loc'] = e_loc
+    return loss, grads, stats
+

@@ -97,6 +97,31 @@ class Program:
     buf_names: Dict[str, int]
     weight_slots: List[tuple]      # (offset, module, leaf, kind, meta) for repacking
     flops_per_walker: float        # F_lin = 2 * sum rows*in*out over Linear layers (unpadded)
+    # inverse of the weight packing: grad_src[j] = the parameter element flat weight j was copied from (-1: constant or
+    # padding), element ids index the leaves of grad_leaves {(module, leaf): (first id, shape)}; grad_unsupported names a
+    # packing that is not a copy (then the flat gradient cannot be mapped back)
+    grad_src: Optional[np.ndarray] = None
+    grad_leaves: Optional[Dict[Tuple[str, str], Tuple[int, tuple]]] = None
+    grad_unsupported: Optional[str] = None
+
+    def unflatten_grad(self, g):
+        """Flat gradient over the weight buffer (dqmc_log_psi_vjp) -> haiku tree {module: {leaf: array}}: the transpose of
+        the packing (copies, zero padding, broadcasts and column scatters are summed back onto their parameter element)."""
+        if self.grad_unsupported:
+            raise NotImplementedError(f'unflatten_grad: unsupported for this program ({self.grad_unsupported})')
+        if hasattr(g, 'detach'):
+            g = g.detach().cpu().numpy()
+        g = np.asarray(g, np.float64).reshape(-1)
+        if g.size != self.grad_src.size:
+            raise ValueError(f'gradient of {g.size} entries for a weight buffer of {self.grad_src.size}')
+        n_el = sum(int(np.prod(sh)) for _, sh in self.grad_leaves.values())
+        m = self.grad_src >= 0
+        flat = np.zeros(n_el)
+        np.add.at(flat, self.grad_src[m], g[m])
+        tree: Dict[str, Dict[str, np.ndarray]] = {}
+        for (mod, leaf), (base, shape) in self.grad_leaves.items():
+            tree.setdefault(mod, {})[leaf] = flat[base:base + int(np.prod(shape))].reshape(shape)
+        return tree
 
     def c_bufs(self):
         arr = (DqmcBuf * len(self.bufs))()
@@ -129,6 +154,30 @@ class _Builder:
         self.slots: List[tuple] = []
         self.it: List[int] = []
         self.flops = 0.0
+        # inverse of the packing (Program.grad_src / grad_leaves)
+        self.src: List[np.ndarray] = []
+        self.leaves: Dict[Tuple[str, str], Tuple[int, tuple]] = {}
+        self.n_el = 0
+        self.id_override: Dict[Tuple[str, str], np.ndarray] = {}
+        self.grad_unsupported: Optional[str] = None
+
+    def ids(self, module, leaf):
+        """Element ids of parameter leaf (module, leaf), shaped like the leaf (or as overridden by a re-layout)."""
+        key = (module, leaf)
+        if key in self.id_override:
+            return self.id_override[key]
+        if key not in self.leaves:
+            shape = tuple(np.shape(self.params[module][leaf]))
+            self.leaves[key] = (self.n_el, shape)
+            self.n_el += int(np.prod(shape))
+        base, shape = self.leaves[key]
+        return base + np.arange(int(np.prod(shape))).reshape(shape)
+
+    def finish(self, prog: 'Program') -> 'Program':
+        prog.grad_src = np.concatenate(self.src).astype(np.int64)
+        prog.grad_leaves = dict(self.leaves)
+        prog.grad_unsupported = self.grad_unsupported
+        return prog
 
     # -- allocation helpers --
     def buf(self, name, rows, width):
@@ -136,12 +185,20 @@ class _Builder:
         self.names[name] = len(self.bufs) - 1
         return len(self.bufs) - 1
 
-    def push_w(self, arr, slot):
+    def push_w(self, arr, slot, src=None):
+        """src: parameter element id of every entry of `arr` (-1: none); default: the leaf itself for 'raw' slots, none
+        for constants."""
         off = self.w_len
         a = np.asarray(arr, np.float64).reshape(-1)
         n = pad4(a.size)
         buf = np.zeros(n)
         buf[:a.size] = a
+        if src is None and slot[2] == 'raw':
+            src = self.ids(slot[0], slot[1])
+        sb = np.full(n, -1, np.int64)
+        if src is not None:
+            sb[:a.size] = np.asarray(src, np.int64).reshape(-1)
+        self.src.append(sb)
         self.w.append(buf)
         self.w_len += n
         self.slots.append((off,) + slot)
@@ -158,18 +215,24 @@ class _Builder:
         W = np.asarray(p['w'], np.float64)
         assert W.shape[0] == sum(piece_K), (module, W.shape, piece_K)
         nout = W.shape[1]
-        blocks, o = [], 0
+        W_id = self.ids(module, 'w')
+        blocks, sblocks, o = [], [], 0
         for K in piece_K:
             blk = np.zeros((pad4(K), pad4(nout)))
             blk[:K, :nout] = W[o:o + K]
+            sblk = np.full((pad4(K), pad4(nout)), -1, np.int64)
+            sblk[:K, :nout] = W_id[o:o + K]
             blocks.append(blk)
+            sblocks.append(sblk)
             o += K
-        w_off = self.push_w(np.concatenate(blocks, 0), (module, 'w', 'linear_w', tuple(piece_K)))
+        w_off = self.push_w(np.concatenate(blocks, 0), (module, 'w', 'linear_w', tuple(piece_K)), np.concatenate(sblocks, 0))
         b_off = -1
         if 'b' in p:
             b = np.zeros(pad4(nout))
             b[:nout] = np.asarray(p['b'], np.float64)
-            b_off = self.push_w(b, (module, 'b', 'linear_b', (nout,)))
+            sb = np.full(pad4(nout), -1, np.int64)
+            sb[:nout] = self.ids(module, 'b')
+            b_off = self.push_w(b, (module, 'b', 'linear_b', (nout,)), sb)
         return w_off, b_off, nout
 
     def linear(self, module, pieces, dst, dst_r0, dst_col0, nrows, act, res=-1, res_r0=0, res_scale=1.0, note=''):
@@ -236,6 +299,7 @@ def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int
             raise ValueError(f'{spec.name}: the nuclear geometry R and eps are needed to compile nuclear tokens')
         from .nuclear_stream import fold
         nuc_kv, nuc_zetas = fold(params, spec, R, eps)
+        b.grad_unsupported = 'the nuclear-token stream is folded into constants and simplified envelopes (not a copy of parameters)'
     N, K, D, E = n_up + n_down, spec.n_determinants, spec.embedding_dim, spec.two_particle_dim
     S2 = 1.0 / np.sqrt(2.0)
 
@@ -390,10 +454,11 @@ def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int
     if spec.cusp is not None and spec.cusp_trainable_alpha:
         cm = params[f'{WF}/~/electronic_cusp_asymptotic']
         al_off = b.push_w(np.array([float(cm['same_alpha']), float(cm['anti_alpha'])]),
-                          (f'{WF}/~/electronic_cusp_asymptotic', ('same_alpha', 'anti_alpha'), 'alphas', ()))
+                          (f'{WF}/~/electronic_cusp_asymptotic', ('same_alpha', 'anti_alpha'), 'alphas', ()),
+                          [b.ids(f'{WF}/~/electronic_cusp_asymptotic', nm).reshape(-1)[0] for nm in ('same_alpha', 'anti_alpha')])
     else:
         al_off = b.push_w(np.array([spec.cusp_alpha, spec.cusp_alpha]), ('', '', 'const', ()))
     b.ops.append(Op(OP_FINAL, [jas, cc_off, cusp_kind, al_off], [spec.cusp_same_scale, spec.cusp_anti_scale, 0, 0],
                     note='CI sum + cusp + Jastrow (+ potentials, E_loc)'))
-    return Program(spec, n_up, n_down, n_nuc, b.bufs, b.ops, np.concatenate(b.w), np.asarray(b.it, np.int32),
-                   b.names, b.slots, b.flops)
+    return b.finish(Program(spec, n_up, n_down, n_nuc, b.bufs, b.ops, np.concatenate(b.w), np.asarray(b.it, np.int32),
+                            b.names, b.slots, b.flops))

@@ -66,11 +66,15 @@ def compile_featurewise(fs: FeaturewiseSpec, params, n_up: int, n_down: int, n_n
     x0 = b.buf('x0', N, D)
     t_el = np.zeros((N, b.bufs[x0][1]))
     t_el[:, :D] = el[0]
-    b.ops.append(Op(OP_CONST, [x0, b.push_w(t_el, (f'{GNN}/~/electron_embedding/ElectronicEmbedding', 'embeddings', 'const', ()))],
+    s_el = np.full(t_el.shape, -1, np.int64)
+    s_el[:, :D] = b.ids(f'{GNN}/~/electron_embedding/ElectronicEmbedding', 'embeddings').reshape(-1, D)[0]
+    b.ops.append(Op(OP_CONST, [x0, b.push_w(t_el, (f'{GNN}/~/electron_embedding/ElectronicEmbedding', 'embeddings', 'const', ()), s_el)],
                     note='electron embedding (constant)'))
     xn = b.buf('nuc', n_nuc, D)
+    s_nuc = np.full((n_nuc, b.bufs[xn][1]), -1, np.int64)
+    s_nuc[:, :D] = b.ids(f'{GNN}/~/nuclei_embedding/~/embed', 'embeddings').reshape(n_nuc, D)
     b.ops.append(Op(OP_CONST, [xn, b.push_w(np.pad(nuc, ((0, 0), (0, b.bufs[xn][1] - D))),
-                                            (f'{GNN}/~/nuclei_embedding/~/embed', 'embeddings', 'const', ()))],
+                                            (f'{GNN}/~/nuclei_embedding/~/embed', 'embeddings', 'const', ()), s_nuc)],
                     note='nuclear embedding (constant)'))
 
     # ---- edges: same / anti (electron senders), ne (nuclear senders, row = nucleus * N + electron) ----
@@ -115,11 +119,16 @@ def compile_featurewise(fs: FeaturewiseSpec, params, n_up: int, n_down: int, n_n
         dims = fs.backflow.dims(D, K * n_s)
         last = f'{mod}/linear_{len(dims) - 1}'
         W, bias = np.asarray(P[last]['w'], np.float64), np.asarray(P[last]['b'], np.float64)
+        W_id, b_id = b.ids(last, 'w'), b.ids(last, 'b')
         Wf, bf_ = np.zeros((W.shape[0], K * N)), np.zeros(K * N)
+        sW, sb = np.full(Wf.shape, -1, np.int64), np.full(K * N, -1, np.int64)
         for k in range(K):                                   # orbital mu' of this spin -> column k*N + col0 + mu'
             Wf[:, k * N + col0:k * N + col0 + n_s] = W[:, k * n_s:(k + 1) * n_s]
             bf_[k * N + col0:k * N + col0 + n_s] = bias[k * n_s:(k + 1) * n_s]
+            sW[:, k * N + col0:k * N + col0 + n_s] = W_id[:, k * n_s:(k + 1) * n_s]
+            sb[k * N + col0:k * N + col0 + n_s] = b_id[k * n_s:(k + 1) * n_s]
         P[last] = {'w': Wf, 'b': bf_}
+        b.id_override[(last, 'w')], b.id_override[(last, 'b')] = sW, sb
         cur, d_in = [(x, r0, D, 0)], D
         for k, dim in enumerate(dims):
             if k < len(dims) - 1:
@@ -135,21 +144,25 @@ def compile_featurewise(fs: FeaturewiseSpec, params, n_up: int, n_down: int, n_n
     shell_col = [a * n_env + s for a in range(n_nuc) for s in range(int(mol_shells[a]))]      # table column of shell j
     assert pi.shape == (K * N, len(shell_col)) and zetas.shape == (len(shell_col),)
     L = n_nuc * n_env
+    pi_id, ze_id = b.ids(f'{WF}/~/exponential_envelopes', 'pi'), b.ids(f'{WF}/~/exponential_envelopes', 'zetas')
     tabs = {}
     for spin, lo, hi in (('up', 0, n_up), ('down', n_up, N)):
         t_pi, t_ze = np.zeros((K * N, L)), np.ones((K * N, L))
+        s_pi, s_ze = np.full((K * N, L), -1, np.int64), np.full((K * N, L), -1, np.int64)
         for k in range(K):
             for mu in range(lo, hi):
                 t_pi[k * N + mu, shell_col] = pi[k * N + mu]
+                s_pi[k * N + mu, shell_col] = pi_id[k * N + mu]
         t_ze[:, shell_col] = zetas[None]
-        tabs[spin] = (t_pi, t_ze)
-    offs = [b.push_w(tabs['up'][0], ('', '', 'const', ())), b.push_w(tabs['down'][0], ('', '', 'const', ())),
-            b.push_w(tabs['up'][1], ('', '', 'const', ())), b.push_w(tabs['down'][1], ('', '', 'const', ()))]
+        s_ze[:, shell_col] = ze_id[None]
+        tabs[spin] = (t_pi, t_ze, s_pi, s_ze)
+    offs = [b.push_w(tabs['up'][0], ('', '', 'const', ()), tabs['up'][2]), b.push_w(tabs['down'][0], ('', '', 'const', ()), tabs['down'][2]),
+            b.push_w(tabs['up'][1], ('', '', 'const', ()), tabs['up'][3]), b.push_w(tabs['down'][1], ('', '', 'const', ()), tabs['down'][3])]
     orb = b.buf('orbitals', K, N * N)
     b.ops.append(Op(OP_ORBITALS, [bf, orb] + offs + [n_env], note='block-diagonal Slater matrices = envelope * backflow'))
     b.ops.append(Op(OP_SLOGDET, [orb], note='slogdet + derivative traces'))
     cc_off = b.push_w(P[f'{WF}/~/conf_coeff']['w'], (f'{WF}/~/conf_coeff', 'w', 'raw', ()))
     al_off = b.push_w(np.array([fs.cusp_alpha, fs.cusp_alpha]), ('', '', 'const', ()))
     b.ops.append(Op(OP_FINAL, [jas, cc_off, 1, al_off], [fs.cusp_same_scale, fs.cusp_anti_scale, 0, 0], note='CI sum + cusp + Jastrow'))
-    return Program(fs.as_ansatz_spec(), n_up, n_down, n_nuc, b.bufs, b.ops, np.concatenate(b.w), np.asarray(b.it, np.int32),
-                   b.names, b.slots, b.flops)
+    return b.finish(Program(fs.as_ansatz_spec(), n_up, n_down, n_nuc, b.bufs, b.ops, np.concatenate(b.w),
+                            np.asarray(b.it, np.int32), b.names, b.slots, b.flops))

@@ -126,3 +126,15 @@ class NeuralNetworkWaveFunction:
         return Psi(sign, log)
 
     __call__ = apply
+
+    def log_psi_vjp(self, params, phys_conf, cotangent=None):
+        """jax.vjp of vmap(ansatz.apply)(params, r).log (loss/loss_function.py:59-75) with one cotangent per walker:
+        returns (Psi(sign, log), grad tree {module: {leaf: ndarray}}) with grad = sum_b cotangent[b] d log|psi(r_b)| / d params.
+        cotangent None = all ones.  Programs whose packing is not a copy of the parameters (nuclear tokens) and programs
+        with attention ops are not supported."""
+        r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
+        R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
+        eng = self.engine(params, R)
+        sign, log, g = eng.log_psi_vjp(r, cotangent, R)
+        return Psi(sign, log), eng.program.unflatten_grad(g)
+

@@ -18,6 +18,8 @@
  *   dqmc_energy_stats   <- EnergyMonitor's mean/std/min/max, observable.py:474-479
  *                          (per-rank partial record; ranks merge them after one all-gather)
  *   dqmc_set_weights    <- a new `params` tree after an optimiser step
+ *   dqmc_log_psi_vjp    <- jax.vjp of vmap(ansatz.apply)(., r).log with a cotangent per walker
+ *                          (loss/loss_function.py:59-75): the parameter gradient of the energy loss
  *
  * Conventions: plain pointers and sizes only.  Unless marked "host", every pointer is a
  * DEVICE pointer.  Walker-major contiguous layouts: r[B][N][3], R[n_nuc][3].  `real` is
@@ -161,6 +163,17 @@ int dqmc_local_energy(dqmc_ctx* ctx, const void* r, const void* R, int B, void* 
  * non-local ECP quadrature: what jax.value_and_grad(psi) hands the reference's LangevinSampler
  * (sampling/electron_samplers.py:193-201).  logpsi / sign may be NULL. */
 int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logpsi, int32_t* sign, void* grad);
+
+/* Sum over walkers of cot[b] * d log|psi(r_b)| / d w, for every entry w of the flat weight buffer (same layout and
+ * length as dqmc_set_weights).  cot: real[B] device, NULL = all ones.  grad: device double[n_weights], overwritten.
+ * logpsi / sign: optional, as dqmc_wf_eval.  Walkers with sign 0 or a non-finite log|psi| contribute nothing.
+ * Entries that are constants or padding receive whatever their position accumulates (padding rows / columns of the
+ * linear layers: exact zeros); mapping the flat gradient back onto the parameters is the caller's (Program.unflatten_grad).
+ * Per walker chunk ("ws_budget_mb", adjoint buffers included) a value pass op by op, then the ops in reverse; the
+ * walker sums run in a fixed order, so two identical calls give bit-identical results.
+ * DQMC_E_UNSUPPORTED for programs with ATTENTION ops (Psiformer, TransPsiformer). */
+int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot,
+                     double* grad, void* logpsi, int32_t* sign);
 
 /* Gaussian-type effective core potential (reference ecp/gaussian_type_ecp.py:32-93 table layout,
  * :127-159 local part, :161-255 non-local part; replaces GaussianTypeECP.__init__'s pyscf lookup by
