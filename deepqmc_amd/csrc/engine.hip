@@ -60,6 +60,7 @@ struct dqmc_ctx {
                            int32_t* sign) = 0;
   virtual int psi_grad(const void* r, const void* R, int B, void* logpsi, int32_t* sign, void* grad) = 0;
   virtual int log_psi_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* logpsi, int32_t* sign) = 0;
+  virtual int log_psi_jacobian(const void* r, const void* R, int B, void* jac, size_t ld_jac, void* logpsi, int32_t* sign) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -477,6 +478,7 @@ struct Engine : dqmc_ctx {
 #include "engine_ecp.inl"
 #include "engine_mcmc.inl"
 #include "engine_grad.inl"
+#include "engine_jac.inl"
 };
 
 }  // namespace
@@ -544,6 +546,12 @@ int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const v
   if (!ctx || !r || !R || !grad) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->log_psi_vjp(r, R, B, cot, grad, logpsi, sign);
+}
+int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, void* jac, size_t ld_jac, void* logpsi,
+                          int32_t* sign) {
+  if (!ctx || !r || !R || !jac) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->log_psi_jacobian(r, R, B, jac, ld_jac, logpsi, sign);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

@@ -119,7 +119,7 @@
     for (int b0 = 0; b0 < B && !rc; b0 += (int)chunk) {
       const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
       rc = grad_chunk(r + (size_t)b0 * N * 3, R, nb, cot ? cot + b0 : nullptr, grad, logpsi ? logpsi + b0 : nullptr,
-                      sign ? sign + b0 : nullptr);
+                      sign ? sign + b0 : nullptr, nullptr, 0);
     }
     fused_enabled = fused_saved;
     mlp_child.swap(child_saved);
@@ -128,7 +128,10 @@
     return DQMC_OK;
   }
 
-  int grad_chunk(const real* r, const real* R, int B, const real* cot, double* grad, real* logpsi, int32_t* sign) {
+  // jac == nullptr: accumulate sum_b cot[b] (...) into grad (dqmc_log_psi_vjp).  Otherwise (dqmc_log_psi_jacobian, cot == nullptr,
+  // grad unused) row b of jac[B][ld_jac] receives walker b's parameter partials (engine_jac.inl).
+  int grad_chunk(const real* r, const real* R, int B, const real* cot, double* grad, real* logpsi, int32_t* sign, real* jac,
+                 size_t ld_jac) {
     // adjoint workspace of this chunk
     std::vector<size_t> adj(bufs.size());
     size_t off = 0;
@@ -153,6 +156,9 @@
     int32_t* sg = sign ? sign : reinterpret_cast<int32_t*>(gw + o_sg);
     { const int rc = run_chunk(r, R, B, false, lp, sg, nullptr, nullptr, B, nullptr, 0); if (rc) return rc; }
     HIP_TRY(hipMemsetAsync(gw, 0, adj_end, st));
+    const dqmc::JacOut<real> jo{jac, (long)ld_jac, lp, sg, jac_accum ? 1 : 0,
+                                (ld_jac % 4 == 0 && (reinterpret_cast<uintptr_t>(jac) & 15) == 0) ? 1 : 0};
+    if (jac) jac_zero_rows(jac, ld_jac, B);
     const int32_t* gt = (const int32_t*)g_tab.p;
     double* dL = reinterpret_cast<double*>(gw + o_dl);
     for (size_t opi = ops.size(); opi-- > 0;) {
@@ -184,7 +190,7 @@
           f.W = d_w + i[22]; f.ldw = pad4(i[21]); f.bias = i[23] >= 0 ? d_w + i[23] : nullptr;
           f.dst = Z; f.ld_dst = f.ldw; f.rpw_dst = i[20]; f.r0_dst = 0; f.col0_dst = 0;
           f.act = 0; f.nrows = i[20]; f.B = B; f.T = 1; f.TP = 1;
-          t_begin("linear_bwd", 6.0 * B * i[20] * (double)w_row * f.ldw);     // Z recompute, dX, dW
+          t_begin(jac ? "linear_jac" : "linear_bwd", 6.0 * B * i[20] * (double)w_row * f.ldw);     // Z recompute, dX, dW
           dqmc::launch_linear<real>(st, f);
           a.W = f.W; a.ldw = f.ldw; a.nout = i[21]; a.nrows = i[20]; a.B = B; a.act = i[24];
           a.Z = Z; a.dZ = reinterpret_cast<real*>(gw + o_dz); a.dZs = reinterpret_cast<real*>(gw + o_dzs);
@@ -193,7 +199,8 @@
           a.res_scale = i[27] ? (real)0.70710678118654752440 : (real)1;
           a.dW = grad + i[22]; a.dbias = i[23] >= 0 ? grad + i[23] : nullptr;
           a.part = reinterpret_cast<double*>(gw + o_part);
-          dqmc::launch_linear_bwd<real>(st, a);
+          if (jac) dqmc::launch_linear_jac<real>(st, a, jo, i[22], i[23]);
+          else dqmc::launch_linear_bwd<real>(st, a);
           t_end();
           break;
         }
@@ -218,6 +225,11 @@
           break;
         }
         case DQMC_OP_CONST:
+          if (jac) {
+            dqmc::launch_jac_scatter<real, real>(st, A(i[0]), (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width,
+                                                 B, jo, i[1]);
+            break;
+          }
           dqmc::launch_colsum<real>(st, A(i[0]), B, (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width, grad + i[1]);
           break;
         case DQMC_OP_ORBITALS: {
@@ -226,7 +238,9 @@
           t_begin("orbitals_bwd", 0);
           dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[0]), A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
                                           d_w + i[4], d_w + i[5], pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps);
-          for (int q = 0; q < 4; ++q) dqmc::launch_colsum_f64(st, pw + (size_t)q * KN * L, B, 4L * KN * L, KN * L, grad + i[2 + q]);
+          for (int q = 0; q < 4; ++q)
+            if (jac) dqmc::launch_jac_scatter<double, real>(st, pw + (size_t)q * KN * L, 4L * KN * L, KN * L, B, jo, i[2 + q]);
+            else dqmc::launch_colsum_f64(st, pw + (size_t)q * KN * L, B, 4L * KN * L, KN * L, grad + i[2 + q]);
           t_end();
           break;
         }
@@ -250,6 +264,11 @@
           a.pw = reinterpret_cast<double*>(gw + o_pw);
           a.B = B; a.N = N; a.n_up = sys.n_up; a.K = sys.n_det;
           dqmc::launch_final_bwd<real>(st, a);
+          if (jac) {
+            if (i[1] >= 0) dqmc::launch_jac_scatter<double, real>(st, a.pw, sys.n_det + 2, sys.n_det, B, jo, i[1]);
+            dqmc::launch_jac_scatter<double, real>(st, a.pw + sys.n_det, sys.n_det + 2, 2, B, jo, i[3]);
+            break;
+          }
           if (i[1] >= 0) dqmc::launch_colsum_f64(st, a.pw, B, sys.n_det + 2, sys.n_det, grad + i[1]);
           dqmc::launch_colsum_f64(st, a.pw + sys.n_det, B, sys.n_det + 2, 2, grad + i[3]);
           break;

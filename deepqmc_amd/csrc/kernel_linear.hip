@@ -1236,3 +1236,4 @@ template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 }  // namespace dqmc
 
 #include "kernels_grad.inl"
+#include "kernels_jac.inl"

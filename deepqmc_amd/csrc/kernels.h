@@ -423,4 +423,23 @@ void launch_orbitals_bwd(hipStream_t st, const real* r, const real* R, const rea
                          const real* pi_up, const real* pi_dn, const real* ze_up, const real* ze_dn, double* pw, int B, int N, int n_up,
                          int n_env, int n_nuc, int K, double eps);
 
+// ---- kernels_jac.inl (included by kernel_linear.hip): per-walker parameter Jacobian (dqmc_log_psi_jacobian) ----
+// LINEAR weight blocks are formed per walker in tiles of at most JAC_TILE entries (LDS staged), JAC_MAX_COLS columns wide
+constexpr int JAC_TILE = 4096, JAC_MAX_COLS = 1024;
+template <typename real> struct JacOut {
+  real* J;              // row b of walker b of the chunk, ld entries apart
+  long ld;
+  const real* lp;       // log|psi| and sign of the chunk's walkers: sign 0 or a non-finite log|psi| gives zeros
+  const int32_t* sg;
+  int accum;            // 1: add into J (rows zeroed first), 0: plain stores (no weight block is shared between ops)
+  int vec;              // 1: J and ld allow 16-byte stores
+};
+// the LINEAR reverse pass with the weight gradient per walker: k_lin_dz and k_lin_dx as launch_linear_bwd, the weight block of
+// every piece at column w_col + w_row * ldw and the bias at bias_col (< 0: none); a.dW, a.dbias and a.part are not used
+template <typename real> void launch_linear_jac(hipStream_t st, const LinBwdArgs<real>& a, const JacOut<real>& o, long w_col, long bias_col);
+// J[b][col + m] = (real) src[b * stride + m], m < n (added with o.accum)
+template <typename T, typename real> void launch_jac_scatter(hipStream_t st, const T* src, long stride, int n, int B, const JacOut<real>& o, long col);
+// J[b][cols[m]] = 0, m < n (cols == nullptr: columns 0 .. n-1)
+template <typename real> void launch_jac_zero(hipStream_t st, real* J, long ld_jac, const int32_t* cols, int n, int B);
+
 }  // namespace dqmc

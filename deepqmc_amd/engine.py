@@ -161,6 +161,26 @@ class Engine:
                                               logpsi.data_ptr(), sign.data_ptr()))
         return sign, logpsi, grad
 
+    def log_psi_jacobian(self, r, R=None, out=None):
+        """Per-walker rows J[b] = d log|psi(r_b)| / d w over the flat weight buffer (dqmc_log_psi_jacobian): the Jacobian that
+        log_psi_vjp contracts with its cotangent.  Returns (sign, logpsi, J): J is [B, n_weights] on the engine's device, in the
+        engine's dtype; map it onto the parameters with `self.program.unflatten_jacobian`.  `out`: a preallocated [B, ld]
+        tensor (ld >= n_weights, unit column stride) that J is a view of; its columns >= n_weights are not touched."""
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+        nw = self.program.weights.size
+        if out is None:
+            out = torch.empty(B, nw, dtype=self.dtype, device=self.device)
+        elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < nw or out.dtype != self.dtype or out.device.type != self.device.type
+              or out.stride(1) != 1 or out.stride(0) < nw):
+            raise DqmcError(f'out must be a [{B}, >= {nw}] {self.dtype} tensor on {self.device} with unit column stride')
+        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
+        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._check(self.lib.dqmc_log_psi_jacobian(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, out.data_ptr(),
+                                                   out.stride(0), logpsi.data_ptr(), sign.data_ptr()))
+        return sign, logpsi, out[:, :nw]
+
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None):
         """`rng` (an int seed or None) keys the random quadrature rotation of the non-local ECP term

@@ -1,6 +1,7 @@
 """Batch-level callers of the hot path: `compute_local_energy` (reference
 src/deepqmc/loss/energy.py:19-60), `compute_psi_ratio` (loss/overlap.py:19-99) and the training gradient of the
-energy loss `compute_energy_loss_and_grad` (loss/loss_function.py:191-226), with the
+energy loss `compute_energy_loss_and_grad` (loss/loss_function.py:191-226) with its natural-gradient form
+`compute_energy_loss_and_natgrad`, with the
 reference's `[molecule, electronic state, walker]` batch axes.  The molecule and state axes are
 host loops over HIP contexts (one per state's parameter set; the geometry of a molecule is an argument
 of the call); the walker axis is the GPU batch.  `phys_conf` is either the electron tensor r[M,S,B,N,3]
@@ -132,10 +133,21 @@ def compute_energy_loss_and_grad(rng, hamil, ansatz, params: Sequence, phys_conf
     the mask count taken over all states and walkers, as the reference's masked_mean over [M, S, B].
     Returns (loss = mean(E_loc w) over [1, S, B], [grad tree per state], stats: the hamiltonian statistics of
     compute_local_energy and 'E_loc' [1, S, B]).  The overlap and spin penalties are not included."""
-    from .types import PhysicalConfiguration
+    r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_grad', rng, hamil, ansatz, params, phys_conf,
+                                                             weight, clip_mask_fn)
+    grads = []
+    for s, cot in enumerate(cots):
+        pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
+        _, grad = ansatz.log_psi_vjp(params[s], pc, cot.to(eng.dtype).to(eng.device).contiguous())
+        grads.append(grad)
+    return loss, grads, stats
+
+
+def _energy_loss_cotangents(name, rng, hamil, ansatz, params, phys_conf, weight, clip_mask_fn):
+    """-> (r, Rs, loss, [cotangent c_s [B] per state], [clip mask [B] per state], stats) of the energy loss on a [1, S, B] batch."""
     r, Rs = _unpack(phys_conf)
     if r.shape[0] != 1:
-        raise ValueError('compute_energy_loss_and_grad: one molecule per batch ([1, S, B])')
+        raise ValueError(f'{name}: one molecule per batch ([1, S, B])')
     e_loc, stats = compute_local_energy(rng, hamil, ansatz, params, phys_conf)
     S, B = r.shape[1], r.shape[2]
     e64 = e_loc.double()
@@ -144,16 +156,66 @@ def compute_energy_loss_and_grad(rng, hamil, ansatz, params: Sequence, phys_conf
     # masked_mean over the whole [1, S, B] batch (loss/energy.py:101, utils.py:51-54): ONE mask count for all states
     clipped = [clip_mask_fn(e64[0, s]) for s in range(S)]
     n_mask = sum(mask.to(torch.float64).sum() for _, mask in clipped)
-    grads = []
+    cots = []
     for s, (e_clip, mask) in enumerate(clipped):
         mean_e = (e_clip * w[0, s]).mean()
-        cot = mask.to(torch.float64) * w[0, s] * (e_clip - mean_e) / n_mask
-        rr = r[0, s].contiguous()
-        pc = rr if Rs[0] is None else PhysicalConfiguration(Rs[0], rr, None)
-        eng = ansatz.engine(params[s], Rs[0])
-        _, grad = ansatz.log_psi_vjp(params[s], pc, cot.to(eng.dtype).to(eng.device).contiguous())
-        grads.append(grad)
+        cots.append(mask.to(torch.float64) * w[0, s] * (e_clip - mean_e) / n_mask)
     stats = dict(stats)
     stats['E_loc'] = e_loc
-    return loss, grads, stats
+    return r, Rs, loss, cots, [mask for _, mask in clipped], stats
+
+
+def _state_conf(ansatz, params_s, r, Rs, s):
+    from .types import PhysicalConfiguration
+    rr = r[0, s].contiguous()
+    pc = rr if Rs[0] is None else PhysicalConfiguration(Rs[0], rr, None)
+    return pc, ansatz.engine(params_s, Rs[0])
+
+
+def compute_energy_loss_and_natgrad(rng, hamil, ansatz, params: Sequence, phys_conf, damping=1e-3, weight=None,
+                                    clip_mask_fn=median_clip_and_mask):
+    """compute_energy_loss_and_grad preconditioned by the damped Fisher matrix of the per-walker log|psi| gradients (natural
+    gradient / stochastic reconfiguration), in the MinSR form that needs only a B x B solve.  Per state s, with the per-walker
+    rows O_b = d log|psi_s(r_sb)| / d theta_s (NeuralNetworkWaveFunction.log_psi_jacobian), the clip mask m_b, its count n_s over
+    the state's walkers and the masked mean Obar_s = sum_b m_b O_b / n_s:
+        g_s     = sum_b c_sb O_b                                 (the gradient of compute_energy_loss_and_grad, same c_sb)
+        A_s     = rows sqrt(m_b / n_s) (O_b - Obar_s)
+        delta_s = (A_s^T A_s + damping I)^-1 g_s = (g_s - A_s^T (A_s A_s^T + damping I)^-1 A_s g_s) / damping.
+    The Gram matrix A_s A_s^T is formed with torch.matmul in the Jacobian's dtype, its Cholesky solve runs in float64, and one
+    step of iterative refinement removes the cancellation of the Woodbury form at small damping.
+    Returns (loss, [delta_s tree per state], stats): stats as compute_energy_loss_and_grad's, plus 'grad' = [g_s tree per state].
+    Single process only: the Jacobians of other ranks are not gathered."""
+    if not damping > 0:
+        raise ValueError('damping must be positive')
+    r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_natgrad', rng, hamil, ansatz, params, phys_conf,
+                                                             weight, clip_mask_fn)
+    deltas, gs = [], []
+    for s, cot in enumerate(cots):
+        pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
+        _, Jp = ansatz.log_psi_jacobian(params[s], pc)
+        dt, dev = Jp.dtype, Jp.device
+        c = cot.to(dt).to(dev)                                  # the cotangent log_psi_vjp receives
+        g = torch.matmul(c, Jp).double()
+        m = masks[s].to(torch.float64).to(dev)
+        n_s = m.sum()
+        obar = torch.matmul((m / n_s).to(dt), Jp)
+        A = Jp.sub_(obar).mul_(torch.sqrt(m / n_s).to(dt)[:, None])          # in place: Jp is this call's own tensor
+        gram = torch.matmul(A, A.transpose(0, 1)).double()
+        gram.diagonal().add_(damping)
+        chol = torch.linalg.cholesky(gram)
+        Av = lambda v: torch.matmul(A, v.to(dt)).double()
+        AtV = lambda v: torch.matmul(v.to(dt), A).double()
+
+        def solve(v):                     # (A^T A + damping I)^-1 v, Woodbury
+            z = torch.cholesky_solve(Av(v)[:, None], chol)[:, 0]
+            return (v - AtV(z)) / damping
+
+        delta = solve(g)
+        delta = delta + solve(g - AtV(Av(delta)) - damping * delta)      # one step of iterative refinement
+        prog = eng.program
+        deltas.append(prog.unflatten_params(delta))
+        gs.append(prog.unflatten_params(g))
+        del A, Jp
+    stats['grad'] = gs
+    return loss, deltas, stats
 

@@ -123,6 +123,67 @@ class Program:
             tree.setdefault(mod, {})[leaf] = flat[base:base + int(np.prod(shape))].reshape(shape)
         return tree
 
+    def leaf_slices(self):
+        """Columns of unflatten_jacobian per parameter leaf: {(module, leaf): (slice, shape)}, in grad_leaves order."""
+        return {key: (slice(base, base + int(np.prod(shape))), tuple(shape)) for key, (base, shape) in self.grad_leaves.items()}
+
+    def n_params(self):
+        return sum(int(np.prod(sh)) for _, sh in self.grad_leaves.values())
+
+    def unflatten_params(self, v):
+        """A [n_params] vector (one row of unflatten_jacobian, or anything in its column order) -> haiku tree
+        {module: {leaf: ndarray}}."""
+        if hasattr(v, 'detach'):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v).reshape(-1)
+        if v.size != self.n_params():
+            raise ValueError(f'vector of {v.size} entries for {self.n_params()} parameters')
+        tree: Dict[str, Dict[str, np.ndarray]] = {}
+        for (mod, leaf), (sl, shape) in self.leaf_slices().items():
+            tree.setdefault(mod, {})[leaf] = v[sl].reshape(shape)
+        return tree
+
+    def _jacobian_gather(self):
+        """Per source multiplicity m, the flat weight entries that hold the m-th copy of each parameter element (ascending
+        entry order, as np.add.at in unflatten_grad sums them) and the mask of elements that have one."""
+        if getattr(self, '_jac_gather', None) is None:
+            n_el = self.n_params()
+            j = np.nonzero(self.grad_src >= 0)[0]           # ascending
+            e = self.grad_src[j]
+            order = np.argsort(e, kind='stable')            # by element, ascending entry within an element
+            j, e = j[order], e[order]
+            first = np.searchsorted(e, np.arange(n_el))
+            rank = np.arange(e.size) - first[e]
+            tabs = []
+            for m in range(int(rank.max()) + 1 if rank.size else 0):
+                sel = rank == m
+                idx = np.zeros(n_el, np.int64)
+                has = np.zeros(n_el, bool)
+                idx[e[sel]] = j[sel]
+                has[e[sel]] = True
+                tabs.append((idx, has))
+            self._jac_gather = tabs
+        return self._jac_gather
+
+    def unflatten_jacobian(self, J):
+        """Per-walker Jacobian over the weight buffer (Engine.log_psi_jacobian, [B, n_weights]) -> [B, n_params] on J's device
+        and in J's dtype: row b is unflatten_grad(J[b]) flattened in grad_leaves order (see leaf_slices / unflatten_params).
+        A gather per source multiplicity summed in a fixed order, so the result is deterministic on the GPU."""
+        if self.grad_unsupported:
+            raise NotImplementedError(f'unflatten_jacobian: unsupported for this program ({self.grad_unsupported})')
+        import torch
+        if J.dim() != 2 or J.shape[1] != self.grad_src.size:
+            raise ValueError(f'Jacobian of shape {tuple(J.shape)} for a weight buffer of {self.grad_src.size}')
+        out = None
+        for idx, has in self._jacobian_gather():
+            col = J.index_select(1, torch.as_tensor(idx, device=J.device))
+            if not has.all():
+                col = torch.where(torch.as_tensor(has, device=J.device)[None], col, torch.zeros((), dtype=J.dtype, device=J.device))
+            out = col if out is None else out.add_(col)
+        if out is None:
+            out = torch.zeros(J.shape[0], self.n_params(), dtype=J.dtype, device=J.device)
+        return out
+
     def c_bufs(self):
         arr = (DqmcBuf * len(self.bufs))()
         for k, (r, w) in enumerate(self.bufs):

@@ -138,3 +138,18 @@ class NeuralNetworkWaveFunction:
         sign, log, g = eng.log_psi_vjp(r, cotangent, R)
         return Psi(sign, log), eng.program.unflatten_grad(g)
 
+    def log_psi_jacobian(self, params, phys_conf):
+        """The per-walker rows of the Jacobian that log_psi_vjp contracts: returns (Psi(sign, log), Jp) with
+        Jp[b] = d log|psi(r_b)| / d params as a [B, n_params] tensor on the device, in the wave function's dtype, columns in
+        the program's grad_leaves order (eng.program.leaf_slices / unflatten_params map them back onto the tree).  The same
+        programs as log_psi_vjp are supported."""
+        r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
+        R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
+        eng = self.engine(params, R)
+        if eng.program.grad_unsupported:          # before the B x n_weights allocation
+            raise NotImplementedError(f'log_psi_jacobian: unsupported for this program ({eng.program.grad_unsupported})')
+        sign, log, J = eng.log_psi_jacobian(r, R)
+        Jp = eng.program.unflatten_jacobian(J)
+        del J
+        return Psi(sign, log), Jp
+

@@ -20,6 +20,7 @@
  *   dqmc_set_weights    <- a new `params` tree after an optimiser step
  *   dqmc_log_psi_vjp    <- jax.vjp of vmap(ansatz.apply)(., r).log with a cotangent per walker
  *                          (loss/loss_function.py:59-75): the parameter gradient of the energy loss
+ *   dqmc_log_psi_jacobian <- the per-walker rows of that Jacobian (natural-gradient / KFAC preconditioners)
  *
  * Conventions: plain pointers and sizes only.  Unless marked "host", every pointer is a
  * DEVICE pointer.  Walker-major contiguous layouts: r[B][N][3], R[n_nuc][3].  `real` is
@@ -174,6 +175,17 @@ int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logp
  * DQMC_E_UNSUPPORTED for programs with ATTENTION ops (Psiformer, TransPsiformer). */
 int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot,
                      double* grad, void* logpsi, int32_t* sign);
+
+/* Per-walker parameter Jacobian of log|psi|: row b = d log|psi(r_b)| / d w for every entry w of the flat weight buffer
+ * (the layout of dqmc_set_weights), B rows -- the per-walker rows O_b of natural-gradient / stochastic-reconfiguration and
+ * KFAC preconditioners.
+ *   jac: real[B][ld_jac], ld_jac >= n_weights; columns >= n_weights are not touched.  logpsi / sign: optional outputs.
+ * Same conventions as dqmc_log_psi_vjp: walkers with sign 0 or a non-finite log|psi| get an all-zero row; constant and
+ * padding entries get what their position accumulates (padding of linear layers: exact zeros); walker chunks per
+ * "ws_budget_mb" (dqmc_last_chunks); no atomics, so identical calls are bit-identical, and a chunked call equals an
+ * unchunked one bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
+int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, void* jac, size_t ld_jac,
+                          void* logpsi, int32_t* sign);
 
 /* Gaussian-type effective core potential (reference ecp/gaussian_type_ecp.py:32-93 table layout,
  * :127-159 local part, :161-255 non-local part; replaces GaussianTypeECP.__init__'s pyscf lookup by
