@@ -233,7 +233,7 @@ def test_near_node_walker_and_no_twin_fallback():
     c = lone.ecp_counts() if lone.refine_info()['mode'] == 1 else None
     assert torch.isfinite(e_a[1:]).all() and lone.last_refined() == 0 and lone.refine_info()['mode'] == 0      # refinement switched itself off
     plain = NeuralNetworkWaveFunction(h, small, dtype=torch.float32, device='cpu', lib=emu_lib(), norm_eps=geom.F32_EPS).engine(params)
-    plain.set_option('refine', 0); plain.set_option('tail_f64', 0)
+    plain.set_option('refine', 0)
     e_p, st_p = plain.local_energy(torch.as_tensor(r), ecp_phi=torch.as_tensor(phi))
     np.testing.assert_allclose(st_a['hamil/V_nl'].numpy()[1:], st_p['hamil/V_nl'].numpy()[1:], rtol=1e-5, atol=1e-6)   # float32 ratios, only the negligible pairs dropped
     np.testing.assert_array_equal(e_b.numpy()[1:], e_p.numpy()[1:])         # later calls: the plain float32 path (refine 0)
