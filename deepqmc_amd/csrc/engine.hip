@@ -61,6 +61,9 @@ struct dqmc_ctx {
   virtual int psi_grad(const void* r, const void* R, int B, void* logpsi, int32_t* sign, void* grad) = 0;
   virtual int log_psi_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* logpsi, int32_t* sign) = 0;
   virtual int log_psi_jacobian(const void* r, const void* R, int B, void* jac, size_t ld_jac, void* logpsi, int32_t* sign) = 0;
+  virtual int kfac_layout(int* n_linear, size_t* n_factor_doubles, size_t* n_rest) = 0;
+  virtual int log_psi_kfac(const void* r, const void* R, int B, const void* cot, double* grad, double* factors, void* rest,
+                           void* logpsi, int32_t* sign) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -446,6 +449,7 @@ struct Engine : dqmc_ctx {
 #include "engine_mcmc.inl"
 #include "engine_grad.inl"
 #include "engine_jac.inl"
+#include "engine_kfac.inl"
 };
 
 }  // namespace
@@ -519,6 +523,17 @@ int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, vo
   if (!ctx || !r || !R || !jac) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->log_psi_jacobian(r, R, B, jac, ld_jac, logpsi, sign);
+}
+int dqmc_kfac_layout(dqmc_ctx* ctx, int* n_linear, size_t* n_factor_doubles, size_t* n_rest) {
+  if (!ctx) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->kfac_layout(n_linear, n_factor_doubles, n_rest);
+}
+int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, double* factors, void* rest,
+                      void* logpsi, int32_t* sign) {
+  if (!ctx || !r || !R || !grad || !factors) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->log_psi_kfac(r, R, B, cot, grad, factors, rest, logpsi, sign);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

@@ -11,6 +11,12 @@
     void* p = nullptr;
     ~GradDev() { if (p) (void)hipFree(p); }
   };
+  // dqmc_log_psi_kfac's additions to one chunk of the reverse pass (engine_kfac.inl)
+  struct KfacChunk {
+    const real* cot;             // the chunk's cotangents, or nullptr (ones)
+    double* factors;             // A_l, G_l of every LINEAR op, accumulated
+    real* rest;                  // [B][n_rest] partials of the entries no LINEAR op owns, or nullptr
+  };
   GradDev g_ws, g_tab;
   size_t g_ws_bytes = 0;
   std::vector<int> g_tab_of;     // per op: {rows table offset, Sr, senders table offset, Ss} into g_tab (CONV, EDGE_SUM)
@@ -130,8 +136,10 @@
 
   // jac == nullptr: accumulate sum_b cot[b] (...) into grad (dqmc_log_psi_vjp).  Otherwise (dqmc_log_psi_jacobian, cot == nullptr,
   // grad unused) row b of jac[B][ld_jac] receives walker b's parameter partials (engine_jac.inl).
+  // kf != nullptr (dqmc_log_psi_kfac, cot == nullptr, jac == nullptr): the adjoints are those of a unit cotangent; kf->cot
+  // weights the walker sums of grad, and the KFAC factors and rest partials are formed on the way (engine_kfac.inl).
   int grad_chunk(const real* r, const real* R, int B, const real* cot, double* grad, real* logpsi, int32_t* sign, real* jac,
-                 size_t ld_jac) {
+                 size_t ld_jac, const KfacChunk* kf = nullptr) {
     // adjoint workspace of this chunk
     std::vector<size_t> adj(bufs.size());
     size_t off = 0;
@@ -144,6 +152,7 @@
     const size_t o_dl = bump(sizeof(double) * (size_t)B * sys.n_det), o_pw = bump(sizeof(double) * (size_t)B * (sys.n_det + 2));
     const size_t o_lp = bump(sizeof(real) * (size_t)B), o_sg = bump(sizeof(int32_t) * (size_t)B);
     const size_t o_part = bump(grad_part_bytes());
+    const size_t o_kw = bump(kf ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = bump(kf ? kfac_part_bytes() : 0);
     if (off > g_ws_bytes) {
       if (g_ws.p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(g_ws.p)); g_ws.p = nullptr; g_ws_bytes = 0; }
       const hipError_t e = hipMalloc(&g_ws.p, off);
@@ -159,6 +168,13 @@
     const dqmc::JacOut<real> jo{jac, (long)ld_jac, lp, sg, jac_accum ? 1 : 0,
                                 (ld_jac % 4 == 0 && (reinterpret_cast<uintptr_t>(jac) & 15) == 0) ? 1 : 0};
     if (jac) jac_zero_rows(jac, ld_jac, B);
+    // kfac: per-walker weights of the walker sums (cot, 0 for invalid walkers) and validity flags of the factors
+    double* kw = kf ? reinterpret_cast<double*>(gw + o_kw) : nullptr;
+    const dqmc::JacOut<real> ko{kf ? kf->rest : nullptr, (long)k_n_rest, lp, sg, jac_accum ? 1 : 0, 0};
+    if (kf) {
+      dqmc::launch_kfac_weights<real>(st, lp, sg, kf->cot, kw, B);
+      if (kf->rest) kfac_zero_rest(kf->rest, B);
+    }
     const int32_t* gt = (const int32_t*)g_tab.p;
     double* dL = reinterpret_cast<double*>(gw + o_dl);
     for (size_t opi = ops.size(); opi-- > 0;) {
@@ -199,8 +215,14 @@
           a.res_scale = i[27] ? (real)0.70710678118654752440 : (real)1;
           a.dW = grad + i[22]; a.dbias = i[23] >= 0 ? grad + i[23] : nullptr;
           a.part = reinterpret_cast<double*>(gw + o_part);
+          a.wt = kw;
           if (jac) dqmc::launch_linear_jac<real>(st, a, jo, i[22], i[23]);
           else dqmc::launch_linear_bwd<real>(st, a);
+          if (kf) {
+            double* fA = kf->factors + k_fac_off[opi];
+            dqmc::launch_kfac_factors<real>(st, a, i[23] >= 0, kw + B, fA, fA + kfac_dim_a(op) * kfac_dim_a(op),
+                                            reinterpret_cast<double*>(gw + o_kpart));
+          }
           t_end();
           break;
         }
@@ -230,7 +252,11 @@
                                                  B, jo, i[1]);
             break;
           }
-          dqmc::launch_colsum<real>(st, A(i[0]), B, (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width, grad + i[1]);
+          if (kf && kf->rest)
+            dqmc::launch_jac_scatter<real, real>(st, A(i[0]), (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width,
+                                                 B, ko, k_rest_pos[i[1]]);
+          dqmc::launch_colsum<real>(st, A(i[0]), B, (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width, grad + i[1],
+                                    kw);
           break;
         case DQMC_OP_ORBITALS: {
           const int n_env = i[6] > 0 ? i[6] : 1, KN = sys.n_det * N, L = sys.n_nuc * n_env;
@@ -238,9 +264,11 @@
           t_begin("orbitals_bwd", 0);
           dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[0]), A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
                                           d_w + i[4], d_w + i[5], pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps);
-          for (int q = 0; q < 4; ++q)
-            if (jac) dqmc::launch_jac_scatter<double, real>(st, pw + (size_t)q * KN * L, 4L * KN * L, KN * L, B, jo, i[2 + q]);
-            else dqmc::launch_colsum_f64(st, pw + (size_t)q * KN * L, B, 4L * KN * L, KN * L, grad + i[2 + q]);
+          for (int q = 0; q < 4; ++q) {
+            if (jac) { dqmc::launch_jac_scatter<double, real>(st, pw + (size_t)q * KN * L, 4L * KN * L, KN * L, B, jo, i[2 + q]); continue; }
+            if (kf && kf->rest) dqmc::launch_jac_scatter<double, real>(st, pw + (size_t)q * KN * L, 4L * KN * L, KN * L, B, ko, k_rest_pos[i[2 + q]]);
+            dqmc::launch_colsum_f64(st, pw + (size_t)q * KN * L, B, 4L * KN * L, KN * L, grad + i[2 + q], kw);
+          }
           t_end();
           break;
         }
@@ -269,8 +297,12 @@
             dqmc::launch_jac_scatter<double, real>(st, a.pw + sys.n_det, sys.n_det + 2, 2, B, jo, i[3]);
             break;
           }
-          if (i[1] >= 0) dqmc::launch_colsum_f64(st, a.pw, B, sys.n_det + 2, sys.n_det, grad + i[1]);
-          dqmc::launch_colsum_f64(st, a.pw + sys.n_det, B, sys.n_det + 2, 2, grad + i[3]);
+          if (kf && kf->rest) {
+            if (i[1] >= 0) dqmc::launch_jac_scatter<double, real>(st, a.pw, sys.n_det + 2, sys.n_det, B, ko, k_rest_pos[i[1]]);
+            dqmc::launch_jac_scatter<double, real>(st, a.pw + sys.n_det, sys.n_det + 2, 2, B, ko, k_rest_pos[i[3]]);
+          }
+          if (i[1] >= 0) dqmc::launch_colsum_f64(st, a.pw, B, sys.n_det + 2, sys.n_det, grad + i[1], kw);
+          dqmc::launch_colsum_f64(st, a.pw + sys.n_det, B, sys.n_det + 2, 2, grad + i[3], kw);
           break;
         }
         default:

@@ -357,6 +357,7 @@ template <typename real> struct LinBwdArgs {
   double* dW;         // gradient of W (double, flat weight layout), accumulated
   double* dbias;      // gradient of the bias, or nullptr
   double* part;       // split-K scratch: grad_dw_part_doubles of the largest block
+  const double* wt;   // per-walker weights of the weight-gradient sums (dqmc_log_psi_kfac), or nullptr: unweighted
 };
 // Split-K of the weight-gradient GEMMs: about GRAD_DW_WAVES waves (16 x 16 tiles x splits) per launch, at most GRAD_DW_MAX_SPLIT
 // splits (the fixed-order second pass reads every split of an entry serially) and at least 64 rows per split
@@ -377,9 +378,11 @@ inline size_t grad_dw_part_doubles(int kt, int nt) {
   return (size_t)s * tiles * 256;
 }
 template <typename real> void launch_linear_bwd(hipStream_t st, const LinBwdArgs<real>& a);
-// out[m] += sum_c in[c * stride + m] (c < count, m < n_out), fixed summation order
-template <typename real> void launch_colsum(hipStream_t st, const real* in, long count, long stride, int n_out, double* out);
-void launch_colsum_f64(hipStream_t st, const double* in, long count, long stride, int n_out, double* out);
+// out[m] += sum_c in[c * stride + m] (c < count, m < n_out), fixed summation order; with wt, term c is in[..] * wt[c]
+// (exactly 0 where wt[c] == 0)
+template <typename real>
+void launch_colsum(hipStream_t st, const real* in, long count, long stride, int n_out, double* out, const double* wt = nullptr);
+void launch_colsum_f64(hipStream_t st, const double* in, long count, long stride, int n_out, double* out, const double* wt = nullptr);
 template <typename real> void launch_spin_mean_bwd(hipStream_t st, real* dx, const real* dm, int B, int N, int n_up, int width);
 template <typename real> void launch_row_sum_bwd(hipStream_t st, real* dx, const real* ds, int B, int rows, int width);
 // edge-row adjoint of CONV (hx given) / EDGE_SUM (hx == nullptr, factor `scale`) through rtab[row][Sr][2] = (receiver, sender)
@@ -434,5 +437,34 @@ template <typename real> void launch_linear_jac(hipStream_t st, const LinBwdArgs
 template <typename T, typename real> void launch_jac_scatter(hipStream_t st, const T* src, long stride, int n, int B, const JacOut<real>& o, long col);
 // J[b][cols[m]] = 0, m < n (cols == nullptr: columns 0 .. n-1)
 template <typename real> void launch_jac_zero(hipStream_t st, real* J, long ld_jac, const int32_t* cols, int n, int B);
+
+// ---- kernels_kfac.inl (included by kernel_linear.hip): KFAC Kronecker factors (dqmc_log_psi_kfac) ----
+// Gram products: super-tiles of GRAM_TI x GRAM_TJ 16 x 16 tiles (one tile row per wave), LDS row blocks of GRAM_RB_MAX rows
+// (float; half as many for double), about GRAM_WGS workgroups per launch
+constexpr int GRAM_TI = 4, GRAM_TJ = 8, GRAM_RB_MAX = 64;
+constexpr long GRAM_WGS = 512;
+template <typename real> struct GramPiece {
+  const real* X;      // rows X[(b * rpw + r0 + (bcast ? 0 : rr)) * ld + kk], kk < K
+  int ld, rpw, r0, K, Kp, bcast;   // Kp = pad4(K) columns of y, zeros past K
+  int col0;           // first column of y
+};
+template <typename real> struct GramArgs {
+  int n_pieces;
+  GramPiece<real> piece[4];
+  int bias_col;       // column of the constant 1, or -1
+  int D;              // columns of y
+  int nrows;          // rows per walker
+  long M;             // B * nrows
+  const double* ok;   // per walker: 0 = contributes nothing
+};
+struct GramPlan { int nt, T, RB; long groups, S, m_per; };
+GramPlan gram_plan(int D, long M, int real_bytes);
+size_t gram_part_doubles(int D);
+// A += sum over the valid walkers' rows of x~ x~^T (x~: the pieces of a, zero padded to pad4(K), then 1 if has_bias) and
+// G += sum dZ dZ^T over the ldw columns of a.dZ; part: gram_part_doubles of the larger of the two
+template <typename real>
+void launch_kfac_factors(hipStream_t st, const LinBwdArgs<real>& a, int has_bias, const double* ok, double* A, double* G, double* part);
+// w[b] = cot[b] (cot == nullptr: 1) and w[B + b] = 1 for valid walkers, 0 and 0 otherwise
+template <typename real> void launch_kfac_weights(hipStream_t st, const real* lp, const int32_t* sg, const real* cot, double* w, int B);
 
 }  // namespace dqmc

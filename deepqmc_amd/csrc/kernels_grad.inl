@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(256) k_lin_dx(const real* __restrict__ dZ, int
 template <typename real>
 __global__ void __launch_bounds__(64) k_lin_dw(const real* __restrict__ X, int ld, int rpw, int r0, int bcast, int K,
                                                const real* __restrict__ dZ, int ldw, int nrows, long M, long m_per,
-                                               double* __restrict__ part) {
+                                               double* __restrict__ part, const double* __restrict__ wt) {
   typedef typename Mfma<real>::acc_t acc_t;
   const int lane = threadIdx.x & 63;
   const int k0 = blockIdx.x * 16, n0 = blockIdx.y * 16, s = blockIdx.z;
@@ -96,6 +96,7 @@ __global__ void __launch_bounds__(64) k_lin_dw(const real* __restrict__ X, int l
       const int rr = (int)(m - b * nrows);
       if (kk < K) a = X ? X[(b * rpw + r0 + (bcast ? 0 : rr)) * ld + kk] : (real)1;
       if (n < ldw) bv = dZ[m * ldw + n];
+      if (wt) { const double w = wt[b]; bv = w == 0 ? (real)0 : (real)((double)bv * w); }
     }
     acc = Mfma<real>::run(a, bv, acc);
   }
@@ -115,12 +116,18 @@ __global__ void __launch_bounds__(256) k_lin_dw_reduce(const double* __restrict_
 }
 
 // out[m] += sum_c in[c * stride + m], c < count: one workgroup per m, strided partial sums then a fixed tree
+// (wt: term c is in[c * stride + m] * wt[c], exactly 0 where wt[c] == 0)
 template <typename T>
-__global__ void __launch_bounds__(256) k_colsum(const T* __restrict__ in, long count, long stride, double* __restrict__ out) {
+__global__ void __launch_bounds__(256) k_colsum(const T* __restrict__ in, long count, long stride, double* __restrict__ out,
+                                                const double* __restrict__ wt) {
   __shared__ double red[256];
   const int m = blockIdx.x, t = threadIdx.x;
   double s = 0;
-  for (long c = t; c < count; c += 256) s += (double)in[c * stride + m];
+  if (wt) {
+    for (long c = t; c < count; c += 256) s += wt[c] == 0 ? 0.0 : (double)in[c * stride + m] * wt[c];
+  } else {
+    for (long c = t; c < count; c += 256) s += (double)in[c * stride + m];
+  }
   red[t] = s;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -370,7 +377,7 @@ void launch_linear_bwd(hipStream_t st, const LinBwdArgs<real>& a) {
     const long m_per = ((M + S0 - 1) / S0 + 3) / 4 * 4;
     const long S = (M + m_per - 1) / m_per;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lin_dw<real>), dim3((unsigned)kt, (unsigned)Nt, (unsigned)S), dim3(64), 0, st, X, ld, rpw, r0,
-                       bcast, K, (const real*)a.dZ, a.ldw, a.nrows, M, m_per, a.part);
+                       bcast, K, (const real*)a.dZ, a.ldw, a.nrows, M, m_per, a.part, a.wt);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lin_dw_reduce), dim3(grad_grid((long)K * a.nout)), dim3(256), 0, st, (const double*)a.part,
                        (int)S, kt * 16, Nt * 16, K, a.nout, a.ldw, g);
   };
@@ -394,11 +401,11 @@ void launch_linear_bwd(hipStream_t st, const LinBwdArgs<real>& a) {
 }
 
 template <typename real>
-void launch_colsum(hipStream_t st, const real* in, long count, long stride, int m, double* out) {
-  if (m > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colsum<real>), dim3((unsigned)m), dim3(256), 0, st, in, count, stride, out);
+void launch_colsum(hipStream_t st, const real* in, long count, long stride, int m, double* out, const double* wt) {
+  if (m > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colsum<real>), dim3((unsigned)m), dim3(256), 0, st, in, count, stride, out, wt);
 }
-void launch_colsum_f64(hipStream_t st, const double* in, long count, long stride, int m, double* out) {
-  if (m > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colsum<double>), dim3((unsigned)m), dim3(256), 0, st, in, count, stride, out);
+void launch_colsum_f64(hipStream_t st, const double* in, long count, long stride, int m, double* out, const double* wt) {
+  if (m > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colsum<double>), dim3((unsigned)m), dim3(256), 0, st, in, count, stride, out, wt);
 }
 
 template <typename real>
@@ -446,7 +453,7 @@ void launch_orbitals_bwd(hipStream_t st, const real* r, const real* R, const rea
 
 #define DQMC_GRAD_INST(real)                                                                                                        \
   template void launch_linear_bwd<real>(hipStream_t, const LinBwdArgs<real>&);                                                    \
-  template void launch_colsum<real>(hipStream_t, const real*, long, long, int, double*);                                          \
+  template void launch_colsum<real>(hipStream_t, const real*, long, long, int, double*, const double*);                           \
   template void launch_spin_mean_bwd<real>(hipStream_t, real*, const real*, int, int, int, int);                                  \
   template void launch_row_sum_bwd<real>(hipStream_t, real*, const real*, int, int, int);                                         \
   template void launch_edge_rows_bwd<real>(hipStream_t, real*, int, int, const real*, int, int, const real*, int, int,            \

@@ -181,6 +181,43 @@ class Engine:
                                                    out.stride(0), logpsi.data_ptr(), sign.data_ptr()))
         return sign, logpsi, out[:, :nw]
 
+    def kfac_layout(self):
+        """(n_linear, n_factor_doubles, n_rest) as the library computes them (dqmc_kfac_layout); Program.kfac_layout has the same."""
+        n_lin, n_fac, n_rest = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+        self._check(self.lib.dqmc_kfac_layout(self._ctx, ctypes.byref(n_lin), ctypes.byref(n_fac), ctypes.byref(n_rest)))
+        return n_lin.value, n_fac.value, n_rest.value
+
+    def log_psi_kfac(self, r, cot=None, R=None, rest=True, out=None):
+        """The VJP of log_psi_vjp and the KFAC Kronecker factors of every LINEAR op in one reverse pass (dqmc_log_psi_kfac).
+        Returns (sign, logpsi, grad, factors, rest): grad float64 [n_weights] as log_psi_vjp's; factors a list of per-op
+        (A [d_A, d_A], G [ldw, ldw]) float64 tensors on the device, views of one buffer, in program order
+        (Program.kfac_layout); rest [B, n_rest] in the engine's dtype, the per-walker partials of the weight entries no LINEAR
+        op owns (columns Program.kfac_layout()['rest_index']), or None with rest=False.  `out`: optional preallocated
+        (factor buffer, rest) tensors."""
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+        c = None
+        if cot is not None:
+            c = self._t(cot).reshape(-1)
+            self.check_walker_vector('cot', c, B)
+        lay = self.program.kfac_layout()
+        fac = out[0] if out is not None else torch.empty(lay['n_factor_doubles'], dtype=torch.float64, device=self.device)
+        rst = None
+        if rest:
+            rst = out[1] if out is not None and out[1] is not None else torch.empty(B, lay['n_rest'], dtype=self.dtype, device=self.device)
+            assert rst.shape == (B, lay['n_rest']) and rst.dtype == self.dtype and rst.is_contiguous()
+        assert fac.numel() == lay['n_factor_doubles'] and fac.dtype == torch.float64 and fac.is_contiguous()
+        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
+        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+        grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_log_psi_kfac(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, c.data_ptr() if c is not None else None,
+                                               grad.data_ptr(), fac.data_ptr(), rst.data_ptr() if rst is not None else None,
+                                               logpsi.data_ptr(), sign.data_ptr()))
+        factors = [(fac[o['a_off']:o['a_off'] + o['d_a'] ** 2].view(o['d_a'], o['d_a']),
+                    fac[o['g_off']:o['g_off'] + o['d_g'] ** 2].view(o['d_g'], o['d_g'])) for o in lay['ops']]
+        return sign, logpsi, grad, factors, rst
+
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None):
         """`rng` (an int seed or None) keys the random quadrature rotation of the non-local ECP term

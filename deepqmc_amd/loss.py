@@ -1,7 +1,7 @@
 """Batch-level callers of the hot path: `compute_local_energy` (reference
 src/deepqmc/loss/energy.py:19-60), `compute_psi_ratio` (loss/overlap.py:19-99) and the training gradient of the
 energy loss `compute_energy_loss_and_grad` (loss/loss_function.py:191-226) with its natural-gradient form
-`compute_energy_loss_and_natgrad`, with the
+`compute_energy_loss_and_natgrad` and its KFAC form `compute_energy_loss_and_kfac`, with the
 reference's `[molecule, electronic state, walker]` batch axes.  The molecule and state axes are
 host loops over HIP contexts (one per state's parameter set; the geometry of a molecule is an argument
 of the call); the walker axis is the GPU batch.  `phys_conf` is either the electron tensor r[M,S,B,N,3]
@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from typing import Sequence
 
+import numpy as np
 import torch
 
 from .hamil import STAT_KEYS
@@ -219,3 +220,123 @@ def compute_energy_loss_and_natgrad(rng, hamil, ansatz, params: Sequence, phys_c
     stats['grad'] = gs
     return loss, deltas, stats
 
+
+
+def kfac_module_factors(prog, factors, n_valid):
+    """The KFAC-expand factors of every Kronecker module of kfac_blocks in haiku layout (bias as the last row of A):
+    A_hat = sum_l A_l / (n_valid R_mod), G_hat = sum_l G_l / n_valid over the module's ops -> {module: (A_hat, G_hat)}."""
+    blocks, _ = prog.kfac_blocks()
+    out = {}
+    for mod, blk in blocks.items():
+        dev = factors[0][0].device
+        da, dg = blk['n_in'] + int(blk['has_bias']), blk['n_out']
+        A = torch.zeros(da, da, dtype=torch.float64, device=dev)
+        G = torch.zeros(dg, dg, dtype=torch.float64, device=dev)
+        for q, rows, cols in zip(blk['ops'], blk['rows'], blk['cols']):
+            Al, Gl = factors[q]
+            sr, sc = torch.as_tensor(rows >= 0, device=dev), torch.as_tensor(cols >= 0, device=dev)
+            ri, ci = torch.as_tensor(rows[rows >= 0], device=dev), torch.as_tensor(cols[cols >= 0], device=dev)
+            A[ri[:, None], ri[None, :]] += Al[sr][:, sr]
+            G[ci[:, None], ci[None, :]] += Gl[sc][:, sc]
+        out[mod] = (A / (n_valid * blk['R']), G / n_valid)
+    return out
+
+
+def _rest_gather(prog, elems):
+    """Per source multiplicity, the rest columns that hold a copy of each parameter element of `elems` (-1: none)."""
+    lay = prog.kfac_layout()
+    pos = np.full(prog.weights.size, -1, np.int64)
+    pos[lay['rest_index']] = np.arange(lay['n_rest'])
+    tabs = []
+    for idx, has in prog._jacobian_gather():
+        col = np.where(has[elems], pos[idx[elems]], -1)
+        if (has[elems] & (col < 0)).any():
+            raise NotImplementedError('compute_energy_loss_and_kfac: a diagonal parameter is held by a linear layer of a module '
+                                      'that kfac_blocks cannot factor')
+        tabs.append(col)
+    return tabs
+
+
+def compute_energy_loss_and_kfac(rng, hamil, ansatz, params: Sequence, phys_conf, state=None, damping=1e-3, ema=0.95, weight=None,
+                                 clip_mask_fn=median_clip_and_mask):
+    """compute_energy_loss_and_grad preconditioned by KFAC (Kronecker-factored approximate curvature of the Fisher matrix of
+    log|psi|), one dqmc_log_psi_kfac call per state.  With n_v valid walkers (sign != 0, finite log|psi|) and, per module of
+    Program.kfac_blocks, R_mod the rows per walker of its ops:
+        A_hat = sum_l A_l / (n_v R_mod),  G_hat = sum_l G_l / n_v        (KFAC-expand normalisation, bias = last row of A_hat)
+        F <- ema F_old + (1 - ema) F_new  (the first call takes F_new; the factors live in `state`)
+        pi = sqrt((tr A_hat / dim A_hat) / (tr G_hat / dim G_hat))
+        delta [W; b] = (A_hat + pi sqrt(damping) I)^-1 [grad W; grad b] (G_hat + sqrt(damping) / pi I)^-1   (float64, every call)
+    Every other parameter element (envelopes, cusp alphas, conf_coeff, modules kfac_blocks cannot factor) takes a diagonal
+    block: with o_bi = d log|psi_b| / d theta_i (its copies' rest columns summed), F_ii = sum_b o_bi^2 / n_v (same EMA) and
+    delta_i = g_i / (F_ii + damping).  This normalisation is this library's definition; it is not pinned to kfac_jax, which
+    may, for instance, scale G by a constant of its predictive distribution.
+    Returns (loss, [delta tree per state], stats, state): stats as compute_energy_loss_and_grad's plus 'grad' (the gradient
+    trees) and 'precon_grad_dot' = [<delta_s, g_s>] (what the reference's norm constraint needs); state = one dict of factors
+    per electronic state, to pass to the next call.  Single process only: the factors of other ranks are not summed."""
+    if not damping > 0:
+        raise ValueError('damping must be positive')
+    r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_kfac', rng, hamil, ansatz, params, phys_conf,
+                                                             weight, clip_mask_fn)
+    S = len(cots)
+    state = list(state) if state is not None else [None] * S
+    if len(state) != S:
+        raise ValueError('state holds the factors of a different number of states')
+    sq = damping ** 0.5
+    mix = lambda old, new: new if old is None else ema * old + (1 - ema) * new
+    deltas, gs, dots = [], [], []
+    for s, cot in enumerate(cots):
+        pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
+        prog = eng.program
+        rr = pc.r if hasattr(pc, 'r') else pc
+        RR = pc.R if hasattr(pc, 'R') else None
+        sign, logpsi, g, factors, rest = eng.log_psi_kfac(rr, cot.to(eng.dtype).to(eng.device).contiguous(), RR)
+        dev = g.device
+        valid = (sign != 0) & torch.isfinite(logpsi)
+        n_v = max(int(valid.sum()), 1)
+        gtree = prog.unflatten_grad(g)
+        old = state[s] or {}
+        new = {'A': {}, 'G': {}}
+        delta = {m: {k: np.zeros_like(v) for k, v in leaves.items()} for m, leaves in gtree.items()}
+        for mod, (A, G) in kfac_module_factors(prog, factors, n_v).items():
+            A = mix(old.get('A', {}).get(mod), A)
+            G = mix(old.get('G', {}).get(mod), G)
+            new['A'][mod], new['G'][mod] = A, G
+            pi = float(torch.sqrt((torch.trace(A) / A.shape[0]) / (torch.trace(G) / G.shape[0])))
+            gw = torch.as_tensor(gtree[mod]['w'], device=dev)
+            if 'b' in gtree[mod]:
+                gw = torch.cat([gw, torch.as_tensor(gtree[mod]['b'], device=dev)[None]], 0)
+            Ad = A + pi * sq * torch.eye(A.shape[0], dtype=A.dtype, device=dev)
+            Gd = G + sq / pi * torch.eye(G.shape[0], dtype=G.dtype, device=dev)
+            d = torch.cholesky_solve(gw, torch.linalg.cholesky(Ad))
+            d = torch.cholesky_solve(d.T.contiguous(), torch.linalg.cholesky(Gd)).T
+            d = d.cpu().numpy()
+            delta[mod]['w'] = d[:gw.shape[0] - int('b' in gtree[mod])]
+            if 'b' in gtree[mod]:
+                delta[mod]['b'] = d[-1]
+        # the diagonal block: every parameter element outside the Kronecker modules
+        kron = set(new['A'])
+        elems = np.concatenate([np.arange(base, base + int(np.prod(shape))) for (mod, leaf), (base, shape) in prog.grad_leaves.items()
+                                if mod not in kron] or [np.zeros(0, np.int64)]).astype(np.int64)
+        if elems.size:
+            o = torch.zeros(rest.shape[0], elems.size, dtype=torch.float64, device=dev)
+            for col in _rest_gather(prog, elems):
+                sel = torch.as_tensor(col >= 0, device=dev)
+                o[:, sel] += rest[:, torch.as_tensor(col[col >= 0], device=dev)].double()
+            F = mix(old.get('diag'), (o * o).sum(0) / n_v)
+            new['diag'] = F
+            gflat = np.concatenate([np.asarray(gtree[mod][leaf]).reshape(-1) for (mod, leaf) in prog.grad_leaves])
+            dflat = gflat[elems] / (F.cpu().numpy() + damping)
+            pos = 0
+            for (mod, leaf), (base, shape) in prog.grad_leaves.items():
+                if mod in kron:
+                    continue
+                n = int(np.prod(shape))
+                delta[mod][leaf] = dflat[pos:pos + n].reshape(shape)
+                pos += n
+        state[s] = new
+        deltas.append(delta)
+        gs.append(gtree)
+        dots.append(sum(float(np.sum(delta[m][k] * gtree[m][k])) for m in gtree for k in gtree[m]))
+    stats['grad'] = gs
+    stats['precon_grad_dot'] = torch.tensor(dots, dtype=torch.float64)
+    return loss, deltas, stats, state

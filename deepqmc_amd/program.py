@@ -184,6 +184,96 @@ class Program:
             out = torch.zeros(J.shape[0], self.n_params(), dtype=J.dtype, device=J.device)
         return out
 
+    def kfac_layout(self):
+        """The layout of dqmc_log_psi_kfac's outputs (include/dqmc.h), computed from the program: {'n_linear', 'n_factor_doubles',
+        'n_rest', 'rest_index': the flat weight entries of the rest columns (ascending), 'ops': one dict per LINEAR op in program
+        order with 'op' (index into ops), 'module', 'nrows', 'has_bias', 'd_a', 'd_g' and the offsets 'a_off', 'g_off' of A_l
+        and G_l in the factor buffer}."""
+        owned = np.zeros(self.weights.size, bool)
+        slot_mod = {sl[0]: sl[1] for sl in self.weight_slots}
+        ops, off = [], 0
+        for k, op in enumerate(self.ops):
+            if op.kind != OP_LINEAR:
+                continue
+            i = op.i
+            rows = sum(pad4(i[3 + 4 * p]) for p in range(i[0]))
+            has_bias = i[23] >= 0
+            d_a, d_g = rows + int(has_bias), pad4(i[21])
+            owned[i[22]:i[22] + rows * d_g] = True
+            if has_bias:
+                owned[i[23]:i[23] + d_g] = True
+            ops.append(dict(op=k, module=slot_mod.get(i[22], op.note), nrows=i[20], has_bias=has_bias, d_a=d_a, d_g=d_g, a_off=off, g_off=off + d_a * d_a))
+            off += d_a * d_a + d_g * d_g
+        rest = np.nonzero(~owned)[0]
+        return dict(n_linear=len(ops), n_factor_doubles=off, n_rest=int(rest.size), rest_index=rest, ops=ops)
+
+    def kfac_blocks(self):
+        """The LINEAR ops grouped by haiku module, for Kronecker-factored preconditioning.  Returns (blocks, fallback):
+        blocks = {module: {'ops': [indices into kfac_layout()['ops']], 'rows': [per op: int array over the op's d_A rows of A,
+        the module's w row (bias: n_in) or -1 for padding], 'cols': [per op: int array over its ldw columns of G, the w column
+        or -1], 'n_in', 'n_out', 'has_bias', 'R': total rows per walker of the module's ops}}, built from grad_src; every op's
+        maps are checked to be permutations of the module's w rows (+ bias) and columns.  fallback = the names of the modules
+        with a 'w' leaf that is not mapped this way (no op, or an op that covers only part of w): their parameters take the
+        diagonal treatment."""
+        if self.grad_unsupported:
+            raise NotImplementedError(f'kfac_blocks: unsupported for this program ({self.grad_unsupported})')
+        lay = self.kfac_layout()
+        by_mod: Dict[str, list] = {}
+        for q, o in enumerate(lay['ops']):
+            by_mod.setdefault(o['module'], []).append(q)
+        blocks, fallback = {}, []
+        for (mod, leaf), (base, shape) in self.grad_leaves.items():
+            if leaf != 'w':
+                continue
+            if mod not in by_mod or len(shape) != 2:
+                fallback.append(mod)
+                continue
+            n_in, n_out = shape
+            b_base = self.grad_leaves[(mod, 'b')][0] if (mod, 'b') in self.grad_leaves else None
+            ok, rows_l, cols_l = True, [], []
+            for q in by_mod[mod]:
+                o = lay['ops'][q]
+                i = self.ops[o['op']].i
+                ldw, wr = o['d_g'], o['d_a'] - int(o['has_bias'])
+                if o['has_bias'] != (b_base is not None):
+                    ok = False
+                    break
+                src = self.grad_src[i[22]:i[22] + wr * ldw].reshape(wr, ldw)
+                rel = np.where(src >= 0, src - base, -1)
+                if ((src >= 0) & ((rel < 0) | (rel >= n_in * n_out))).any():
+                    ok = False
+                    break
+                rows = np.full(o['d_a'], -1, np.int64)
+                cols = np.full(ldw, -1, np.int64)
+                rr, cc = np.nonzero(src >= 0)
+                k_in, k_out = rel[rr, cc] // n_out, rel[rr, cc] % n_out
+                # every packed row holds one w row, every packed column one w column, consistently
+                rows[:wr][rr] = k_in
+                cols[cc] = k_out
+                if not (np.array_equal(rows[rr], k_in) and np.array_equal(cols[cc], k_out)):
+                    ok = False
+                    break
+                if o['has_bias']:
+                    bsrc = self.grad_src[i[23]:i[23] + ldw]
+                    if not np.array_equal(bsrc >= 0, cols >= 0) or not np.array_equal(bsrc[cols >= 0] - b_base, cols[cols >= 0]):
+                        ok = False
+                        break
+                    rows[wr] = n_in
+                full_r = np.sort(rows[:wr][rows[:wr] >= 0])
+                full_c = np.sort(cols[cols >= 0])
+                if not (np.array_equal(full_r, np.arange(n_in)) and np.array_equal(full_c, np.arange(n_out))
+                        and rr.size == n_in * n_out):
+                    ok = False
+                    break
+                rows_l.append(rows)
+                cols_l.append(cols)
+            if not ok:
+                fallback.append(mod)
+                continue
+            blocks[mod] = dict(ops=by_mod[mod], rows=rows_l, cols=cols_l, n_in=n_in, n_out=n_out, has_bias=b_base is not None,
+                               R=sum(lay['ops'][q]['nrows'] for q in by_mod[mod]))
+        return blocks, fallback
+
     def c_bufs(self):
         arr = (DqmcBuf * len(self.bufs))()
         for k, (r, w) in enumerate(self.bufs):

@@ -153,3 +153,15 @@ class NeuralNetworkWaveFunction:
         del J
         return Psi(sign, log), Jp
 
+    def log_psi_kfac(self, params, phys_conf, cotangent=None):
+        """log_psi_vjp plus the KFAC statistics of the same reverse pass (Engine.log_psi_kfac): returns (Psi(sign, log), grad
+        tree, factors, rest) with factors the per-LINEAR-op (A, G) float64 tensors and rest the [B, n_rest] per-walker partials
+        of the entries no LINEAR op owns (Program.kfac_layout / kfac_blocks map both onto the parameters).  The same programs
+        as log_psi_vjp are supported."""
+        r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
+        R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
+        eng = self.engine(params, R)
+        if eng.program.grad_unsupported:
+            raise NotImplementedError(f'log_psi_kfac: unsupported for this program ({eng.program.grad_unsupported})')
+        sign, log, g, factors, rest = eng.log_psi_kfac(r, cotangent, R)
+        return Psi(sign, log), eng.program.unflatten_grad(g), factors, rest

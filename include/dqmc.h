@@ -21,6 +21,7 @@
  *   dqmc_log_psi_vjp    <- jax.vjp of vmap(ansatz.apply)(., r).log with a cotangent per walker
  *                          (loss/loss_function.py:59-75): the parameter gradient of the energy loss
  *   dqmc_log_psi_jacobian <- the per-walker rows of that Jacobian (natural-gradient / KFAC preconditioners)
+ *   dqmc_log_psi_kfac   <- the loss gradient plus the KFAC Kronecker factors of every linear layer
  *
  * Conventions: plain pointers and sizes only.  Unless marked "host", every pointer is a
  * DEVICE pointer.  Walker-major contiguous layouts: r[B][N][3], R[n_nuc][3].  `real` is
@@ -186,6 +187,33 @@ int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const v
  * unchunked one bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
 int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, void* jac, size_t ld_jac,
                           void* logpsi, int32_t* sign);
+
+/* KFAC Kronecker factors from the reverse pass.  A walker is valid when its sign is nonzero and its log|psi| is finite;
+ * every sum below runs over the valid walkers only.  For each DQMC_OP_LINEAR op l, in program order, with nrows_l rows
+ * per walker, pieces p of K_p inputs, ldw = pad4(nout):
+ *   x~[b][r]  the op's input row of walker b, row r: the pieces concatenated in packed-weight row order, piece p taking
+ *             pad4(K_p) entries (zeros past K_p; a broadcast piece gives walker b's one row to every r), then a 1 if the
+ *             op has a bias;  d_A = sum_p pad4(K_p) + has_bias.
+ *   dZ1[b][r] d log|psi(r_b)| / d Z[b][r] over the ldw pre-activation columns (padding columns 0): the adjoint of a unit
+ *             cotangent.
+ *   A_l = sum_b sum_r x~ x~^T   double[d_A][d_A], row-major; A_l[d_A-1][d_A-1] = n_valid * nrows_l when has_bias.
+ *   G_l = sum_b sum_r dZ1 dZ1^T double[ldw][ldw], row-major.
+ * Padding rows and columns of both are exact zeros.
+ * Layout of `factors`: A_0, G_0, A_1, G_1, ... contiguous in program order (A_l at the sum of d_A^2 + ldw^2 over the ops
+ * before l).  "Rest" entries: the flat weight entries (dqmc_set_weights layout) that lie in no LINEAR op's W block
+ * (sum_p pad4(K_p) x ldw at its weight offset) or bias block (ldw at its bias offset), in ascending order: envelopes,
+ * cusp alphas, conf_coeff, CONST tables, padding.
+ *   dqmc_kfac_layout: host outputs, each may be NULL: the number of LINEAR ops, the doubles of `factors`, the rest entries.
+ *   dqmc_log_psi_kfac arguments:
+ *     cot     real[B] or NULL (ones);  grad double[n_weights]: sum_b cot[b] d log|psi_b| / d w, as dqmc_log_psi_vjp;
+ *     factors double[n_factor_doubles];  rest real[B][n_rest] or NULL: rest[b][j] = d log|psi(r_b)| / d w of rest entry j
+ *     (the values dqmc_log_psi_jacobian writes into those columns; invalid walkers get zeros);  logpsi / sign optional.
+ * One value pass and one reverse pass (unit cotangent) per walker chunk ("ws_budget_mb", dqmc_last_chunks); the cotangent
+ * weights the walker sums of grad.  No atomics: identical calls are bit-identical; with cot == NULL grad equals
+ * dqmc_log_psi_vjp's bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
+int dqmc_kfac_layout(dqmc_ctx* ctx, int* n_linear, size_t* n_factor_doubles, size_t* n_rest);
+int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, double* factors,
+                      void* rest, void* logpsi, int32_t* sign);
 
 /* Gaussian-type effective core potential (reference ecp/gaussian_type_ecp.py:32-93 table layout,
  * :127-159 local part, :161-255 non-local part; replaces GaussianTypeECP.__init__'s pyscf lookup by
