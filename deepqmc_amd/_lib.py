@@ -29,6 +29,8 @@ SIGNATURES = [
     ('dqmc_log_psi_jacobian', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     ('dqmc_kfac_layout', c_int, [c_void_p, POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]),
     ('dqmc_log_psi_kfac', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ('dqmc_log_psi_grad_coords', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ('dqmc_hf_force', c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
     ('dqmc_mcmc_steps', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                 c_int, c_double, c_uint64, c_void_p, c_void_p, c_void_p, POINTER(c_double)]),
     ('dqmc_langevin_update', c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -4,7 +4,8 @@
 // This file: the context base, the state of Engine<real> (members, options' storage, captured-graph bookkeeping), and
 // the extern "C" entry points.  The member functions live in engine_*.inl by concern -- program analyses
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
-// float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl) -- and
+// float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), reverse
+// passes (engine_grad.inl, engine_jac.inl, engine_kfac.inl), coordinate gradients and forces (engine_coords.inl) -- and
 // are included inside the struct body: one translation unit, as before.
 #include <hip/hip_runtime.h>
 
@@ -62,6 +63,9 @@ struct dqmc_ctx {
   virtual int log_psi_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* logpsi, int32_t* sign) = 0;
   virtual int log_psi_jacobian(const void* r, const void* R, int B, void* jac, size_t ld_jac, void* logpsi, int32_t* sign) = 0;
   virtual int kfac_layout(int* n_linear, size_t* n_factor_doubles, size_t* n_rest) = 0;
+  virtual int log_psi_grad_coords(const void* r, const void* R, int B, void* grad_r, void* grad_R, void* logpsi, int32_t* sign) = 0;
+  virtual int hf_force(int est, const void* r, const void* R, int B, const void* grad_r, const void* grad_R, const void* e_loc,
+                       double energy, double* force) = 0;
   virtual int log_psi_kfac(const void* r, const void* R, int B, const void* cot, double* grad, double* factors, void* rest,
                            void* logpsi, int32_t* sign) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
@@ -450,6 +454,7 @@ struct Engine : dqmc_ctx {
 #include "engine_grad.inl"
 #include "engine_jac.inl"
 #include "engine_kfac.inl"
+#include "engine_coords.inl"
 };
 
 }  // namespace
@@ -534,6 +539,18 @@ int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const 
   if (!ctx || !r || !R || !grad || !factors) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->log_psi_kfac(r, R, B, cot, grad, factors, rest, logpsi, sign);
+}
+int dqmc_log_psi_grad_coords(dqmc_ctx* ctx, const void* r, const void* R, int B, void* grad_r, void* grad_R, void* logpsi,
+                             int32_t* sign) {
+  if (!ctx || !r || !R) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->log_psi_grad_coords(r, R, B, grad_r, grad_R, logpsi, sign);
+}
+int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, int B, const void* grad_r, const void* grad_R,
+                  const void* e_loc, double energy, double* force) {
+  if (!ctx || !r || !R || !force) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->hf_force(estimator, r, R, B, grad_r, grad_R, e_loc, energy, force);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

@@ -17,6 +17,11 @@
     double* factors;             // A_l, G_l of every LINEAR op, accumulated
     real* rest;                  // [B][n_rest] partials of the entries no LINEAR op owns, or nullptr
   };
+  // dqmc_log_psi_grad_coords's outputs for one chunk (engine_coords.inl); either may be nullptr
+  struct CoordChunk {
+    real* grad_r;                // [B][N][3]
+    real* grad_R;                // [B][n_nuc][3]
+  };
   GradDev g_ws, g_tab;
   size_t g_ws_bytes = 0;
   std::vector<int> g_tab_of;     // per op: {rows table offset, Sr, senders table offset, Ss} into g_tab (CONV, EDGE_SUM)
@@ -138,8 +143,10 @@
   // grad unused) row b of jac[B][ld_jac] receives walker b's parameter partials (engine_jac.inl).
   // kf != nullptr (dqmc_log_psi_kfac, cot == nullptr, jac == nullptr): the adjoints are those of a unit cotangent; kf->cot
   // weights the walker sums of grad, and the KFAC factors and rest partials are formed on the way (engine_kfac.inl).
+  // cc != nullptr (dqmc_log_psi_grad_coords, cot, grad, jac and kf all nullptr): no parameter gradients; the adjoints are carried
+  // into the coordinates instead (engine_coords.inl).
   int grad_chunk(const real* r, const real* R, int B, const real* cot, double* grad, real* logpsi, int32_t* sign, real* jac,
-                 size_t ld_jac, const KfacChunk* kf = nullptr) {
+                 size_t ld_jac, const KfacChunk* kf = nullptr, const CoordChunk* cc = nullptr) {
     // adjoint workspace of this chunk
     std::vector<size_t> adj(bufs.size());
     size_t off = 0;
@@ -148,11 +155,12 @@
     const size_t adj_end = off;
     const size_t o_z = bump(sizeof(real) * (size_t)B * grad_zrow()), o_dz = bump(sizeof(real) * (size_t)B * grad_zrow());
     const size_t o_dzs = bump(sizeof(real) * (size_t)B * grad_max_ldw());
-    const size_t o_orb = bump(sizeof(double) * (size_t)B * (grad_orb_partials() ? grad_orb_partials() : 1));
+    const size_t o_orb = bump(sizeof(double) * (size_t)B * (!cc && grad_orb_partials() ? grad_orb_partials() : 1));
     const size_t o_dl = bump(sizeof(double) * (size_t)B * sys.n_det), o_pw = bump(sizeof(double) * (size_t)B * (sys.n_det + 2));
     const size_t o_lp = bump(sizeof(real) * (size_t)B), o_sg = bump(sizeof(int32_t) * (size_t)B);
-    const size_t o_part = bump(grad_part_bytes());
+    const size_t o_part = bump(cc ? 0 : grad_part_bytes());
     const size_t o_kw = bump(kf ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = bump(kf ? kfac_part_bytes() : 0);
+    const size_t o_slot = bump(cc ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
     if (off > g_ws_bytes) {
       if (g_ws.p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(g_ws.p)); g_ws.p = nullptr; g_ws_bytes = 0; }
       const hipError_t e = hipMalloc(&g_ws.p, off);
@@ -177,13 +185,21 @@
     }
     const int32_t* gt = (const int32_t*)g_tab.p;
     double* dL = reinterpret_cast<double*>(gw + o_dl);
+    double* slot = cc ? reinterpret_cast<double*>(gw + o_slot) : nullptr;     // coordinate-difference adjoints (kernels_coords.inl)
     for (size_t opi = ops.size(); opi-- > 0;) {
       const dqmc_op& op = ops[opi];
       const int32_t* i = op.i;
       switch (op.kind) {
-        case DQMC_OP_FEAT_EN:
+        case DQMC_OP_FEAT_EN:      // leaves: no parameters; only the coordinate mode carries their adjoints on
+          if (cc)
+            dqmc::launch_feat_en_coords<real>(st, r, R, A(i[0]), bufs[i[0]].width, B, N, sys.n_nuc, sys.norm_eps, i[1],
+                                              slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+          break;
         case DQMC_OP_FEAT_EE:
-          break;       // leaves: no parameters, no adjoint to pass on
+          if (cc)
+            dqmc::launch_feat_ee_coords<real>(st, r, R, d_it + i[1], A(i[0]), i[2], B, N, sys.norm_eps, i[3],
+                                              slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+          break;
         case DQMC_OP_LINEAR: {
           // Z = X W + b with the forward kernel (no activation, no residual)
           dqmc::LinArgs<real> f{};
@@ -206,14 +222,14 @@
           f.W = d_w + i[22]; f.ldw = pad4(i[21]); f.bias = i[23] >= 0 ? d_w + i[23] : nullptr;
           f.dst = Z; f.ld_dst = f.ldw; f.rpw_dst = i[20]; f.r0_dst = 0; f.col0_dst = 0;
           f.act = 0; f.nrows = i[20]; f.B = B; f.T = 1; f.TP = 1;
-          t_begin(jac ? "linear_jac" : "linear_bwd", 6.0 * B * i[20] * (double)w_row * f.ldw);     // Z recompute, dX, dW
+          t_begin(cc ? "linear_dx" : jac ? "linear_jac" : "linear_bwd", (cc ? 4.0 : 6.0) * B * i[20] * (double)w_row * f.ldw);     // Z recompute, dX, dW
           dqmc::launch_linear<real>(st, f);
           a.W = f.W; a.ldw = f.ldw; a.nout = i[21]; a.nrows = i[20]; a.B = B; a.act = i[24];
           a.Z = Z; a.dZ = reinterpret_cast<real*>(gw + o_dz); a.dZs = reinterpret_cast<real*>(gw + o_dzs);
           a.dY = A(i[17]); a.ld_dst = bufs[i[17]].width; a.rpw_dst = bufs[i[17]].rows; a.r0_dst = i[18]; a.col0_dst = i[19];
           if (i[25] >= 0) { a.dres = A(i[25]); a.ld_res = bufs[i[25]].width; a.rpw_res = bufs[i[25]].rows; a.r0_res = i[26]; }
           a.res_scale = i[27] ? (real)0.70710678118654752440 : (real)1;
-          a.dW = grad + i[22]; a.dbias = i[23] >= 0 ? grad + i[23] : nullptr;
+          a.dW = cc ? nullptr : grad + i[22]; a.dbias = !cc && i[23] >= 0 ? grad + i[23] : nullptr;
           a.part = reinterpret_cast<double*>(gw + o_part);
           a.wt = kw;
           if (jac) dqmc::launch_linear_jac<real>(st, a, jo, i[22], i[23]);
@@ -247,6 +263,7 @@
           break;
         }
         case DQMC_OP_CONST:
+          if (cc) break;
           if (jac) {
             dqmc::launch_jac_scatter<real, real>(st, A(i[0]), (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width,
                                                  B, jo, i[1]);
@@ -263,7 +280,15 @@
           double* pw = reinterpret_cast<double*>(gw + o_orb);
           t_begin("orbitals_bwd", 0);
           dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[0]), A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
-                                          d_w + i[4], d_w + i[5], pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps);
+                                          d_w + i[4], d_w + i[5], cc ? nullptr : pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det,
+                                          sys.norm_eps);
+          if (cc) {
+            dqmc::launch_orbitals_coords<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
+                                               d_w + i[4], d_w + i[5], B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps,
+                                               slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+            t_end();
+            break;
+          }
           for (int q = 0; q < 4; ++q) {
             if (jac) { dqmc::launch_jac_scatter<double, real>(st, pw + (size_t)q * KN * L, 4L * KN * L, KN * L, B, jo, i[2 + q]); continue; }
             if (kf && kf->rest) dqmc::launch_jac_scatter<double, real>(st, pw + (size_t)q * KN * L, 4L * KN * L, KN * L, B, ko, k_rest_pos[i[2 + q]]);
@@ -292,6 +317,12 @@
           a.pw = reinterpret_cast<double*>(gw + o_pw);
           a.B = B; a.N = N; a.n_up = sys.n_up; a.K = sys.n_det;
           dqmc::launch_final_bwd<real>(st, a);
+          if (cc) {
+            if (i[2])
+              dqmc::launch_cusp_coords<real>(st, r, d_w + i[3], i[2], op.f[0], op.f[1], sys.norm_eps, B, N, sys.n_up,
+                                             slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+            break;
+          }
           if (jac) {
             if (i[1] >= 0) dqmc::launch_jac_scatter<double, real>(st, a.pw, sys.n_det + 2, sys.n_det, B, jo, i[1]);
             dqmc::launch_jac_scatter<double, real>(st, a.pw + sys.n_det, sys.n_det + 2, 2, B, jo, i[3]);
@@ -309,6 +340,8 @@
           return fail(DQMC_E_UNSUPPORTED, "log_psi_vjp: op kind " + std::to_string(op.kind));
       }
     }
+    if (cc)
+      dqmc::launch_coords_gather<real>(st, slot, c_n_slots, (const int32_t*)c_tab.p, c_S, lp, sg, B, N, sys.n_nuc, cc->grad_r, cc->grad_R);
     HIP_TRY(hipGetLastError());
     return DQMC_OK;
   }

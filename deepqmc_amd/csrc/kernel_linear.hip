@@ -1229,3 +1229,4 @@ template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 #include "kernels_grad.inl"
 #include "kernels_jac.inl"
 #include "kernels_kfac.inl"
+#include "kernels_coords.inl"

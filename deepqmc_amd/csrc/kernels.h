@@ -354,7 +354,7 @@ template <typename real> struct LinBwdArgs {
   real* dres;         // adjoint of the residual input, or nullptr
   int ld_res, rpw_res, r0_res;
   real res_scale;
-  double* dW;         // gradient of W (double, flat weight layout), accumulated
+  double* dW;         // gradient of W (double, flat weight layout), accumulated; nullptr (with dbias nullptr): dX only
   double* dbias;      // gradient of the bias, or nullptr
   double* part;       // split-K scratch: grad_dw_part_doubles of the largest block
   const double* wt;   // per-walker weights of the weight-gradient sums (dqmc_log_psi_kfac), or nullptr: unweighted
@@ -413,7 +413,8 @@ template <typename real> struct FinalBwdArgs {
 template <typename real> void launch_final_bwd(hipStream_t st, const FinalBwdArgs<real>& a);
 constexpr int GRAD_GJ_NMAX = 44;      // largest N of the Gauss-Jordan inverse of k_slogdet_bwd (as the forward slogdet)
 template <typename real> void launch_slogdet_bwd(hipStream_t st, const real* orb, int orb_w, const double* dL, real* dorb, int B, int K, int N);
-// pw: per-walker partials double[B][4][K*N][n_nuc*n_env] of the pi_up / pi_down / zeta_up / zeta_down tables
+// pw: per-walker partials double[B][4][K*N][n_nuc*n_env] of the pi_up / pi_down / zeta_up / zeta_down tables, or nullptr (the
+// backflow adjoint alone)
 template <typename real>
 void launch_orbitals_bwd(hipStream_t st, const real* r, const real* R, const real* bf, int bf_w, real* dbf, const real* dorb, int orb_w,
                          const real* pi_up, const real* pi_dn, const real* ze_up, const real* ze_dn, double* pw, int B, int N, int n_up,
@@ -466,5 +467,29 @@ template <typename real>
 void launch_kfac_factors(hipStream_t st, const LinBwdArgs<real>& a, int has_bias, const double* ok, double* A, double* G, double* part);
 // w[b] = cot[b] (cot == nullptr: 1) and w[B + b] = 1 for valid walkers, 0 and 0 otherwise
 template <typename real> void launch_kfac_weights(hipStream_t st, const real* lp, const int32_t* sg, const real* cot, double* w, int B);
+
+// ---- kernels_coords.inl (included by kernel_linear.hip): coordinate reverse pass (dqmc_log_psi_grad_coords), force estimators ----
+// Slots: double[B][n_slots][3], d log|psi| / d d of one difference d = r_p - r_q each; `slot` points at the first slot of the op's
+// range.  FEAT_EN / ORBITALS: slot i * n_nuc + a (d = r_i - R_a); FEAT_EE: slot `row`; cusps: the pair (i < j, row-major), d = r_i - r_j.
+template <typename real>
+void launch_feat_en_coords(hipStream_t st, const real* r, const real* R, const real* dx, int width, int B, int N, int n_nuc, double eps,
+                           int log_rescale, double* slot, int n_slots);
+template <typename real>
+void launch_feat_ee_coords(hipStream_t st, const real* r, const real* R, const int32_t* pairs, const real* de, int n_rows, int B, int N,
+                           double eps, int log_rescale, double* slot, int n_slots);
+template <typename real>
+void launch_orbitals_coords(hipStream_t st, const real* r, const real* R, const real* bf, int bf_w, const real* dorb, int orb_w,
+                            const real* pi_up, const real* pi_dn, const real* ze_up, const real* ze_dn, int B, int N, int n_up, int n_env,
+                            int n_nuc, int K, double eps, double* slot, int n_slots);
+template <typename real>
+void launch_cusp_coords(hipStream_t st, const real* r, const real* alphas, int cusp_kind, double same_scale, double anti_scale,
+                        double eps, int B, int N, int n_up, double* slot, int n_slots);
+// grad_r[b][i] / grad_R[b][a] (either may be nullptr) = sum over tab[particle][S][2] = (slot, +1 / -1), slot -1 = end of the list
+template <typename real>
+void launch_coords_gather(hipStream_t st, const double* slot, int n_slots, const int32_t* tab, int S, const real* lp, const int32_t* sg,
+                          int B, int N, int n_nuc, real* grad_r, real* grad_R);
+template <typename real>
+void launch_hf_force(hipStream_t st, int est, const real* r, const real* R, const double* Z, const real* gr, const real* gR,
+                     const real* e_loc, double energy, int B, int N, int n_nuc, double* force);
 
 }  // namespace dqmc

@@ -328,10 +328,10 @@ __global__ void __launch_bounds__(256) k_orbitals_bwd(const real* __restrict__ r
   const int lo = sp ? n_up : 0, hi = sp ? N : n_up;
   const real* pi = (sp ? pi_dn : pi_up) + (long)o * L;
   const real* ze = (sp ? ze_dn : ze_up) + (long)o * L;
-  double* p_pi = pw + ((long)b * 4 + sp) * KN * L + (long)o * L;
-  double* p_ze = pw + ((long)b * 4 + 2 + sp) * KN * L + (long)o * L;
+  double* p_pi = pw ? pw + ((long)b * 4 + sp) * KN * L + (long)o * L : nullptr;
+  double* p_ze = pw ? pw + ((long)b * 4 + 2 + sp) * KN * L + (long)o * L : nullptr;
   const real* rb = r + (long)b * N * 3;
-  for (int a = 0; a < L; ++a) {
+  for (int a = 0; pw && a < L; ++a) {      // table partials (none without pw)
     const int nuc = a / n_env;
     const double z = (double)ze[a], az = fabs(z), sz = (double)((z > 0) - (z < 0));
     double s_pi = 0, s_ze = 0;
@@ -385,7 +385,7 @@ void launch_linear_bwd(hipStream_t st, const LinBwdArgs<real>& a) {
   for (int p = 0; p < a.n_pieces; ++p) {
     const LinBwdPiece<real>& q = a.piece[p];
     const int kt = (q.K + 15) / 16;
-    dw(q.X, q.ld, q.rpw, q.r0, q.bcast, q.K, a.dW + (long)q.w_row * a.ldw);
+    if (a.dW) dw(q.X, q.ld, q.rpw, q.r0, q.bcast, q.K, a.dW + (long)q.w_row * a.ldw);
     if (!q.dX) continue;
     // input adjoint; a broadcast piece first sums the segment's rows of dZ per walker
     if (q.bcast) {

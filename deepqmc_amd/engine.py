@@ -20,6 +20,8 @@ from .types import PhysicalConfiguration
 
 F32_EPS = float(np.finfo(np.float32).eps)
 F64_EPS = float(np.finfo(np.float64).eps)
+# estimator codes of dqmc_hf_force (include/dqmc.h: DQMC_FORCE_*), in code order
+FORCE_ESTIMATORS = ('nuclear', 'bare', 'ac_zvq', 'ac_zvzbq', 'ac_zb', 'ac_zvqzb')
 SAMPLER_STAT_KEYS = ('sampling/acceptance', 'sampling/tau', 'sampling/age/mean', 'sampling/age/max',
                      'sampling/log_psi/mean', 'sampling/log_psi/std', 'sampling/dists/mean')
 
@@ -217,6 +219,51 @@ class Engine:
         factors = [(fac[o['a_off']:o['a_off'] + o['d_a'] ** 2].view(o['d_a'], o['d_a']),
                     fac[o['g_off']:o['g_off'] + o['d_g'] ** 2].view(o['d_g'], o['d_g'])) for o in lay['ops']]
         return sign, logpsi, grad, factors, rst
+
+    # ---- jax.grad of log|psi| with respect to the coordinates; force estimators ----
+    def log_psi_grad_coords(self, r, R=None, want_r=True, want_R=True):
+        """d log|psi(r_b)| / d r and d log|psi(r_b)| / d R per walker from the reverse pass (dqmc_log_psi_grad_coords).
+        Returns (sign, logpsi, grad_r [B, N, 3] or None, grad_R [B, n_nuc, 3] or None) in the engine's dtype on its device.
+        Walkers with sign 0 or a non-finite log|psi| get zero rows.  Programs with attention ops raise DqmcError (-4)."""
+        if not (want_r or want_R):
+            raise ValueError('log_psi_grad_coords: want_r and want_R are both False')
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+        gr = torch.empty(B, self.N, 3, dtype=self.dtype, device=self.device) if want_r else None
+        gR = torch.empty(B, self.hamil.n_nuc, 3, dtype=self.dtype, device=self.device) if want_R else None
+        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
+        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._check(self.lib.dqmc_log_psi_grad_coords(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B,
+                                                      gr.data_ptr() if gr is not None else None,
+                                                      gR.data_ptr() if gR is not None else None, logpsi.data_ptr(), sign.data_ptr()))
+        return sign, logpsi, gr, gR
+
+    def hf_force(self, estimator: str, r, R=None, grad_r=None, grad_R=None, e_loc=None, energy: float = 0.0):
+        """Per-walker Hellmann-Feynman force of `estimator` (one of FORCE_ESTIMATORS; formulas at dqmc_hf_force in
+        include/dqmc.h) as float64 [B, n_nuc, 3] on the device.  grad_r [B, N, 3] (the ZVQ family), grad_R [B, n_nuc, 3]
+        ('ac_zb', 'ac_zvqzb') and e_loc [B] (the estimators with a ZB term) are device tensors in the engine's dtype."""
+        if estimator not in FORCE_ESTIMATORS:
+            raise ValueError(f'unknown force estimator {estimator!r}; one of {FORCE_ESTIMATORS}')
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+
+        def arg(name, t, shape):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor) or t.dtype != self.dtype or not t.is_contiguous() or t.device.type != self.device.type \
+                    or tuple(t.shape) != shape:
+                raise DqmcError(f"'{name}' must be a contiguous {self.dtype} tensor of shape {shape} on {self.device}")
+            return t
+        grad_r = arg('grad_r', grad_r, (B, self.N, 3))
+        grad_R = arg('grad_R', grad_R, (B, self.hamil.n_nuc, 3))
+        e_loc = arg('e_loc', e_loc, (B,))
+        force = torch.empty(B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self._check(self.lib.dqmc_hf_force(self._ctx, FORCE_ESTIMATORS.index(estimator), r.data_ptr(), self._R(R).data_ptr(), B,
+                                           ptr(grad_r), ptr(grad_R), ptr(e_loc), float(energy), force.data_ptr()))
+        return force
 
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None):

@@ -165,3 +165,16 @@ class NeuralNetworkWaveFunction:
             raise NotImplementedError(f'log_psi_kfac: unsupported for this program ({eng.program.grad_unsupported})')
         sign, log, g, factors, rest = eng.log_psi_kfac(r, cotangent, R)
         return Psi(sign, log), eng.program.unflatten_grad(g), factors, rest
+
+    def log_psi_grad_coords(self, params, phys_conf):
+        """jax.grad of ansatz.apply(.).log with respect to the electron and the nuclear coordinates (reference force.py
+        make_grad_log_wf / make_grad_nuc_log_wf), per walker, from the reverse pass (Engine.log_psi_grad_coords): returns
+        (Psi(sign, log), grad_r [B, N, 3], grad_R [B, n_nuc, 3]) on the device, in the wave function's dtype.  The same
+        programs as log_psi_vjp are supported."""
+        r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
+        R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
+        eng = self.engine(params, R)
+        if eng.program.grad_unsupported:
+            raise NotImplementedError(f'log_psi_grad_coords: unsupported for this program ({eng.program.grad_unsupported})')
+        sign, log, gr, gR = eng.log_psi_grad_coords(r, R)
+        return Psi(sign, log), gr, gR

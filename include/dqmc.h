@@ -22,6 +22,10 @@
  *                          (loss/loss_function.py:59-75): the parameter gradient of the energy loss
  *   dqmc_log_psi_jacobian <- the per-walker rows of that Jacobian (natural-gradient / KFAC preconditioners)
  *   dqmc_log_psi_kfac   <- the loss gradient plus the KFAC Kronecker factors of every linear layer
+ *   dqmc_log_psi_grad_coords <- jax.grad of ansatz.apply(.).log with respect to r and R (force.py make_grad_log_wf,
+ *                          make_grad_nuc_log_wf), vmapped over walkers
+ *   dqmc_hf_force       <- the Hellmann-Feynman force estimators of force.py (nuclear_force, evaluate_hf_force_bare,
+ *                          evaluate_hf_force_ac_zvq / _zvzbq / _zb), per walker
  *
  * Conventions: plain pointers and sizes only.  Unless marked "host", every pointer is a
  * DEVICE pointer.  Walker-major contiguous layouts: r[B][N][3], R[n_nuc][3].  `real` is
@@ -214,6 +218,39 @@ int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, vo
 int dqmc_kfac_layout(dqmc_ctx* ctx, int* n_linear, size_t* n_factor_doubles, size_t* n_rest);
 int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, double* factors,
                       void* rest, void* logpsi, int32_t* sign);
+
+/* Per walker b: grad_r[b] = d log|psi(r_b)| / d r (real[B][N][3]) and grad_R[b] = d log|psi(r_b)| / d R
+ * (real[B][n_nuc][3]); either may be NULL, not both.  logpsi / sign optional, as dqmc_wf_eval.
+ * The reverse pass of dqmc_log_psi_vjp (value pass op by op, then the ops in reverse, per "ws_budget_mb" walker chunk) with
+ * no weight gradients: the adjoints of the feature, envelope and cusp inputs are carried into the coordinates.  Sums over
+ * the electrons and nuclei run in a fixed order (no atomics): identical calls are bit-identical, and a chunked call equals
+ * an unchunked one bit for bit.  Walkers with sign 0 or a non-finite log|psi| get zero rows.  By translation invariance
+ * sum_a grad_R[b][a] = -sum_i grad_r[b][i].  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
+int dqmc_log_psi_grad_coords(dqmc_ctx* ctx, const void* r, const void* R, int B, void* grad_r, void* grad_R,
+                             void* logpsi, int32_t* sign);
+
+/* Hellmann-Feynman force estimators (reference force.py), per walker b and nucleus I, Cartesian:
+ * force: device double[B][n_nuc][3], overwritten.  Z_I = the charges given to dqmc_create.  With d = r_i - R_I,
+ * rho = |d|, u = d / rho, g_i = grad_r[b][i], F_nuc,I = sum_{J != I} Z_I Z_J (R_I - R_J) / |R_I - R_J|^3:
+ *   DQMC_FORCE_NUCLEAR   F_nuc                                                       (nuclear_force)
+ *   DQMC_FORCE_BARE      F_nuc + Z_I sum_i d / rho^3                                 (evaluate_hf_force_bare, all-electron)
+ *   DQMC_FORCE_AC_ZVQ    F_nuc + Z_I sum_i (g_i - (u . g_i) u) / rho                 (evaluate_hf_force_ac_zvq)
+ *   DQMC_FORCE_AC_ZVZBQ  AC_ZVQ - 2 (e_loc[b] - energy) Z_I sum_i u                  (evaluate_hf_force_ac_zvzbq)
+ *   DQMC_FORCE_AC_ZB     BARE - 2 (e_loc[b] - energy) grad_R[b][I]                   (evaluate_hf_force_ac_zb)
+ *   DQMC_FORCE_AC_ZVQZB  AC_ZVQ - 2 (e_loc[b] - energy) grad_R[b][I]                 (AC_ZVQ with the ZB term of AC_ZB)
+ * r: real[B][N][3], R: real[n_nuc][3]; grad_r: real[B][N][3] (d log|psi| / d r, e.g. from dqmc_psi_grad), needed by the
+ * ZVQ family; grad_R: real[B][n_nuc][3] (dqmc_log_psi_grad_coords), needed by AC_ZB and AC_ZVQZB; e_loc: real[B], needed by
+ * the estimators with a ZB term; each may be NULL where it is not needed.  energy: the batch energy E.  Sums in double. */
+enum dqmc_force_estimator {
+  DQMC_FORCE_NUCLEAR = 0,
+  DQMC_FORCE_BARE = 1,
+  DQMC_FORCE_AC_ZVQ = 2,
+  DQMC_FORCE_AC_ZVZBQ = 3,
+  DQMC_FORCE_AC_ZB = 4,
+  DQMC_FORCE_AC_ZVQZB = 5
+};
+int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, int B, const void* grad_r, const void* grad_R,
+                  const void* e_loc, double energy, double* force);
 
 /* Gaussian-type effective core potential (reference ecp/gaussian_type_ecp.py:32-93 table layout,
  * :127-159 local part, :161-255 non-local part; replaces GaussianTypeECP.__init__'s pyscf lookup by
