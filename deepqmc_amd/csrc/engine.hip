@@ -4,8 +4,9 @@
 // This file: the context base, the state of Engine<real> (members, options' storage, captured-graph bookkeeping), and
 // the extern "C" entry points.  The member functions live in engine_*.inl by concern -- program analyses
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
-// float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), reverse
-// passes (engine_grad.inl, engine_jac.inl, engine_kfac.inl), coordinate gradients and forces (engine_coords.inl) -- and
+// float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
+// pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
+// engine_coords.inl, with the force estimators) -- and
 // are included inside the struct body: one translation unit, as before.
 #include <hip/hip_runtime.h>
 
@@ -452,6 +453,7 @@ struct Engine : dqmc_ctx {
 #include "engine_ecp.inl"
 #include "engine_mcmc.inl"
 #include "engine_grad.inl"
+#include "engine_reverse.inl"
 #include "engine_jac.inl"
 #include "engine_kfac.inl"
 #include "engine_coords.inl"

@@ -1,10 +1,9 @@
 // engine_coords.inl -- member functions of Engine<real>, included INSIDE the struct body by engine.hip: d log|psi| / d r and
 // d log|psi| / d R per walker (dqmc_log_psi_grad_coords) and the Hellmann-Feynman force estimators (dqmc_hf_force).
 //
-// The coordinate gradients are the reverse pass of engine_grad.inl in a third mode (CoordChunk): LINEAR forms dX only (no
-// weight-gradient GEMMs, no walker reductions), CONST is skipped, ORBITALS and FINAL form no parameter partials.  The ops that
-// read the coordinates (FEAT_EN, FEAT_EE, ORBITALS, the cusps of FINAL) turn their adjoints into one 3-vector per coordinate
-// difference they read ("slots", kernels_coords.inl); one gather per particle then sums them in the fixed order of c_tab.
+// The coordinate gradients are the Coords mode of the reverse pass (engine_reverse.inl).  The ops that read the coordinates
+// (FEAT_EN, FEAT_EE, ORBITALS, the cusps of FINAL) turn their adjoints into one 3-vector per coordinate difference they read
+// ("slots", kernels_coords.inl); one gather per particle then sums them in the fixed order of c_tab, which is built here.
 
   GradDev c_tab;                 // int32 [N + n_nuc][c_S][2]: (slot, +1 / -1) per particle, slot -1 = end of the list
   std::vector<int> c_slot0;      // per op: first slot of its range, -1: none
@@ -61,39 +60,12 @@
     return DQMC_OK;
   }
 
-  int log_psi_grad_coords(const void* r_, const void* R_, int B, void* grad_r, void* grad_R, void* logpsi_, int32_t* sign) override {
-    if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
+  int log_psi_grad_coords(const void* r, const void* R, int B, void* grad_r, void* grad_R, void* logpsi, int32_t* sign) override {
     if (!grad_r && !grad_R) return fail(DQMC_E_ARG, "log_psi_grad_coords: grad_r and grad_R are both NULL");
-    if (has_attention()) return fail(DQMC_E_UNSUPPORTED, "log_psi_grad_coords: no reverse pass for ATTENTION ops");
-    if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, "log_psi_grad_coords: more than 44 electrons");
-    const real* r = (const real*)r_;
-    const real* R = (const real*)R_;
-    real* logpsi = (real*)logpsi_;
-    { const int rc = grad_tables(); if (rc) return rc; }
     { const int rc = coord_tables(); if (rc) return rc; }
-    const size_t per = ws_bytes_per_walker(1) + grad_bytes_per_walker() + sizeof(double) * 3 * (size_t)c_n_slots;
-    long chunk = per ? (long)(ws_budget / per) : B;
-    if (chunk < 1) chunk = 1;
-    last_chunks[0] = chunk >= B ? 1 : (int)((B + chunk - 1) / chunk);
-    // the value pass op by op with every activation in memory, as dqmc_log_psi_vjp
-    const int fused_saved = fused_enabled;
-    std::vector<int> child_saved;
-    child_saved.swap(mlp_child);
-    mlp_child.assign(ops.size(), -1);
-    fused_enabled = 0;
-    int rc = DQMC_OK;
-    for (int b0 = 0; b0 < B && !rc; b0 += (int)chunk) {
-      const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
-      const CoordChunk cc{grad_r ? (real*)grad_r + (size_t)b0 * N * 3 : nullptr,
-                          grad_R ? (real*)grad_R + (size_t)b0 * sys.n_nuc * 3 : nullptr};
-      rc = grad_chunk(r + (size_t)b0 * N * 3, R, nb, nullptr, nullptr, logpsi ? logpsi + b0 : nullptr, sign ? sign + b0 : nullptr,
-                      nullptr, 0, nullptr, &cc);
-    }
-    fused_enabled = fused_saved;
-    mlp_child.swap(child_saved);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return DQMC_OK;
+    RevReq q{Rev::Coords};
+    q.logpsi = (real*)logpsi; q.sign = sign; q.grad_r = (real*)grad_r; q.grad_R = (real*)grad_R;
+    return reverse_pass((const real*)r, (const real*)R, B, q);
   }
 
   int hf_force(int est, const void* r, const void* R, int B, const void* grad_r, const void* grad_R, const void* e_loc, double energy,

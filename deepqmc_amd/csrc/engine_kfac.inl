@@ -1,12 +1,11 @@
 // engine_kfac.inl -- member functions of Engine<real>, included INSIDE the struct body by engine.hip: KFAC Kronecker factors
 // of the LINEAR ops from the reverse pass (dqmc_log_psi_kfac).
 //
-// One value pass and one reverse pass per walker chunk (grad_chunk with a KfacChunk).  The reverse pass is linear in the
-// cotangent and the cotangent enters only at FINAL, so it runs with a unit cotangent: every pre-activation adjoint is then the
-// dZ1 of G, and the cotangent is applied as a per-walker weight where parameter partials are summed over the walkers (the
-// split-K k_lin_dw and the colsums of CONST, ORBITALS and FINAL).  After each LINEAR backward has formed dZ, the factor
-// kernels (kernels_kfac.inl) add A_l and G_l of the chunk; the per-walker partials of the entries no LINEAR op owns go to
-// the compact `rest` block through the Jacobian's scatter.
+// One value pass and one reverse pass per walker chunk, the Kfac mode of engine_reverse.inl.  The reverse pass is linear in
+// the cotangent and the cotangent enters only at FINAL, so it runs with a unit cotangent: every pre-activation adjoint is then
+// the dZ1 of G, and the cotangent is applied as a per-walker weight where parameter partials are summed over the walkers (the
+// split-K k_lin_dw and the colsums of CONST, ORBITALS and FINAL).  Here: the layout of the factors and of the compact `rest`
+// block, which the per-walker partials of the entries no LINEAR op owns reach through the Jacobian's scatter.
 //
 // Layout (include/dqmc.h): LINEAR op l in program order owns A_l (d_A x d_A, d_A = sum_p pad4(K_p) + has_bias) followed by
 // G_l (ldw x ldw, ldw = pad4(nout)), both row-major double; rest column j is the j-th weight entry, ascending, that lies in
@@ -21,11 +20,7 @@
   int k_rest_nzero = 0;
   bool k_planned = false;
 
-  static long kfac_dim_a(const dqmc_op& o) {
-    long d = o.i[23] >= 0 ? 1 : 0;
-    for (int p = 0; p < o.i[0]; ++p) d += pad4(o.i[3 + 4 * p]);
-    return d;
-  }
+  static long kfac_dim_a(const dqmc_op& o) { return linear_w_rows(o) + (o.i[23] >= 0 ? 1 : 0); }
   static long kfac_dim_g(const dqmc_op& o) { return pad4(o.i[21]); }
   size_t kfac_part_bytes() const {
     size_t m = 0;
@@ -40,34 +35,18 @@
     { const int rc = jac_plan(); if (rc) return rc; }
     k_fac_off.assign(ops.size(), 0);
     std::vector<uint8_t> owned(n_weights, 0), written(n_weights, 0);
-    auto mark = [&](std::vector<uint8_t>& v, long off, long n) { for (long j = off; j < off + n; ++j) v[j] = 1; };
     k_fac_total = 0;
     k_n_linear = 0;
     for (size_t k = 0; k < ops.size(); ++k) {
-      const dqmc_op& o = ops[k];
-      const int32_t* i = o.i;
-      switch (o.kind) {
-        case DQMC_OP_LINEAR: {
-          const long da = kfac_dim_a(o), dg = kfac_dim_g(o);
-          k_fac_off[k] = k_fac_total;
-          k_fac_total += (size_t)(da * da + dg * dg);
-          ++k_n_linear;
-          mark(owned, i[22], (da - (i[23] >= 0 ? 1 : 0)) * dg);
-          if (i[23] >= 0) mark(owned, i[23], dg);
-          break;
-        }
-        case DQMC_OP_CONST: mark(written, i[1], (long)bufs[i[0]].rows * bufs[i[0]].width); break;
-        case DQMC_OP_ORBITALS: {
-          const long ne = (long)sys.n_det * N * sys.n_nuc * (i[6] > 0 ? i[6] : 1);
-          for (int q = 0; q < 4; ++q) mark(written, i[2 + q], ne);
-          break;
-        }
-        case DQMC_OP_FINAL:
-          if (i[1] >= 0) mark(written, i[1], sys.n_det);
-          mark(written, i[3], 2);
-          break;
-        default: break;
+      if (ops[k].kind == DQMC_OP_LINEAR) {
+        const long da = kfac_dim_a(ops[k]), dg = kfac_dim_g(ops[k]);
+        k_fac_off[k] = k_fac_total;
+        k_fac_total += (size_t)(da * da + dg * dg);
+        ++k_n_linear;
       }
+      for_each_weight_block(ops[k], [&](long off, long n, bool linear) {
+        for (long j = off; j < off + n; ++j) (linear ? owned : written)[j] = 1;
+      });
     }
     k_rest_pos.assign(n_weights, -1);
     std::vector<int32_t> zero;
@@ -98,41 +77,12 @@
     return DQMC_OK;
   }
 
-  int log_psi_kfac(const void* r_, const void* R_, int B, const void* cot_, double* grad, double* factors, void* rest_, void* logpsi_,
+  int log_psi_kfac(const void* r, const void* R, int B, const void* cot, double* grad, double* factors, void* rest, void* logpsi,
                    int32_t* sign) override {
-    if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
-    if (has_attention()) return fail(DQMC_E_UNSUPPORTED, "log_psi_kfac: no reverse pass for ATTENTION ops");
-    if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, "log_psi_kfac: more than 44 electrons");
-    const real* r = (const real*)r_;
-    const real* R = (const real*)R_;
-    const real* cot = (const real*)cot_;
-    real* rest = (real*)rest_;
-    real* logpsi = (real*)logpsi_;
-    { const int rc = grad_tables(); if (rc) return rc; }
     { const int rc = kfac_plan(); if (rc) return rc; }
-    const size_t per = ws_bytes_per_walker(1) + grad_bytes_per_walker() + 2 * sizeof(double);
-    const size_t fixed = grad_part_bytes() + kfac_part_bytes();
-    long chunk = per ? (long)((ws_budget > fixed ? ws_budget - fixed : 0) / per) : B;
-    if (chunk < 1) chunk = 1;
-    last_chunks[0] = chunk >= B ? 1 : (int)((B + chunk - 1) / chunk);
     HIP_TRY(hipMemsetAsync(grad, 0, sizeof(double) * n_weights, st));
     if (k_fac_total) HIP_TRY(hipMemsetAsync(factors, 0, sizeof(double) * k_fac_total, st));
-    // the value pass op by op with every activation in memory, as dqmc_log_psi_vjp
-    const int fused_saved = fused_enabled;
-    std::vector<int> child_saved;
-    child_saved.swap(mlp_child);
-    mlp_child.assign(ops.size(), -1);
-    fused_enabled = 0;
-    int rc = DQMC_OK;
-    for (int b0 = 0; b0 < B && !rc; b0 += (int)chunk) {
-      const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
-      const KfacChunk kf{cot ? cot + b0 : nullptr, factors, rest ? rest + (size_t)b0 * k_n_rest : nullptr};
-      rc = grad_chunk(r + (size_t)b0 * N * 3, R, nb, nullptr, grad, logpsi ? logpsi + b0 : nullptr, sign ? sign + b0 : nullptr, nullptr,
-                      0, &kf);
-    }
-    fused_enabled = fused_saved;
-    mlp_child.swap(child_saved);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return DQMC_OK;
+    RevReq q{Rev::Kfac};
+    q.logpsi = (real*)logpsi; q.sign = sign; q.cot = (const real*)cot; q.grad = grad; q.factors = factors; q.rest = (real*)rest;
+    return reverse_pass((const real*)r, (const real*)R, B, q);
   }

@@ -1,0 +1,288 @@
+// engine_reverse.inl -- member functions of Engine<real>, included INSIDE the struct body by engine.hip: the reverse pass of
+// log|psi| that dqmc_log_psi_vjp, dqmc_log_psi_jacobian, dqmc_log_psi_kfac and dqmc_log_psi_grad_coords share.  A request
+// (RevReq) names one of four modes and that mode's outputs; reverse_pass() checks it, sizes the walker chunks and runs
+// grad_chunk() on each.
+//
+// Per walker chunk: the per-op value pass (TP = 1, no fused kernel, no chained MLPs, so that every activation buffer the
+// reverse pass reads is in memory), then the ops in reverse with adjoint buffers of the same shapes.  LINEAR recomputes its
+// pre-activation Z = X W + b with the forward kernel (act = none) instead of storing it in the forward: the value pass
+// stays the one dqmc_wf_eval runs, and one extra GEMM per layer costs less than the other two (dX, dW) each.  Weight
+// gradients accumulate across chunks in double through fixed-order reductions (kernels_grad.inl).
+//
+// What the modes make of an op's per-walker parameter partials:
+//   Vjp     sum_b cot[b] (...) into grad (the cotangent enters at FINAL).
+//   Jac     unit cotangent; row b of jac[B][ld_jac] receives walker b's partials: LINEAR forms its weight blocks per walker
+//           (kernels_jac.inl, no split-K reduction), CONST / ORBITALS / FINAL copy theirs (engine_jac.inl).
+//   Kfac    unit cotangent, so every pre-activation adjoint is the dZ1 of G; cot is applied as a per-walker weight where
+//           partials are summed over the walkers into grad.  After each LINEAR backward has formed dZ, the factor kernels
+//           (kernels_kfac.inl) add A_l and G_l; partials of the entries no LINEAR op owns go to `rest` (engine_kfac.inl).
+//   Coords  no parameter partials: LINEAR forms dX only, CONST is skipped, and the ops that read the coordinates carry their
+//           adjoints into r and R (engine_coords.inl).
+
+  enum class Rev { Vjp, Jac, Kfac, Coords };
+  static const char* rev_name(Rev m) {
+    switch (m) {
+      case Rev::Vjp: return "log_psi_vjp";
+      case Rev::Jac: return "log_psi_jacobian";
+      case Rev::Kfac: return "log_psi_kfac";
+      default: return "log_psi_grad_coords";
+    }
+  }
+  // what one call (and, moved to walker b0 by at(), one chunk) asks of the reverse pass; only the fields of `mode` are read
+  struct RevReq {
+    Rev mode;
+    real* logpsi = nullptr;      // [B], optional in every mode
+    int32_t* sign = nullptr;     // [B], optional in every mode
+    const real* cot = nullptr;   // Vjp, Kfac: [B] cotangents, or nullptr (ones)
+    double* grad = nullptr;      // Vjp, Kfac: [n_weights], accumulated
+    real* jac = nullptr;         // Jac: [B][ld_jac]
+    size_t ld_jac = 0;
+    double* factors = nullptr;   // Kfac: A_l, G_l of every LINEAR op, accumulated
+    real* rest = nullptr;        // Kfac: [B][n_rest] partials of the entries no LINEAR op owns, or nullptr
+    real* grad_r = nullptr;      // Coords: [B][N][3], or nullptr
+    real* grad_R = nullptr;      // Coords: [B][n_nuc][3], or nullptr
+    template <class T> static T* adv(T* p, size_t n) { return p ? p + n : nullptr; }
+    RevReq at(size_t b0, int N, int n_nuc, size_t n_rest) const {   // the same request for the chunk that starts at walker b0
+      RevReq c = *this;
+      c.logpsi = adv(logpsi, b0); c.sign = adv(sign, b0); c.cot = adv(cot, b0);
+      c.jac = adv(jac, b0 * ld_jac); c.rest = adv(rest, b0 * n_rest);
+      c.grad_r = adv(grad_r, b0 * N * 3); c.grad_R = adv(grad_R, b0 * n_nuc * 3);
+      return c;
+    }
+  };
+
+  // For its lifetime the value pass runs op by op with every activation in memory: no fused kernel, no chained MLPs.
+  struct UnfusedForward {
+    Engine& e;
+    const int fused_saved;
+    std::vector<int> child_saved;
+    explicit UnfusedForward(Engine& e_) : e(e_), fused_saved(e_.fused_enabled) {
+      child_saved.swap(e.mlp_child);
+      e.mlp_child.assign(e.ops.size(), -1);
+      e.fused_enabled = 0;
+    }
+    ~UnfusedForward() { e.fused_enabled = fused_saved; e.mlp_child.swap(child_saved); }
+    UnfusedForward(const UnfusedForward&) = delete;
+    UnfusedForward& operator=(const UnfusedForward&) = delete;
+  };
+
+  // Walkers per chunk under ws_budget: the workspace of grad_chunk per walker, and the part that does not grow with the chunk.
+  // The modes differ on purpose (Coords reserves nothing for the split-K partials it never allocates).  Chunk boundaries fix
+  // the order in which chunks add into grad and factors, so a change here moves results in the last bits.
+  long rev_chunk_len(Rev mode, int B) const {
+    size_t per = ws_bytes_per_walker(1) + grad_bytes_per_walker(), fixed = 0;
+    switch (mode) {
+      case Rev::Vjp: case Rev::Jac: fixed = grad_part_bytes(); break;
+      case Rev::Kfac: per += 2 * sizeof(double); fixed = grad_part_bytes() + kfac_part_bytes(); break;
+      case Rev::Coords: per += sizeof(double) * 3 * (size_t)c_n_slots; break;
+    }
+    const long chunk = per ? (long)((ws_budget > fixed ? ws_budget - fixed : 0) / per) : B;
+    return chunk < 1 ? 1 : chunk;
+  }
+
+  // The caller has run its mode's plan (jac_plan, kfac_plan, coord_tables) and zeroed the accumulators it passes.
+  int reverse_pass(const real* r, const real* R, int B, const RevReq& q) {
+    const std::string name = rev_name(q.mode);
+    if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
+    if (has_attention()) return fail(DQMC_E_UNSUPPORTED, name + ": no reverse pass for ATTENTION ops");
+    if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 44 electrons");
+    { const int rc = grad_tables(); if (rc) return rc; }
+    const long chunk = rev_chunk_len(q.mode, B);
+    last_chunks[0] = chunk >= B ? 1 : (int)((B + chunk - 1) / chunk);
+    const UnfusedForward unfused(*this);
+    for (int b0 = 0; b0 < B; b0 += (int)chunk) {
+      const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
+      const int rc = grad_chunk(r + (size_t)b0 * N * 3, R, nb, q.at(b0, N, sys.n_nuc, k_n_rest));
+      if (rc) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return DQMC_OK;
+  }
+
+  int grad_chunk(const real* r, const real* R, int B, const RevReq& q) {
+    const bool jac = q.mode == Rev::Jac, kfac = q.mode == Rev::Kfac, coords = q.mode == Rev::Coords;
+    // adjoint workspace of this chunk
+    std::vector<size_t> adj(bufs.size());
+    size_t off = 0;
+    auto bump = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    for (size_t k = 0; k < bufs.size(); ++k) adj[k] = bump(sizeof(real) * (size_t)B * bufs[k].rows * bufs[k].width);
+    const size_t adj_end = off;
+    const size_t o_z = bump(sizeof(real) * (size_t)B * grad_zrow()), o_dz = bump(sizeof(real) * (size_t)B * grad_zrow());
+    const size_t o_dzs = bump(sizeof(real) * (size_t)B * grad_max_ldw());
+    const size_t o_orb = bump(sizeof(double) * (size_t)B * (!coords && grad_orb_partials() ? grad_orb_partials() : 1));
+    const size_t o_dl = bump(sizeof(double) * (size_t)B * sys.n_det), o_pw = bump(sizeof(double) * (size_t)B * (sys.n_det + 2));
+    const size_t o_lp = bump(sizeof(real) * (size_t)B), o_sg = bump(sizeof(int32_t) * (size_t)B);
+    const size_t o_part = bump(coords ? 0 : grad_part_bytes());
+    const size_t o_kw = bump(kfac ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = bump(kfac ? kfac_part_bytes() : 0);
+    const size_t o_slot = bump(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
+    if (off > g_ws_bytes) {
+      if (g_ws.p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(g_ws.p)); g_ws.p = nullptr; g_ws_bytes = 0; }
+      const hipError_t e = hipMalloc(&g_ws.p, off);
+      if (e != hipSuccess) return fail(DQMC_E_NOMEM, "gradient workspace of " + std::to_string(off) + " bytes: " + hipGetErrorString(e));
+      g_ws_bytes = off;
+    }
+    char* gw = (char*)g_ws.p;
+    auto A = [&](int b) { return reinterpret_cast<real*>(gw + adj[b]); };
+    real* lp = q.logpsi ? q.logpsi : reinterpret_cast<real*>(gw + o_lp);
+    int32_t* sg = q.sign ? q.sign : reinterpret_cast<int32_t*>(gw + o_sg);
+    { const int rc = run_chunk(r, R, B, false, lp, sg, nullptr, nullptr, B, nullptr, 0); if (rc) return rc; }
+    HIP_TRY(hipMemsetAsync(gw, 0, adj_end, st));
+    // where per-walker partials go: rows of J (Jac), rows of rest (Kfac)
+    const dqmc::JacOut<real> jo{q.jac, (long)q.ld_jac, lp, sg, jac_accum ? 1 : 0,
+                                (q.ld_jac % 4 == 0 && (reinterpret_cast<uintptr_t>(q.jac) & 15) == 0) ? 1 : 0};
+    const dqmc::JacOut<real> ko{q.rest, (long)k_n_rest, lp, sg, jac_accum ? 1 : 0, 0};
+    if (jac) jac_zero_rows(q.jac, q.ld_jac, B);
+    // Kfac: per-walker weights of the walker sums (cot, 0 for invalid walkers) and validity flags of the factors
+    double* kw = kfac ? reinterpret_cast<double*>(gw + o_kw) : nullptr;
+    if (kfac) {
+      dqmc::launch_kfac_weights<real>(st, lp, sg, q.cot, kw, B);
+      if (q.rest) kfac_zero_rest(q.rest, B);
+    }
+    // an op's per-walker parameter partials src[b * stride + m], m < n, of the weight entries w_off + m
+    auto emit_partials = [&](const auto* src, long stride, int n, long w_off) {
+      using T = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+      switch (q.mode) {
+        case Rev::Coords: return;
+        case Rev::Jac: dqmc::launch_jac_scatter<T, real>(st, src, stride, n, B, jo, w_off); return;
+        case Rev::Kfac:
+          if (q.rest) dqmc::launch_jac_scatter<T, real>(st, src, stride, n, B, ko, k_rest_pos[w_off]);
+          [[fallthrough]];
+        case Rev::Vjp:
+          if constexpr (std::is_same_v<T, real>) dqmc::launch_colsum<real>(st, src, B, stride, n, q.grad + w_off, kw);
+          else dqmc::launch_colsum_f64(st, src, B, stride, n, q.grad + w_off, kw);
+      }
+    };
+    const int32_t* gt = (const int32_t*)g_tab.p;
+    double* dL = reinterpret_cast<double*>(gw + o_dl);
+    double* slot = coords ? reinterpret_cast<double*>(gw + o_slot) : nullptr;   // coordinate-difference adjoints (kernels_coords.inl)
+    for (size_t opi = ops.size(); opi-- > 0;) {
+      const dqmc_op& op = ops[opi];
+      const int32_t* i = op.i;
+      switch (op.kind) {
+        case DQMC_OP_FEAT_EN:      // leaves: no parameters; only the coordinate mode carries their adjoints on
+          if (coords)
+            dqmc::launch_feat_en_coords<real>(st, r, R, A(i[0]), bufs[i[0]].width, B, N, sys.n_nuc, sys.norm_eps, i[1],
+                                              slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+          break;
+        case DQMC_OP_FEAT_EE:
+          if (coords)
+            dqmc::launch_feat_ee_coords<real>(st, r, R, d_it + i[1], A(i[0]), i[2], B, N, sys.norm_eps, i[3],
+                                              slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+          break;
+        case DQMC_OP_LINEAR: {
+          // Z = X W + b with the forward kernel (no activation, no residual)
+          dqmc::LinArgs<real> f{};
+          f.cfg_bf = linear_bf; f.cfg_bkx = linear_bkx; f.cfg_f64_split = linear_f64_split;
+          f.n_pieces = i[0];
+          dqmc::LinBwdArgs<real> a{};
+          a.n_pieces = i[0];
+          int w_row = 0;
+          for (int p = 0; p < i[0]; ++p) {
+            const int sb = i[1 + 4 * p];
+            f.piece[p].src = bptr(sb);
+            f.piece[p].ld = bufs[sb].width; f.piece[p].rpw = bufs[sb].rows; f.piece[p].r0 = i[2 + 4 * p];
+            f.piece[p].K = pad4(i[3 + 4 * p]); f.piece[p].bcast = i[4 + 4 * p]; f.piece[p].w_row = w_row;
+            a.piece[p].X = bptr(sb); a.piece[p].dX = A(sb);
+            a.piece[p].ld = bufs[sb].width; a.piece[p].rpw = bufs[sb].rows; a.piece[p].r0 = i[2 + 4 * p];
+            a.piece[p].K = i[3 + 4 * p]; a.piece[p].bcast = i[4 + 4 * p]; a.piece[p].w_row = w_row;
+            w_row += pad4(i[3 + 4 * p]);
+          }
+          real* Z = reinterpret_cast<real*>(gw + o_z);
+          f.W = d_w + i[22]; f.ldw = pad4(i[21]); f.bias = i[23] >= 0 ? d_w + i[23] : nullptr;
+          f.dst = Z; f.ld_dst = f.ldw; f.rpw_dst = i[20]; f.r0_dst = 0; f.col0_dst = 0;
+          f.act = 0; f.nrows = i[20]; f.B = B; f.T = 1; f.TP = 1;
+          t_begin(coords ? "linear_dx" : jac ? "linear_jac" : "linear_bwd", (coords ? 4.0 : 6.0) * B * i[20] * (double)w_row * f.ldw);     // Z recompute, dX, dW
+          dqmc::launch_linear<real>(st, f);
+          a.W = f.W; a.ldw = f.ldw; a.nout = i[21]; a.nrows = i[20]; a.B = B; a.act = i[24];
+          a.Z = Z; a.dZ = reinterpret_cast<real*>(gw + o_dz); a.dZs = reinterpret_cast<real*>(gw + o_dzs);
+          a.dY = A(i[17]); a.ld_dst = bufs[i[17]].width; a.rpw_dst = bufs[i[17]].rows; a.r0_dst = i[18]; a.col0_dst = i[19];
+          if (i[25] >= 0) { a.dres = A(i[25]); a.ld_res = bufs[i[25]].width; a.rpw_res = bufs[i[25]].rows; a.r0_res = i[26]; }
+          a.res_scale = i[27] ? (real)0.70710678118654752440 : (real)1;
+          if (!coords && !jac) { a.dW = q.grad + i[22]; a.dbias = i[23] >= 0 ? q.grad + i[23] : nullptr; }   // else dX only
+          a.part = reinterpret_cast<double*>(gw + o_part);
+          a.wt = kw;
+          if (jac) dqmc::launch_linear_jac<real>(st, a, jo, i[22], i[23]);
+          else dqmc::launch_linear_bwd<real>(st, a);
+          if (kfac) {
+            double* fA = q.factors + k_fac_off[opi];
+            dqmc::launch_kfac_factors<real>(st, a, i[23] >= 0, kw + B, fA, fA + kfac_dim_a(op) * kfac_dim_a(op),
+                                            reinterpret_cast<double*>(gw + o_kpart));
+          }
+          t_end();
+          break;
+        }
+        case DQMC_OP_SPIN_MEAN:
+          dqmc::launch_spin_mean_bwd<real>(st, A(i[0]), A(i[1]), B, N, i[2], bufs[i[0]].width);
+          break;
+        case DQMC_OP_ROW_SUM:
+          dqmc::launch_row_sum_bwd<real>(st, A(i[0]), A(i[1]), B, bufs[i[0]].rows, bufs[i[0]].width);
+          break;
+        case DQMC_OP_CONV: {
+          const int* t = &g_tab_of[4 * opi];
+          dqmc::launch_edge_rows_bwd<real>(st, A(i[0]), bufs[i[0]].rows, bufs[i[0]].width, bptr(i[1]), bufs[i[1]].rows, bufs[i[1]].width,
+                                           A(i[2]), bufs[i[2]].width, i[3], gt + t[0], t[1], i[6], B, N, 1.0);
+          dqmc::launch_conv_send_bwd<real>(st, A(i[1]), bufs[i[1]].rows, bufs[i[1]].width, bptr(i[0]), bufs[i[0]].rows, bufs[i[0]].width,
+                                           A(i[2]), bufs[i[2]].width, i[3], gt + t[2], t[3], i[6], B, N);
+          break;
+        }
+        case DQMC_OP_EDGE_SUM: {
+          const int* t = &g_tab_of[4 * opi];
+          dqmc::launch_edge_rows_bwd<real>(st, A(i[0]), bufs[i[0]].rows, bufs[i[0]].width, nullptr, 1, 4, A(i[2]), bufs[i[2]].width, i[3],
+                                           gt + t[0], t[1], i[6], B, N, 1.0 / (double)(i[1] > 0 ? i[1] : 1));
+          break;
+        }
+        case DQMC_OP_CONST:
+          emit_partials((const real*)A(i[0]), (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width, i[1]);
+          break;
+        case DQMC_OP_ORBITALS: {
+          const int n_env = i[6] > 0 ? i[6] : 1, KN = sys.n_det * N, L = sys.n_nuc * n_env;
+          double* pw = reinterpret_cast<double*>(gw + o_orb);
+          t_begin("orbitals_bwd", 0);
+          dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[0]), A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
+                                          d_w + i[4], d_w + i[5], coords ? nullptr : pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det,
+                                          sys.norm_eps);
+          if (coords)
+            dqmc::launch_orbitals_coords<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
+                                               d_w + i[4], d_w + i[5], B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps,
+                                               slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+          for (int t = 0; t < 4; ++t) emit_partials((const double*)pw + (size_t)t * KN * L, 4L * KN * L, KN * L, i[2 + t]);
+          t_end();
+          break;
+        }
+        case DQMC_OP_SLOGDET:
+          t_begin("slogdet_bwd", 0);
+          dqmc::launch_slogdet_bwd<real>(st, bptr(i[0]), bufs[i[0]].width, dL, A(i[0]), B, sys.n_det, N);
+          t_end();
+          break;
+        case DQMC_OP_FINAL: {
+          dqmc::FinalBwdArgs<real> a{};
+          a.r = r;
+          a.logdet = reinterpret_cast<double*>(d_ws + off_logdet);
+          a.sign_k = reinterpret_cast<int32_t*>(d_ws + off_signk);
+          a.cc = i[1] >= 0 ? d_w + i[1] : nullptr;
+          a.alphas = d_w + i[3];
+          a.cusp_kind = i[2]; a.same_scale = op.f[0]; a.anti_scale = op.f[1]; a.eps = sys.norm_eps;
+          a.logpsi = lp; a.sign = sg;
+          a.cot = q.mode == Rev::Vjp ? q.cot : nullptr;      // every other mode runs a unit cotangent
+          a.djas = i[0] >= 0 ? A(i[0]) : nullptr;
+          a.jas_ld = i[0] >= 0 ? bufs[i[0]].rows * bufs[i[0]].width : 0;
+          a.dL = dL;
+          a.pw = reinterpret_cast<double*>(gw + o_pw);
+          a.B = B; a.N = N; a.n_up = sys.n_up; a.K = sys.n_det;
+          dqmc::launch_final_bwd<real>(st, a);
+          if (coords && i[2])
+            dqmc::launch_cusp_coords<real>(st, r, d_w + i[3], i[2], op.f[0], op.f[1], sys.norm_eps, B, N, sys.n_up,
+                                           slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+          if (i[1] >= 0) emit_partials((const double*)a.pw, sys.n_det + 2, sys.n_det, i[1]);
+          emit_partials((const double*)a.pw + sys.n_det, sys.n_det + 2, 2, i[3]);
+          break;
+        }
+        default:
+          return fail(DQMC_E_UNSUPPORTED, std::string(rev_name(q.mode)) + ": op kind " + std::to_string(op.kind));
+      }
+    }
+    if (coords)
+      dqmc::launch_coords_gather<real>(st, slot, c_n_slots, (const int32_t*)c_tab.p, c_S, lp, sg, B, N, sys.n_nuc, q.grad_r, q.grad_R);
+    HIP_TRY(hipGetLastError());
+    return DQMC_OK;
+  }
