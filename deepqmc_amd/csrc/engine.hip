@@ -6,7 +6,7 @@
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
 // float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
-// engine_coords.inl, with the force estimators) -- and
+// engine_coords.inl, with the force estimators), SCF-orbital pretraining (engine_pretrain.inl) -- and
 // are included inside the struct body: one translation unit, as before.
 #include <hip/hip_runtime.h>
 
@@ -69,6 +69,13 @@ struct dqmc_ctx {
                        double energy, double* force) = 0;
   virtual int log_psi_kfac(const void* r, const void* R, int B, const void* cot, double* grad, double* factors, void* rest,
                            void* logpsi, int32_t* sign) = 0;
+  virtual int set_pretrain_target(int n_shells, const int32_t* atom, const int32_t* l, const int32_t* n_prim, const double* coeffs,
+                                  const double* zetas, int n_ao, int n_mo, const double* mo_coeffs, int n_conf, const int32_t* confs,
+                                  const double* conf_coeffs) = 0;
+  virtual int pretrain_target(const void* r, const void* R, int B, void* target) = 0;
+  virtual int orbitals(const void* r, const void* R, int B, void* orb) = 0;
+  virtual int orbitals_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* orb) = 0;
+  virtual int pretrain_loss_grad(const void* r, const void* R, int B, double n_total, double* grad, double* per_sample_loss) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -457,6 +464,7 @@ struct Engine : dqmc_ctx {
 #include "engine_jac.inl"
 #include "engine_kfac.inl"
 #include "engine_coords.inl"
+#include "engine_pretrain.inl"
 };
 
 }  // namespace
@@ -553,6 +561,35 @@ int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, in
   if (!ctx || !r || !R || !force) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->hf_force(estimator, r, R, B, grad_r, grad_R, e_loc, energy, force);
+}
+int dqmc_set_pretrain_target(dqmc_ctx* ctx, int n_shells, const int32_t* shell_atom, const int32_t* shell_l, const int32_t* shell_n_prim,
+                             const double* coeffs, const double* zetas, int n_ao, int n_mo, const double* mo_coeffs, int n_conf,
+                             const int32_t* confs, const double* conf_coeffs) {
+  if (!ctx || !shell_atom || !shell_l || !shell_n_prim || !coeffs || !zetas || !mo_coeffs || !confs || !conf_coeffs)
+    return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->set_pretrain_target(n_shells, shell_atom, shell_l, shell_n_prim, coeffs, zetas, n_ao, n_mo, mo_coeffs, n_conf, confs,
+                                  conf_coeffs);
+}
+int dqmc_pretrain_target(dqmc_ctx* ctx, const void* r, const void* R, int B, void* target) {
+  if (!ctx || !r || !R || !target) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->pretrain_target(r, R, B, target);
+}
+int dqmc_orbitals(dqmc_ctx* ctx, const void* r, const void* R, int B, void* orb) {
+  if (!ctx || !r || !R || !orb) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->orbitals(r, R, B, orb);
+}
+int dqmc_orbitals_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, void* orb) {
+  if (!ctx || !r || !R || !cot || !grad) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->orbitals_vjp(r, R, B, cot, grad, orb);
+}
+int dqmc_pretrain_loss_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, double n_total, double* grad, double* per_sample_loss) {
+  if (!ctx || !r || !R || !grad || !per_sample_loss) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->pretrain_loss_grad(r, R, B, n_total, grad, per_sample_loss);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

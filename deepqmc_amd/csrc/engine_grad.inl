@@ -52,6 +52,15 @@
     return sizeof(double) * m;
   }
 
+  int grad_ws_reserve(size_t bytes) {      // the adjoint workspace holds at least `bytes`
+    if (bytes <= g_ws_bytes) return DQMC_OK;
+    if (g_ws.p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(g_ws.p)); g_ws.p = nullptr; g_ws_bytes = 0; }
+    const hipError_t e = hipMalloc(&g_ws.p, bytes);
+    if (e != hipSuccess) return fail(DQMC_E_NOMEM, "gradient workspace of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    g_ws_bytes = bytes;
+    return DQMC_OK;
+  }
+
   // receiver / sender gather tables of the CONV and EDGE_SUM ops (the transposes of their (edge row, sender) lists)
   int grad_tables() {
     if (g_tab_built) return DQMC_OK;

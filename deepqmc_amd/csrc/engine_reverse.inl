@@ -1,6 +1,7 @@
 // engine_reverse.inl -- member functions of Engine<real>, included INSIDE the struct body by engine.hip: the reverse pass of
-// log|psi| that dqmc_log_psi_vjp, dqmc_log_psi_jacobian, dqmc_log_psi_kfac and dqmc_log_psi_grad_coords share.  A request
-// (RevReq) names one of four modes and that mode's outputs; reverse_pass() checks it, sizes the walker chunks and runs
+// log|psi| that dqmc_log_psi_vjp, dqmc_log_psi_jacobian, dqmc_log_psi_kfac and dqmc_log_psi_grad_coords share, and of the
+// Slater matrices themselves (dqmc_orbitals_vjp, dqmc_pretrain_loss_grad).  A request
+// (RevReq) names one of five modes and that mode's outputs; reverse_pass() checks it, sizes the walker chunks and runs
 // grad_chunk() on each.
 //
 // Per walker chunk: the per-op value pass (TP = 1, no fused kernel, no chained MLPs, so that every activation buffer the
@@ -18,13 +19,17 @@
 //           (kernels_kfac.inl) add A_l and G_l; partials of the entries no LINEAR op owns go to `rest` (engine_kfac.inl).
 //   Coords  no parameter partials: LINEAR forms dX only, CONST is skipped, and the ops that read the coordinates carry their
 //           adjoints into r and R (engine_coords.inl).
+//   Orbs    as Vjp, but the cotangent enters at the ORBITALS destination buffer (given, or formed from the pretraining target
+//           by the loss kernel): SLOGDET, FINAL and every op from which no path leads to that buffer are skipped
+//           (engine_pretrain.inl: orb_tables), their gradient entries stay exact zeros.  No invalid-walker rule.
 
-  enum class Rev { Vjp, Jac, Kfac, Coords };
+  enum class Rev { Vjp, Jac, Kfac, Coords, Orbs };
   static const char* rev_name(Rev m) {
     switch (m) {
       case Rev::Vjp: return "log_psi_vjp";
       case Rev::Jac: return "log_psi_jacobian";
       case Rev::Kfac: return "log_psi_kfac";
+      case Rev::Orbs: return "orbitals_vjp";
       default: return "log_psi_grad_coords";
     }
   }
@@ -41,12 +46,17 @@
     real* rest = nullptr;        // Kfac: [B][n_rest] partials of the entries no LINEAR op owns, or nullptr
     real* grad_r = nullptr;      // Coords: [B][N][3], or nullptr
     real* grad_R = nullptr;      // Coords: [B][n_nuc][3], or nullptr
+    const real* cot_orb = nullptr;   // Orbs: [B][K][N][N] cotangent of the Slater matrices; nullptr: formed from the pretraining target
+    real* orb = nullptr;         // Orbs: [B][K][N][N] Slater matrices of the value pass, or nullptr
+    double* ps_loss = nullptr;   // Orbs without cot_orb: [B] per-walker pretraining loss
+    double n_total = 1;          // Orbs without cot_orb: walkers the means of the loss run over
     template <class T> static T* adv(T* p, size_t n) { return p ? p + n : nullptr; }
-    RevReq at(size_t b0, int N, int n_nuc, size_t n_rest) const {   // the same request for the chunk that starts at walker b0
+    RevReq at(size_t b0, int N, int n_nuc, size_t n_rest, size_t n_orb) const {   // the same request for the chunk that starts at walker b0
       RevReq c = *this;
       c.logpsi = adv(logpsi, b0); c.sign = adv(sign, b0); c.cot = adv(cot, b0);
       c.jac = adv(jac, b0 * ld_jac); c.rest = adv(rest, b0 * n_rest);
       c.grad_r = adv(grad_r, b0 * N * 3); c.grad_R = adv(grad_R, b0 * n_nuc * 3);
+      c.cot_orb = adv(cot_orb, b0 * n_orb); c.orb = adv(orb, b0 * n_orb); c.ps_loss = adv(ps_loss, b0);
       return c;
     }
   };
@@ -75,6 +85,7 @@
       case Rev::Vjp: case Rev::Jac: fixed = grad_part_bytes(); break;
       case Rev::Kfac: per += 2 * sizeof(double); fixed = grad_part_bytes() + kfac_part_bytes(); break;
       case Rev::Coords: per += sizeof(double) * 3 * (size_t)c_n_slots; break;
+      case Rev::Orbs: per += pt_target_bytes_per_walker(); fixed = grad_part_bytes(); break;
     }
     const long chunk = per ? (long)((ws_budget > fixed ? ws_budget - fixed : 0) / per) : B;
     return chunk < 1 ? 1 : chunk;
@@ -85,14 +96,15 @@
     const std::string name = rev_name(q.mode);
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
     if (has_attention()) return fail(DQMC_E_UNSUPPORTED, name + ": no reverse pass for ATTENTION ops");
-    if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 44 electrons");
+    if (q.mode != Rev::Orbs && N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 44 electrons");   // (Orbs forms no inverse)
     { const int rc = grad_tables(); if (rc) return rc; }
+    if (q.mode == Rev::Orbs) { const int rc = orb_tables(); if (rc) return rc; }
     const long chunk = rev_chunk_len(q.mode, B);
     last_chunks[0] = chunk >= B ? 1 : (int)((B + chunk - 1) / chunk);
     const UnfusedForward unfused(*this);
     for (int b0 = 0; b0 < B; b0 += (int)chunk) {
       const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
-      const int rc = grad_chunk(r + (size_t)b0 * N * 3, R, nb, q.at(b0, N, sys.n_nuc, k_n_rest));
+      const int rc = grad_chunk(r + (size_t)b0 * N * 3, R, nb, q.at(b0, N, sys.n_nuc, k_n_rest, (size_t)sys.n_det * N * N));
       if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
@@ -100,7 +112,7 @@
   }
 
   int grad_chunk(const real* r, const real* R, int B, const RevReq& q) {
-    const bool jac = q.mode == Rev::Jac, kfac = q.mode == Rev::Kfac, coords = q.mode == Rev::Coords;
+    const bool jac = q.mode == Rev::Jac, kfac = q.mode == Rev::Kfac, coords = q.mode == Rev::Coords, orbs = q.mode == Rev::Orbs;
     // adjoint workspace of this chunk
     std::vector<size_t> adj(bufs.size());
     size_t off = 0;
@@ -115,18 +127,29 @@
     const size_t o_part = bump(coords ? 0 : grad_part_bytes());
     const size_t o_kw = bump(kfac ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = bump(kfac ? kfac_part_bytes() : 0);
     const size_t o_slot = bump(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
-    if (off > g_ws_bytes) {
-      if (g_ws.p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(g_ws.p)); g_ws.p = nullptr; g_ws_bytes = 0; }
-      const hipError_t e = hipMalloc(&g_ws.p, off);
-      if (e != hipSuccess) return fail(DQMC_E_NOMEM, "gradient workspace of " + std::to_string(off) + " bytes: " + hipGetErrorString(e));
-      g_ws_bytes = off;
-    }
+    const size_t o_tgt = bump(orbs && !q.cot_orb ? (size_t)B * pt_target_bytes_per_walker() : 0);
+    { const int rc = grad_ws_reserve(off); if (rc) return rc; }
     char* gw = (char*)g_ws.p;
     auto A = [&](int b) { return reinterpret_cast<real*>(gw + adj[b]); };
     real* lp = q.logpsi ? q.logpsi : reinterpret_cast<real*>(gw + o_lp);
     int32_t* sg = q.sign ? q.sign : reinterpret_cast<int32_t*>(gw + o_sg);
     { const int rc = run_chunk(r, R, B, false, lp, sg, nullptr, nullptr, B, nullptr, 0); if (rc) return rc; }
     HIP_TRY(hipMemsetAsync(gw, 0, adj_end, st));
+    if (orbs) {      // the cotangent enters at the ORBITALS destination buffer
+      const int ob = ops[orb_op].i[1], NN = N * N;
+      const long rows = (long)B * sys.n_det;
+      if (q.orb) dqmc::launch_orbitals_copy<real>(st, bptr(ob), bufs[ob].width, q.orb, NN, NN, rows);
+      if (q.cot_orb) dqmc::launch_orbitals_copy<real>(st, q.cot_orb, NN, A(ob), bufs[ob].width, NN, rows);
+      else {
+        real* tgt = reinterpret_cast<real*>(gw + o_tgt);
+        t_begin("pretrain_target", 0);
+        pt_launch_target(r, R, B, tgt);
+        t_end();
+        t_begin("pretrain_loss", 0);
+        dqmc::launch_pretrain_loss<real>(st, bptr(ob), bufs[ob].width, tgt, A(ob), q.ps_loss, B, N, sys.n_up, sys.n_det, pt_n_conf, q.n_total);
+        t_end();
+      }
+    }
     // where per-walker partials go: rows of J (Jac), rows of rest (Kfac)
     const dqmc::JacOut<real> jo{q.jac, (long)q.ld_jac, lp, sg, jac_accum ? 1 : 0,
                                 (q.ld_jac % 4 == 0 && (reinterpret_cast<uintptr_t>(q.jac) & 15) == 0) ? 1 : 0};
@@ -147,7 +170,7 @@
         case Rev::Kfac:
           if (q.rest) dqmc::launch_jac_scatter<T, real>(st, src, stride, n, B, ko, k_rest_pos[w_off]);
           [[fallthrough]];
-        case Rev::Vjp:
+        case Rev::Vjp: case Rev::Orbs:
           if constexpr (std::is_same_v<T, real>) dqmc::launch_colsum<real>(st, src, B, stride, n, q.grad + w_off, kw);
           else dqmc::launch_colsum_f64(st, src, B, stride, n, q.grad + w_off, kw);
       }
@@ -158,6 +181,7 @@
     for (size_t opi = ops.size(); opi-- > 0;) {
       const dqmc_op& op = ops[opi];
       const int32_t* i = op.i;
+      if (orbs && !orb_live[opi]) continue;
       switch (op.kind) {
         case DQMC_OP_FEAT_EN:      // leaves: no parameters; only the coordinate mode carries their adjoints on
           if (coords)

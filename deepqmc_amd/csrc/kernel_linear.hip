@@ -1230,3 +1230,4 @@ template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 #include "kernels_jac.inl"
 #include "kernels_kfac.inl"
 #include "kernels_coords.inl"
+#include "kernels_pretrain.inl"

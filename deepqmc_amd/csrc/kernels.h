@@ -492,4 +492,22 @@ template <typename real>
 void launch_hf_force(hipStream_t st, int est, const real* r, const real* R, const double* Z, const real* gr, const real* gR,
                      const real* e_loc, double energy, int B, int N, int n_nuc, double* force);
 
+// ---- kernels_pretrain.inl (included by kernel_linear.hip): SCF-orbital pretraining (dqmc_pretrain_target, dqmc_orbitals_vjp, ...) ----
+constexpr int PT_AO_CAP = 4096;       // atomic-orbital values (electrons of one tile x n_ao) k_pretrain_target keeps in LDS
+constexpr int PT_SHELL_INTS = 5;      // per shell: atom, l, first primitive, primitives, first AO
+constexpr int PT_LMAX = 3;
+// target: real[B][n_conf][N][N]; shells int32 [n_shell][PT_SHELL_INTS], prims real [.][2] = (coeff x rnorm, zeta), mo real [n_ao][n_mo],
+// confs int32 [n_conf][N], fac real [n_conf][2] = (|c|^(1/N), sign c); n_ao <= PT_AO_CAP
+template <typename real>
+void launch_pretrain_target(hipStream_t st, const real* r, const real* R, const int32_t* shells, const real* prims, const real* mo,
+                            const int32_t* confs, const real* fac, real* target, int B, int N, int n_shell, int n_ao, int n_mo,
+                            int n_conf);
+// dst[row][e] = src[row][e], e < NN, for `rows` rows of leading dimensions dst_ld / src_ld
+template <typename real>
+void launch_orbitals_copy(hipStream_t st, const real* src, long src_ld, real* dst, long dst_ld, int NN, long rows);
+// loss[b] (double) and the cotangent dorb of the ORBITALS buffer orb (both [B][K][orb_w]) against the tiled, block-diagonal target
+template <typename real>
+void launch_pretrain_loss(hipStream_t st, const real* orb, int orb_w, const real* target, real* dorb, double* loss, int B, int N,
+                          int n_up, int K, int n_conf, double n_total);
+
 }  // namespace dqmc

@@ -265,6 +265,81 @@ class Engine:
                                            ptr(grad_r), ptr(grad_R), ptr(e_loc), float(energy), force.data_ptr()))
         return force
 
+    # ---- SCF-orbital pretraining: target, Slater matrices, their VJP, the fused loss step ----
+    def set_pretrain_target(self, shells, mo_coeffs, confs, conf_coeffs):
+        """Upload the (MC-)SCF target of this context (dqmc_set_pretrain_target).  shells: [(atom, (l, coeffs, zetas))] as
+        GTOBasis.from_pyscf emits them; mo_coeffs [n_ao, n_mo]; confs [n_conf, N] orbital indices (up first); conf_coeffs
+        [n_conf].  Malformed tables raise DqmcError (-1)."""
+        atom = np.ascontiguousarray([a for a, _ in shells], np.int32)
+        ls = np.ascontiguousarray([sh[0] for _, sh in shells], np.int32)
+        cs = [np.asarray(sh[1], np.float64).reshape(-1) for _, sh in shells]
+        zs = [np.asarray(sh[2], np.float64).reshape(-1) for _, sh in shells]
+        if any(c.size != z.size for c, z in zip(cs, zs)):
+            raise ValueError('every shell needs as many coefficients as exponents (one contraction per shell)')
+        npr = np.ascontiguousarray([c.size for c in cs], np.int32)
+        coeffs, zetas = np.ascontiguousarray(np.concatenate(cs)), np.ascontiguousarray(np.concatenate(zs))
+        mo = np.ascontiguousarray(mo_coeffs, np.float64)
+        confs = np.ascontiguousarray(confs, np.int32)
+        cc = np.ascontiguousarray(conf_coeffs, np.float64).reshape(-1)
+        if mo.ndim != 2 or confs.ndim != 2 or confs.shape[1] != self.N or cc.size != confs.shape[0]:
+            raise ValueError(f'expected mo_coeffs [n_ao, n_mo], confs [n_conf, {self.N}], conf_coeffs [n_conf]')
+        pi = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        pd = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        self._check(self.lib.dqmc_set_pretrain_target(self._ctx, len(shells), pi(atom), pi(ls), pi(npr), pd(coeffs), pd(zetas),
+                                                      mo.shape[0], mo.shape[1], pd(mo), confs.shape[0], pi(confs), pd(cc)))
+        self.pretrain_n_conf = confs.shape[0]
+
+    def _orb_check(self, r):
+        if not getattr(self.spec, 'full_determinant', True):
+            raise DqmcError('only full-determinant programs expose their orbital matrices')
+        r = self._t(r)
+        assert r.shape[1:] == (self.N, 3)
+        return r, r.shape[0]
+
+    def pretrain_target(self, r, R=None):
+        """The target Slater matrices [B, n_conf, N, N] (rows electrons, columns orbitals) of the uploaded table
+        (dqmc_pretrain_target), on the device in the engine's dtype."""
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+        if getattr(self, 'pretrain_n_conf', None) is None:
+            raise DqmcError('pretrain_target: no target set (Engine.set_pretrain_target)')
+        out = torch.empty(B, self.pretrain_n_conf, self.N, self.N, dtype=self.dtype, device=self.device)
+        self._check(self.lib.dqmc_pretrain_target(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, out.data_ptr()))
+        return out
+
+    def orbitals(self, r, R=None):
+        """The Slater matrices [B, K, N, N] of the value pass (dqmc_orbitals), on the device in the engine's dtype."""
+        r, B = self._orb_check(r)
+        out = torch.empty(B, self.spec.n_determinants, self.N, self.N, dtype=self.dtype, device=self.device)
+        self._check(self.lib.dqmc_orbitals(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, out.data_ptr()))
+        return out
+
+    def orbitals_vjp(self, r, cot, R=None, want_orbitals=True):
+        """sum_{b,k,i,mu} cot[b,k,i,mu] d A[b,k,i,mu] / d w over the flat weight buffer (dqmc_orbitals_vjp).  cot: [B, K, N, N].
+        Returns (orbitals [B, K, N, N] or None, grad_flat float64 [n_weights]); map grad_flat onto the parameter tree with
+        `self.program.unflatten_grad`.  Programs with attention ops raise DqmcError (-4)."""
+        r, B = self._orb_check(r)
+        shape = (B, self.spec.n_determinants, self.N, self.N)
+        c = self._t(cot)
+        if tuple(c.shape) != shape:
+            raise DqmcError(f"'cot' must have shape {shape}, got {tuple(c.shape)}")
+        orb = torch.empty(shape, dtype=self.dtype, device=self.device) if want_orbitals else None
+        grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_orbitals_vjp(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, c.data_ptr(), grad.data_ptr(),
+                                               orb.data_ptr() if orb is not None else None))
+        return orb, grad
+
+    def pretrain_loss_grad(self, r, R=None, n_total=None):
+        """The fused pretraining step (dqmc_pretrain_loss_grad): returns (per_sample_loss float64 [B], grad_flat float64
+        [n_weights]) with grad_flat = d (sum_b per_sample_loss[b] / n_total) / d w; n_total defaults to B."""
+        r, B = self._orb_check(r)
+        ps = torch.empty(B, dtype=torch.float64, device=self.device)
+        grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_pretrain_loss_grad(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B,
+                                                     float(B if n_total is None else n_total), grad.data_ptr(), ps.data_ptr()))
+        return ps, grad
+
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None):
         """`rng` (an int seed or None) keys the random quadrature rotation of the non-local ECP term

@@ -127,6 +127,34 @@ class NeuralNetworkWaveFunction:
 
     __call__ = apply
 
+    def _orbital_engine(self, name, params, phys_conf):
+        if not self.spec.full_determinant:
+            raise NotImplementedError(f'{name}: only full-determinant programs expose their orbital matrices; spin-factorised '
+                                      'ones store block-diagonal matrices')
+        r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
+        R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
+        return self.engine(params, R), r, R
+
+    def orbitals(self, params, phys_conf):
+        """`apply(..., return_mos=True)` without the host copy: `(orb_up [B, K, n_up, N], orb_down [B, K, n_down, N])`, views of
+        one device tensor written by the value pass (Engine.orbitals)."""
+        eng, r, R = self._orbital_engine('orbitals', params, phys_conf)
+        A = eng.orbitals(r, R)
+        return A[:, :, :self.hamil.n_up], A[:, :, self.hamil.n_up:]
+
+    def orbitals_vjp(self, params, phys_conf, cotangent):
+        """jax.vjp of the batched `apply(..., return_mos=True)`: `cotangent` = `(cot_up [B, K, n_up, N], cot_down
+        [B, K, n_down, N])` or one [B, K, N, N] tensor; returns ((orb_up, orb_down), grad tree {module: {leaf: ndarray}}) with
+        grad = sum cot * d orbitals / d params.  Leaves no path leads from to the orbitals (the Jastrow factor, conf_coeff)
+        get exact zeros.  The same programs as log_psi_vjp are supported."""
+        eng, r, R = self._orbital_engine('orbitals_vjp', params, phys_conf)
+        if eng.program.grad_unsupported:
+            raise NotImplementedError(f'orbitals_vjp: unsupported for this program ({eng.program.grad_unsupported})')
+        if isinstance(cotangent, (tuple, list)):
+            cotangent = torch.cat([torch.as_tensor(c, dtype=self.dtype, device=self.device) for c in cotangent], dim=2)
+        A, g = eng.orbitals_vjp(r, cotangent, R)
+        return (A[:, :, :self.hamil.n_up], A[:, :, self.hamil.n_up:]), eng.program.unflatten_grad(g)
+
     def log_psi_vjp(self, params, phys_conf, cotangent=None):
         """jax.vjp of vmap(ansatz.apply)(params, r).log (loss/loss_function.py:59-75) with one cotangent per walker:
         returns (Psi(sign, log), grad tree {module: {leaf: ndarray}}) with grad = sum_b cotangent[b] d log|psi(r_b)| / d params.

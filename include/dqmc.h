@@ -252,6 +252,45 @@ enum dqmc_force_estimator {
 int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, int B, const void* grad_r, const void* grad_R,
                   const void* e_loc, double energy, double* force);
 
+/* ---- SCF-orbital pretraining (reference pretrain/pretraining.py, pretraining_target.py, gto.py) ----
+ * Slater matrices are real[B][K][N][N], K = n_det: rows electrons (up first), columns orbitals.
+ *
+ * dqmc_set_pretrain_target uploads the (MC-)SCF target once per context; every array is a host pointer.
+ *   shells: n_shells contracted Cartesian GTO shells, one contraction each: shell_atom (index of the nucleus it sits on),
+ *           shell_l (0 .. 3), shell_n_prim, and coeffs / zetas: the primitives of all shells, concatenated in shell order.
+ *           Shell s owns (l+1)(l+2)/2 atomic orbitals in the order (lx, ly, l - lx - ly), lx = l..0, ly = l-lx..0;
+ *           n_ao must equal their sum.
+ *   mo_coeffs: double[n_ao][n_mo];  confs: int32[n_conf][N] orbital indices < n_mo (the first n_up entries the up orbitals,
+ *           then the down ones);  conf_coeffs: double[n_conf].
+ *   A malformed table (l > 3, atom out of range, wrong n_ao, orbital index out of range) returns DQMC_E_ARG before any HIP call.
+ * dqmc_pretrain_target: target real[B][n_conf][N][N] on the device,
+ *   phi = anorm x^lx y^ly z^lz sum_p coeff_p rnorm_p exp(-|zeta_p d^2|), d = r_i - R_atom (the R of this call; plain squared
+ *   distance), anorm = 1 / sqrt(prod (2 l_i - 1)!!), rnorm_p = (2 zeta_p / pi)^(3/4) (4 zeta_p)^(l/2);
+ *   target[b][c][i][mu] = (phi(r_i) . mo_coeffs[:, confs[c][mu]]) |c_c|^(1/N) (sign(c_c) for mu = 0).
+ *   Arithmetic in the context's dtype.
+ * dqmc_orbitals: orb real[B][K][N][N], the Slater matrices of the value pass, run op by op per "ws_budget_mb" walker chunk.
+ *   DQMC_E_UNSUPPORTED unless the program stores full [N][N] matrices.
+ * dqmc_orbitals_vjp: grad (device double[n_weights], overwritten) = sum_{b,k,i,mu} cot[b][k][i][mu] d A[b][k][i][mu] / d w for
+ *   every entry w of the flat weight buffer (layout of dqmc_set_weights); cot real[B][K][N][N]; orb: optional output as
+ *   dqmc_orbitals.  The reverse pass of dqmc_log_psi_vjp with the cotangent entering at the Slater matrices: the
+ *   determinants, the CI sum and every op from which no path leads to the matrices (the Jastrow factor) are skipped and
+ *   their entries are exact zeros.  No walker is left out (orbitals are finite wherever the walker is).  Fixed-order
+ *   sums: identical calls are bit-identical, chunked and unchunked calls differ in the last bits.
+ *   DQMC_E_UNSUPPORTED for ATTENTION programs, as dqmc_log_psi_vjp; any number of electrons.
+ * dqmc_pretrain_loss_grad: value pass -> target -> loss and its cotangent -> reverse pass, all on the device:
+ *   per_sample_loss[b] (device double[B]) = mean_{k, i < n_up, mu} (A - T)^2 + mean_{k, i >= n_up, mu} (A - T)^2, with
+ *   T[k] = target configuration k mod n_conf, its [:n_up, :n_up] and [n_up:, n_up:] blocks, zeros elsewhere;
+ *   grad = d (sum_b per_sample_loss[b] / n_total) / d w.  n_total: the walker count the means of the caller's loss run
+ *   over.  The down term is omitted when n_down == 0.  DQMC_E_ARG before a target is set. */
+int dqmc_set_pretrain_target(dqmc_ctx* ctx, int n_shells, const int32_t* shell_atom, const int32_t* shell_l,
+                             const int32_t* shell_n_prim, const double* coeffs, const double* zetas, int n_ao, int n_mo,
+                             const double* mo_coeffs, int n_conf, const int32_t* confs, const double* conf_coeffs);
+int dqmc_pretrain_target(dqmc_ctx* ctx, const void* r, const void* R, int B, void* target);
+int dqmc_orbitals(dqmc_ctx* ctx, const void* r, const void* R, int B, void* orb);
+int dqmc_orbitals_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, void* orb);
+int dqmc_pretrain_loss_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, double n_total, double* grad,
+                            double* per_sample_loss);
+
 /* Gaussian-type effective core potential (reference ecp/gaussian_type_ecp.py:32-93 table layout,
  * :127-159 local part, :161-255 non-local part; replaces GaussianTypeECP.__init__'s pyscf lookup by
  * caller-supplied tables).  The `charges_host` given to dqmc_create must then be the valence charges
