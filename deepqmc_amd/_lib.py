@@ -22,6 +22,14 @@ SIGNATURES = [
     ('dqmc_destroy', None, [c_void_p]),
     ('dqmc_last_error', c_char_p, []),
     ('dqmc_set_weights', c_int, [c_void_p, POINTER(c_double), c_size_t]),
+    ('dqmc_set_param_map', c_int, [c_void_p, POINTER(c_int32), c_size_t, c_size_t]),
+    ('dqmc_weights_from_params', c_int, [c_void_p, c_void_p]),
+    ('dqmc_grad_to_params', c_int, [c_void_p, c_void_p, c_void_p]),
+    ('dqmc_adam_step', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_double, c_double, c_double, c_double,
+                               c_int64, c_void_p]),
+    ('dqmc_apply_update', c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
+    ('dqmc_debug_read_weights', c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    ('dqmc_graph_counters', c_int, [c_void_p, POINTER(c_int64)]),
     ('dqmc_wf_eval', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     ('dqmc_local_energy', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ('dqmc_psi_grad', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

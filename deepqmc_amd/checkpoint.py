@@ -87,9 +87,9 @@ class _Unpickler(pickle.Unpickler):
             raise pickle.UnpicklingError(f'refusing {module}.{name} in a checkpoint')
         if module in ('jax._src.array', 'jax.interpreters.xla', 'jaxlib.xla_extension') and name == '_reconstruct_array':
             return _reconstruct_array
-        if module == 'deepqmc.types' and name == 'TrainState':
+        if module in ('deepqmc.types', 'deepqmc_amd.checkpoint') and name == 'TrainState':      # (the reference's, and `save`'s own)
             return TrainState
-        if module == 'deepqmc.types' and name == 'Psi':
+        if module in ('deepqmc.types', 'deepqmc_amd.types') and name == 'Psi':
             return Psi
         if module == 'collections' and name in ('OrderedDict', 'defaultdict', 'deque'):
             return super().find_class(module, name)
@@ -113,6 +113,27 @@ def load(path_or_bytes) -> Tuple[int, TrainState]:
     if not isinstance(state, TrainState):
         state = TrainState(*state)
     return int(step), state
+
+
+def save(path, step: int, state: TrainState, ansatz=None):
+    """Write `(step, TrainState)` in the format `load` reads (log.py:114-128), NumPy leaves and device tensors as NumPy
+    arrays.  `ansatz`: the NeuralNetworkWaveFunction the parameter trees are cached under -- trees whose contexts were
+    stepped on the device (deepqmc_amd/optimizer.py) are synced first, so the file never holds stale leaves."""
+    if ansatz is not None:
+        ansatz.sync_params()
+
+    def host(x):
+        if hasattr(x, 'detach'):
+            return x.detach().cpu().numpy()
+        if isinstance(x, Psi):
+            return Psi(host(x.sign), host(x.log))
+        if isinstance(x, dict):
+            return type(x)((k, host(v)) for k, v in x.items())
+        if isinstance(x, (list, tuple)) and not hasattr(x, '_fields'):
+            return type(x)(host(v) for v in x)
+        return x
+    with open(path, 'wb') as f:
+        pickle.dump((int(step), TrainState(host(state.sampler), host(state.params), host(state.opt))), f)
 
 
 def _to_dict(tree):

@@ -6,7 +6,8 @@
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
 // float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
-// engine_coords.inl, with the force estimators), SCF-orbital pretraining (engine_pretrain.inl) -- and
+// engine_coords.inl, with the force estimators), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
+// step (engine_optim.inl) -- and
 // are included inside the struct body: one translation unit, as before.
 #include <hip/hip_runtime.h>
 
@@ -76,6 +77,15 @@ struct dqmc_ctx {
   virtual int orbitals(const void* r, const void* R, int B, void* orb) = 0;
   virtual int orbitals_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* orb) = 0;
   virtual int pretrain_loss_grad(const void* r, const void* R, int B, double n_total, double* grad, double* per_sample_loss) = 0;
+  virtual int set_param_map(const int32_t* src, size_t n, size_t n_params) = 0;
+  virtual int weights_from_params(const double* theta) = 0;
+  virtual int load_weights_device(const double* w64) = 0;
+  virtual int grad_to_params(const double* grad_w, double* grad_theta) = 0;
+  virtual int adam_step(double* theta, double* mu, double* nu, const double* g, size_t n, double lr, double b1, double b2, double eps,
+                        int64_t t, double* norms3) = 0;
+  virtual int apply_update(double* theta, const double* delta, double scale, double* norms3) = 0;
+  virtual int debug_read_weights(int which, void* out, size_t bytes) = 0;
+  virtual void graph_counters(int64_t* out2) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -417,6 +427,7 @@ struct Engine : dqmc_ctx {
     if (d_wpk_off) (void)hipFree(d_wpk_off);
     if (d_wpk) (void)hipFree(d_wpk);
     if (d_tape) (void)hipFree(d_tape);
+    free_optim();
   }
 
   int init(const dqmc_system* s, const double* charges, const dqmc_buf* b, int nb, const dqmc_op* o, int no,
@@ -465,6 +476,7 @@ struct Engine : dqmc_ctx {
 #include "engine_kfac.inl"
 #include "engine_coords.inl"
 #include "engine_pretrain.inl"
+#include "engine_optim.inl"
 };
 
 }  // namespace
@@ -590,6 +602,42 @@ int dqmc_pretrain_loss_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, 
   if (!ctx || !r || !R || !grad || !per_sample_loss) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->pretrain_loss_grad(r, R, B, n_total, grad, per_sample_loss);
+}
+int dqmc_set_param_map(dqmc_ctx* ctx, const int32_t* src_host, size_t n_weights, size_t n_params) {
+  if (!ctx || !src_host) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->set_param_map(src_host, n_weights, n_params);
+}
+int dqmc_weights_from_params(dqmc_ctx* ctx, const double* theta) {
+  if (!ctx || !theta) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->weights_from_params(theta);
+}
+int dqmc_grad_to_params(dqmc_ctx* ctx, const double* grad_w, double* grad_theta) {
+  if (!ctx || !grad_w || !grad_theta) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->grad_to_params(grad_w, grad_theta);
+}
+int dqmc_adam_step(dqmc_ctx* ctx, double* theta, double* mu, double* nu, const double* grad_theta, size_t n, double lr, double b1,
+                   double b2, double eps, int64_t t, double* norms3) {
+  if (!ctx || !theta || !mu || !nu || !grad_theta) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->adam_step(theta, mu, nu, grad_theta, n, lr, b1, b2, eps, t, norms3);
+}
+int dqmc_apply_update(dqmc_ctx* ctx, double* theta, const double* delta, double scale, double* norms3) {
+  if (!ctx || !theta || !delta) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->apply_update(theta, delta, scale, norms3);
+}
+int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t bytes) {
+  if (!ctx) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->debug_read_weights(which, out_host, bytes);
+}
+int dqmc_graph_counters(dqmc_ctx* ctx, int64_t* out2) {
+  if (!ctx || !out2) return fail(DQMC_E_ARG, "null argument");
+  ctx->graph_counters(out2);
+  return DQMC_OK;
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

@@ -463,9 +463,13 @@
   // Fragment-major copy of the Linear weights: [k/4][column block][lane] so that one wave load
   // of 64 consecutive elements is exactly the MFMA B operand (B[k = l>>4][col = l&15]).
   // Per scheduled op two words go to the device: packed-weight offset and "barrier after".
-  int pack_fused_weights() {
-    std::vector<int32_t> words(2 * (size_t)fused_n_ops, 0);
-    std::vector<real> pk;
+  // walk_fused_weights is the layout, once: it decides op_bf, fills `words` and calls, for every element of the packed
+  // buffer in order, plain(flat weight entry or -1) or bf(entry of the low half or -1, of the high half or -1, plane).
+  // pack_fused_weights turns the calls into values, fused_weight_sources (engine_optim.inl) into the table of the device re-pack.
+  template <typename Bf, typename Plain>
+  void walk_fused_weights(std::vector<int32_t>& words, Bf&& bf, Plain&& plain) {
+    words.assign(2 * (size_t)fused_n_ops, 0);
+    size_t count = 0;
     op_bf.assign((size_t)fused_n_ops, 0);
     for (int j = 0; j < fused_n_ops && fused_bf && sizeof(real) == 4; ++j) {
       // a layer goes to the bf16 matrix pipe when every piece is whole octets wide and the chunks of 32 k
@@ -489,8 +493,8 @@
       const int ldw = pad4(i[21]), NCB = (ldw + 15) / 16;
       // quad-interleaved: [piece][quad of 4 k-steps][column block][lane][k-step in quad]; every
       // piece is zero padded to whole quads, so one 16-byte load per lane feeds 4 MFMA k-steps
-      words[2 * j] = (int32_t)pk.size();
-      const real* W = wtmp.data() + i[22];
+      words[2 * j] = (int32_t)count;
+      const long W = i[22];
       int row0 = 0;
       if (op_bf[j]) {
         // bf16 plane layout: [piece][chunk of 32 k][column block][plane][lane][4 words]; word jj of lane l holds
@@ -502,15 +506,13 @@
               for (int pl = 0; pl < 3; ++pl)
                 for (int l = 0; l < 64; ++l)
                   for (int jj = 0; jj < 4; ++jj) {
-                    uint32_t word = 0;
+                    long src[2];
                     for (int h = 0; h < 2; ++h) {
                       const int k = 32 * c + 8 * (l >> 4) + 2 * jj + h, col = cb * 16 + (l & 15);
-                      const float wv = (k < K && col < ldw) ? (float)W[(size_t)(row0 + k) * ldw + col] : 0.0f;
-                      word |= (uint32_t)bf16_piece(wv, pl) << (16 * h);
+                      src[h] = (k < K && col < ldw) ? W + (long)(row0 + k) * ldw + col : -1;
                     }
-                    real as_real;
-                    memcpy(&as_real, &word, 4);       // (float engines only: sizeof(real) == 4)
-                    pk.push_back(as_real);
+                    bf(src[0], src[1], pl);
+                    ++count;
                   }
           row0 += K;
         }
@@ -523,11 +525,28 @@
             for (int l = 0; l < 64; ++l)
               for (int jj = 0; jj < 4; ++jj) {
                 const int ks = q * 4 + jj, row = row0 + ks * 4 + (l >> 4), col = cb * 16 + (l & 15);
-                pk.push_back((ks < KS && col < ldw) ? W[(size_t)row * ldw + col] : (real)0);
+                plain((ks < KS && col < ldw) ? W + (long)row * ldw + col : -1);
+                ++count;
               }
         row0 += KS * 4;
       }
     }
+  }
+  int pack_fused_weights() {
+    std::vector<int32_t> words;
+    if (dev_ahead && d_pm_src) return repack_fused_on_device();      // (wtmp is stale after a device update: engine_optim.inl)
+    std::vector<real> pk;
+    walk_fused_weights(
+        words,
+        [&](long s0, long s1, int pl) {
+          const float v0 = s0 >= 0 ? (float)wtmp[s0] : 0.0f, v1 = s1 >= 0 ? (float)wtmp[s1] : 0.0f;
+          const uint32_t word = (uint32_t)bf16_piece(v0, pl) | (uint32_t)bf16_piece(v1, pl) << 16;
+          real as_real;
+          memcpy(&as_real, &word, 4);       // (float engines only: sizeof(real) == 4)
+          pk.push_back(as_real);
+        },
+        [&](long s) { pk.push_back(s >= 0 ? wtmp[s] : (real)0); });
+    wpk_len = pk.size();
     if (pk.size() > wpk_cap) {
       if (d_wpk) HIP_TRY(hipFree(d_wpk));
       HIP_TRY(hipMalloc((void**)&d_wpk, sizeof(real) * pk.size()));
@@ -536,5 +555,5 @@
     HIP_TRY(hipMemcpyAsync(d_wpk, pk.data(), sizeof(real) * pk.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_wpk_off, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return DQMC_OK;
+    return d_pm_src ? upload_fused_sources() : DQMC_OK;      // (a new plan moves the words: the table of the device re-pack follows it)
   }

@@ -257,6 +257,8 @@
   int set_weights(const double* w, size_t n) override {
     if (n != n_weights) return fail(DQMC_E_ARG, "weight buffer length differs from the one given at creation");
     ++graph_epoch;
+    dev_ahead = false;                       // (engine_optim.inl: the host copies below are the newest again)
+    if (d_w64) HIP_TRY(hipMemcpyAsync(d_w64, w, sizeof(double) * n, hipMemcpyHostToDevice, st));
     wtmp.resize(n);
     for (size_t k = 0; k < n; ++k) wtmp[k] = (real)w[k];
     if (sizeof(real) == 4) {

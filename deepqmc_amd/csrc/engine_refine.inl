@@ -19,7 +19,7 @@
     t->ws_budget = twin_full_budget ? ws_budget : ws_budget / 2;
     t->timing = timing;
     twin = t;
-    return DQMC_OK;
+    return seed_twin_from_device();      // (after device updates w64_h is stale: engine_optim.inl)
   }
   // float64 results of the n walkers listed in d_flag[1..n] replace the float32 ones.  d_count != nullptr: the list is
   // holds fewer than n entries -- the count is read on the device, n is the (padded) size of this pass (kernels_mcmc.hip:

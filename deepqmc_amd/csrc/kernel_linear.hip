@@ -1231,3 +1231,4 @@ template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 #include "kernels_kfac.inl"
 #include "kernels_coords.inl"
 #include "kernels_pretrain.inl"
+#include "kernels_optim.inl"

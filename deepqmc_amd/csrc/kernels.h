@@ -510,4 +510,29 @@ template <typename real>
 void launch_pretrain_loss(hipStream_t st, const real* orb, int orb_w, const real* target, real* dorb, double* loss, int B, int N,
                           int n_up, int K, int n_conf, double n_total);
 
+// ---- kernels_optim.inl (included by kernel_linear.hip): device-resident optimiser step (dqmc_weights_from_params, dqmc_adam_step, ...) ----
+// One destination word of a packed weight buffer (the tape of a generated sub-step kernel, the planes of the fused kernel) as
+// a function of the flat weights w: plane < 0: the word is w[src0] * scale in `real` (src0 < 0: zero); plane 0..2: a 32-bit
+// word of two bf16 numbers, piece `plane` of the three-way split of (float)w[src0] * scale (low half) and of w[src1] (high).
+// The tables are written by the host packers themselves (spec_registry.hip: spec_tape_sources, engine_fused_plan.inl).
+struct PackSrc { int32_t src0, src1; float scale; int32_t plane; };
+constexpr int OPT_BLOCK = 256;        // threads per workgroup of the optimiser kernels
+constexpr int OPT_MAX_BLOCKS = 1024;  // workgroups of an optimiser launch at most = partial sums of a norm
+// w[j] = (real)theta[src[j]] and w64[j] = theta[src[j]] (w64 may be nullptr) where src[j] >= 0; other entries are left alone
+template <typename real>
+void launch_weights_from_params(hipStream_t st, const double* theta, const int32_t* src, real* w, double* w64, long n);
+// out[q] (real, or 32-bit words for real = float) per tab[q] from the flat weights w, n words
+template <typename real>
+void launch_pack_words(hipStream_t st, const PackSrc* tab, const real* w, real* out, long n);
+template <> void launch_pack_words<float>(hipStream_t st, const PackSrc* tab, const float* w, float* out, long n);
+template <> void launch_pack_words<double>(hipStream_t st, const PackSrc* tab, const double* w, double* out, long n);
+// grad_theta[e] = sum of grad_w[col[k]], k in [row[e], row[e + 1]), in that order
+void launch_grad_to_params(hipStream_t st, const double* grad_w, const int32_t* row, const int32_t* col, double* grad_theta, long n_params);
+// optax.adam with bias corrections c1 = 1 - b1^t, c2 = 1 - b2^t, in place on theta, mu, nu.  part: double[3][OPT_MAX_BLOCKS]
+// scratch and norms3: double[3] = 2-norms of theta (before the step), g and the update, or both nullptr.
+void launch_adam(hipStream_t st, double* theta, double* mu, double* nu, const double* g, long n, double lr, double b1, double b2,
+                 double eps, double c1, double c2, double* part, double* norms3);
+// theta += scale * delta; norms3 = 2-norms of theta (before), delta and scale * delta
+void launch_apply_update(hipStream_t st, double* theta, const double* delta, double scale, long n, double* part, double* norms3);
+
 }  // namespace dqmc

@@ -186,5 +186,8 @@ struct SpecKernel {
 // (spec_registry.hip; every csrc/gen/*.hip defines spec_kernel_<name>())
 const SpecKernel* find_spec_kernel(uint64_t hash);
 void spec_pack_tape(const SpecKernel& k, const float* w, uint32_t* tape);
+// the same walk over the tape entries, recording where every word comes from instead of its value (kernels.h: PackSrc;
+// engine_optim.inl: the device re-pack of dqmc_weights_from_params).  out [tape_bytes / 4].
+void spec_tape_sources(const SpecKernel& k, PackSrc* out);
 
 }  // namespace dqmc

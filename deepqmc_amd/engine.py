@@ -61,12 +61,14 @@ class Engine:
         self._compile = compiler if compiler is not None else (       # workspace -- to the cyclic collector instead of the reference count)
             lambda p_: compile_program(spec, p_, hamil.n_up, hamil.n_down, hamil.n_nuc, R=R0_, eps=eps_))
         self.program: Program = self._compile(params)
+        self._theta_ref = None         # the device vector of the last device update (params_flat)
+        self.params_ahead = False      # set by a device update: the context's weights are newer than the tree it is cached under
         self.N = hamil.n_up + hamil.n_down
         sysd = DqmcSystem(hamil.n_up, hamil.n_down, hamil.n_nuc, spec.n_determinants,
                           0 if dtype == torch.float32 else 1, 0, self.norm_eps, 0.0)
         p = self.program
         self._bufs, self._ops = p.c_bufs(), p.c_ops()
-        w = np.ascontiguousarray(p.weights, np.float64)
+        w = self._w_host = np.ascontiguousarray(p.weights, np.float64)      # (params_flat reads theta back from it)
         it = np.ascontiguousarray(p.itable if p.itable.size else np.zeros(1, np.int32), np.int32)
         ch = np.ascontiguousarray(hamil.ns_valence, np.float64)
         stream = 0
@@ -129,8 +131,104 @@ class Engine:
     def set_params(self, params):
         """New parameter tree after an optimiser step (same structure)."""
         prog = self._compile(params)
-        w = np.ascontiguousarray(prog.weights, np.float64)
+        w = self._w_host = np.ascontiguousarray(prog.weights, np.float64)
         self._check(self.lib.dqmc_set_weights(self._ctx, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), w.size))
+        self.params_ahead, self._theta_ref = False, None
+
+    # ---- device-resident parameters and optimiser step (dqmc_set_param_map ... dqmc_apply_update) ----
+    def _ensure_param_map(self):
+        """Upload Program.grad_src on first use (dqmc_set_param_map)."""
+        if not self.__dict__.get('_param_map_set', False):
+            prog = self.program
+            if prog.grad_unsupported:
+                raise NotImplementedError(f'device-resident parameters: unsupported for this program ({prog.grad_unsupported})')
+            src = np.ascontiguousarray(prog.grad_src, np.int32)
+            self._check(self.lib.dqmc_set_param_map(self._ctx, src.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), src.size,
+                                                    prog.n_params()))
+            self._param_map_set = True
+
+    def _theta_arg(self, name, t, n=None):
+        n = self.program.n_params() if n is None else n
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device.type != self.device.type \
+                or t.dim() != 1 or t.shape[0] != n:
+            raise DqmcError(f"'{name}' must be a contiguous 1-d float64 tensor of length {n} on {self.device}")
+        return t
+
+    def params_flat(self, params=None):
+        """The context's current parameters as a float64 device vector in Program.grad_leaves order: the theta of
+        set_params_flat / adam_step / apply_update.  After a device update: a copy of the vector that update used; before
+        one: read back from the weights of the last host upload (every parameter element is copied into the weight buffer
+        verbatim); with `params`: that tree, flattened.  The returned vector is the caller's."""
+        if params is not None:
+            return torch.as_tensor(self.program.flatten_params(params), dtype=torch.float64, device=self.device).contiguous()
+        if self._theta_ref is not None:
+            return self._theta_ref.clone()
+        prog = self.program
+        if prog.grad_unsupported:
+            raise NotImplementedError(f'params_flat: unsupported for this program ({prog.grad_unsupported})')
+        m = prog.grad_src >= 0
+        theta = np.zeros(prog.n_params(), np.float64)
+        theta[prog.grad_src[m]] = self._w_host[m]
+        return torch.as_tensor(theta, dtype=torch.float64, device=self.device).contiguous()
+
+    def set_params_flat(self, theta):
+        """New parameter values from a float64 device vector (dqmc_weights_from_params): weights, twin, tape and fused planes
+        are rewritten on the device, nothing goes through the host and captured graphs stay valid."""
+        self._ensure_param_map()
+        self._check(self.lib.dqmc_weights_from_params(self._ctx, self._theta_arg('theta', theta).data_ptr()))
+        self.params_ahead, self._theta_ref = True, theta
+
+    def grad_to_params(self, g):
+        """Flat gradient over the weight buffer (log_psi_vjp) -> float64 [n_params] device vector: unflatten_grad flattened in
+        leaf order, without leaving the device (dqmc_grad_to_params)."""
+        self._ensure_param_map()
+        g = self._theta_arg('g', g, self.program.weights.size)
+        out = torch.empty(self.program.n_params(), dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_grad_to_params(self._ctx, g.data_ptr(), out.data_ptr()))
+        return out
+
+    def adam_step(self, theta, mu, nu, grad_theta, *, lr, b1=0.9, b2=0.999, eps=1e-8, t=1, norms=None):
+        """One optax.adam step in place on the device vectors theta, mu, nu, then the re-pack (dqmc_adam_step).  t: 1-based count.
+        norms: optional float64 [3] device tensor receiving (param, grad, update) 2-norms."""
+        self._ensure_param_map()
+        n = self.program.n_params()
+        for name, x in (('theta', theta), ('mu', mu), ('nu', nu), ('grad_theta', grad_theta)):
+            self._theta_arg(name, x)
+        if norms is not None:
+            self._theta_arg('norms', norms, 3)
+        self._check(self.lib.dqmc_adam_step(self._ctx, theta.data_ptr(), mu.data_ptr(), nu.data_ptr(), grad_theta.data_ptr(), n,
+                                            float(lr), float(b1), float(b2), float(eps), int(t),
+                                            norms.data_ptr() if norms is not None else None))
+        self.params_ahead, self._theta_ref = True, theta
+
+    def apply_update(self, theta, delta, scale=1.0, norms=None):
+        """theta += scale * delta on the device, then the re-pack (dqmc_apply_update)."""
+        self._ensure_param_map()
+        self._theta_arg('theta', theta)
+        self._theta_arg('delta', delta)
+        if norms is not None:
+            self._theta_arg('norms', norms, 3)
+        self._check(self.lib.dqmc_apply_update(self._ctx, theta.data_ptr(), delta.data_ptr(), float(scale),
+                                               norms.data_ptr() if norms is not None else None))
+        self.params_ahead, self._theta_ref = True, theta
+
+    def debug_read_weights(self, which: int):
+        """Raw bytes (np.uint8) of a weight buffer of the context (dqmc_debug_read_weights): 0 flat weights, 1 the sub-step
+        kernel's tape, 2 the fused kernel's planes, 3 the float64 twin's flat weights.  None if the context has no such buffer."""
+        n = self.lib.dqmc_debug_read_weights(self._ctx, int(which), None, 0)
+        if n == -4:         # DQMC_E_UNSUPPORTED
+            return None
+        if n < 0:
+            self._check(n)
+        out = np.empty(n, np.uint8)
+        self._check(self.lib.dqmc_debug_read_weights(self._ctx, int(which), out.ctypes.data_as(ctypes.c_void_p), out.size))
+        return out
+
+    def graph_counters(self) -> dict:
+        """{captures, replays} of the context's forward-Laplacian graphs (dqmc_graph_counters)."""
+        out = (ctypes.c_int64 * 2)()
+        self._check(self.lib.dqmc_graph_counters(self._ctx, out))
+        return {'captures': int(out[0]), 'replays': int(out[1])}
 
     # ---- ansatz.apply ---------------------------------------------------
     def wf_eval(self, r, R=None):
@@ -341,10 +439,12 @@ class Engine:
         return ps, grad
 
     # ---- hamil.local_energy ---------------------------------------------
-    def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None):
+    def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None, static_io=False):
         """`rng` (an int seed or None) keys the random quadrature rotation of the non-local ECP term
         (hamil.py:166, gaussian_type_ecp.py:221); `ecp_phi` [B, n_ecp_nl, N] overrides it with explicit
-        angles (parity tests).  Both are ignored without an ECP."""
+        angles (parity tests).  Both are ignored without an ECP.  `static_io`: the call reads the walkers from, and writes its
+        results to, buffers the engine keeps per batch size (copies in and out), so that a training loop presents the same
+        pointers at every step and the captured forward-Laplacian graph is replayed instead of re-captured."""
         if isinstance(phys_conf, PhysicalConfiguration):
             r, R = phys_conf.r, phys_conf.R
         else:
@@ -363,11 +463,27 @@ class Engine:
             seed = int(rng) & (2 ** 64 - 1) if isinstance(rng, (int, np.integer)) else 0
             self._check(self.lib.dqmc_ecp_rotation(self._ctx, seed,
                                                    self._ecp_phi.data_ptr() if self._ecp_phi is not None else None))
-        e = torch.empty(B, dtype=self.dtype, device=self.device)
-        st = torch.empty(6, B, dtype=self.dtype, device=self.device)
+        static_io = static_io and not return_grad
+        Rt = self._R(R)
+        if static_io:
+            bufs = self.__dict__.setdefault('_static_io', {})
+            if B not in bufs:
+                bufs[B] = (torch.empty(B, self.N, 3, dtype=self.dtype, device=self.device), torch.empty_like(Rt),
+                           torch.empty(B, dtype=self.dtype, device=self.device), torch.empty(6, B, dtype=self.dtype, device=self.device))
+            r_in, R_in, e, st = bufs[B]
+            r_in.copy_(r)
+            if Rt is not self.R:          # (a sampler stacks a new R tensor per step: same values, another pointer)
+                R_in.copy_(Rt)
+                Rt = R_in
+            r = r_in
+        else:
+            e = torch.empty(B, dtype=self.dtype, device=self.device)
+            st = torch.empty(6, B, dtype=self.dtype, device=self.device)
         grad = torch.empty(B, 3 * self.N, dtype=self.dtype, device=self.device) if return_grad else None
-        self._check(self.lib.dqmc_local_energy(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, e.data_ptr(),
+        self._check(self.lib.dqmc_local_energy(self._ctx, r.data_ptr(), Rt.data_ptr(), B, e.data_ptr(),
                                                st.data_ptr(), grad.data_ptr() if return_grad else None, None, None))
+        if static_io:
+            e, st = e.clone(), st.clone()
         stats = {k: st[i] for i, k in enumerate(STAT_KEYS)}
         return (e, stats, grad) if return_grad else (e, stats)
 

@@ -1,0 +1,65 @@
+"""The variational training loop (reference src/deepqmc/fit.py: `fit_wf` and its train step) on the device-resident
+optimiser step: sample, `opt.step`, merge the electronic states, refresh the sampler's psi -- per step no parameter crosses
+the host and the captured forward-Laplacian graphs of the contexts are replayed.  EWM energies and observable monitors of
+the reference's loop are not part of this one.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .checkpoint import TrainState
+from .optimizer import merge_states_flat
+
+__all__ = ['fit_wf', 'TrainState']
+
+
+def _host_mean(x):
+    """Sampler statistics arrive as nested lists over molecules / states of host floats."""
+    return float(np.mean(np.asarray(x, np.float64)))
+
+
+def fit_wf(rng, hamil, ansatz, opt, molecule_idx_sampler, sampler, steps, train_state, merge_keys, sync_every=None):
+    """fit.py:34-162 as a generator: one training step per element of `steps`, yielding
+    `(step, TrainState(sampler, params, opt), mol_idxs, stats)`.
+
+    `rng`: an integer seed (step k samples with rng * 1000003 + k, as pretrain does); `opt`: an optimiser of
+    deepqmc_amd/optimizer.py (bound to `hamil` / `ansatz` here if it is not yet); `sampler.sample(rng, smpl_state, params,
+    mol_idxs)` -> (smpl_state, phys_conf r[1, S, B, N, 3], stats) as MultiNuclearGeometrySampler over
+    MultiElectronicStateSampler gives it; `train_state`: TrainState(sampler state, [parameter tree per electronic state],
+    optimiser state or None).  `merge_keys`: module-name substrings whose parameters are averaged over the states after every
+    step.  stats: the sampler's statistics (host floats), 'hamil/*' and 'local_energy/{mean,std,min,max}' and 'opt/*' (device
+    tensors: reading them is the caller's synchronisation, the loop itself never waits for the device).
+
+    The yielded parameter trees are the objects of `train_state.params` throughout -- they key the context cache -- and
+    their leaves are brought up to date (NeuralNetworkWaveFunction.sync_params) every `sync_every` steps and when the
+    generator finishes or is closed; in between they are stale and `ansatz.params_stale(tree)` says so."""
+    if hasattr(opt, 'bind') and (getattr(opt, 'hamil', None) is None or getattr(opt, 'ansatz', None) is None):
+        opt.bind(hamil, ansatz)
+    smpl_state, params, opt_state = train_state
+    params = list(params)
+    merge_keys = tuple(merge_keys) if merge_keys is not None else None
+    if opt_state is None:
+        opt_state = opt.init(rng, params, None)
+    try:
+        for k, step in enumerate(steps):
+            seed = int(rng) * 1000003 + k
+            mol_idxs = molecule_idx_sampler.sample()
+            smpl_state, phys_conf, smpl_stats = sampler.sample(seed, smpl_state, params, mol_idxs)
+            params, opt_state, e_loc, _, stats = opt.step(seed, params, opt_state, (phys_conf, None, {}))
+            if getattr(opt, 'changes_params', True):
+                merge_states_flat(ansatz, params, opt_state, merge_keys, phys_conf)
+                if hasattr(sampler, 'update'):      # psi of the walkers under the new parameters (fit.py:90-92)
+                    smpl_state = sampler.update(smpl_state, params)
+            e64 = e_loc.double()
+            out = {k_: _host_mean(v) for k_, v in smpl_stats.items()}
+            out.update({k_ if '/' in k_ else f'hamil/{k_}': v for k_, v in stats.items()})
+            out.update({'local_energy/mean': e64.mean(dim=-1), 'local_energy/std': e64.std(dim=-1, unbiased=False),
+                        'local_energy/min': e64.amin(dim=-1), 'local_energy/max': e64.amax(dim=-1)})
+            if sync_every and (k + 1) % int(sync_every) == 0:
+                for p in params:
+                    ansatz.sync_params(p)
+            yield step, TrainState(smpl_state, params, opt_state), mol_idxs, out
+    finally:
+        for p in params:
+            ansatz.sync_params(p)

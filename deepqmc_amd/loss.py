@@ -41,9 +41,10 @@ def _unpack(phys_conf):
     return r, [R[m] for m in range(M)]
 
 
-def compute_local_energy(rng, hamil, ansatz, params: Sequence, phys_conf_r: torch.Tensor):
+def compute_local_energy(rng, hamil, ansatz, params: Sequence, phys_conf_r: torch.Tensor, static_io: bool = False):
     """loss/energy.py:19-60: returns (E_loc[M,S,B], stats{key: [M,S]} = per-(molecule,state)
-    means over the walkers, energy.py:59).  `params` = one parameter tree per state."""
+    means over the walkers, energy.py:59).  `params` = one parameter tree per state.  `static_io`: Engine.local_energy's
+    (training loops: the same device pointers at every step, so the captured pass is replayed)."""
     from .types import PhysicalConfiguration
     r, Rs = _unpack(phys_conf_r)
     M, S = r.shape[0], r.shape[1]
@@ -54,7 +55,7 @@ def compute_local_energy(rng, hamil, ansatz, params: Sequence, phys_conf_r: torc
         for s in range(S):
             rr = r[m, s].contiguous()
             pc = rr if Rs[m] is None else PhysicalConfiguration(Rs[m], rr, None)
-            e, st = ansatz.engine(params[s], Rs[m]).local_energy(pc, rng=rng)
+            e, st = ansatz.engine(params[s], Rs[m]).local_energy(pc, rng=rng, static_io=static_io)
             em.append(e)
             for k in STAT_KEYS:
                 sm[k].append(st[k].mean())
@@ -126,30 +127,40 @@ def median_clip_and_mask(x: torch.Tensor, clip_width: float = 5.0, median_center
     return torch.clamp(x, center - clip_width * mad, center + clip_width * mad), abs_diff < exclude_width
 
 
-def compute_energy_loss_and_grad(rng, hamil, ansatz, params: Sequence, phys_conf, weight=None, clip_mask_fn=median_clip_and_mask):
+def compute_energy_loss_and_grad(rng, hamil, ansatz, params: Sequence, phys_conf, weight=None, clip_mask_fn=median_clip_and_mask,
+                                 flat: bool = False):
     """The energy part of the reference's training step for a [1, S, B] batch: loss/loss_function.py:191-226 with
     compute_mean_energy / compute_mean_energy_tangent (loss/energy.py:63-102) and clip_local_energy (loss/clip.py:31-47).
     Per state s the loss gradient is one vector-Jacobian product of log|psi| (dqmc_log_psi_vjp),
         grad_s = sum_b c_sb d log|psi_s(r_sb)| / d theta_s,   c_sb = mask_sb w_sb (clip(E)_sb - mean_b(clip(E)_s w_s)) / sum_sb mask_sb,
     the mask count taken over all states and walkers, as the reference's masked_mean over [M, S, B].
     Returns (loss = mean(E_loc w) over [1, S, B], [grad tree per state], stats: the hamiltonian statistics of
-    compute_local_energy and 'E_loc' [1, S, B]).  The overlap and spin penalties are not included."""
+    compute_local_energy and 'E_loc' [1, S, B]).  The overlap and spin penalties are not included.
+    flat=True: the gradients are float64 device vectors in parameter order (Program.grad_leaves, Engine.grad_to_params)
+    instead of host trees -- what the device-resident optimisers (deepqmc_amd/optimizer.py) consume -- and nothing of the
+    call waits for the host."""
     r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_grad', rng, hamil, ansatz, params, phys_conf,
-                                                             weight, clip_mask_fn)
+                                                             weight, clip_mask_fn, static_io=flat)
     grads = []
     for s, cot in enumerate(cots):
         pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
+        if flat:
+            if eng.program.grad_unsupported:
+                raise NotImplementedError(f'compute_energy_loss_and_grad: unsupported for this program ({eng.program.grad_unsupported})')
+            _, _, g = eng.log_psi_vjp(r[0, s].contiguous(), cot.to(eng.dtype).to(eng.device).contiguous(), Rs[0])
+            grads.append(eng.grad_to_params(g))
+            continue
         _, grad = ansatz.log_psi_vjp(params[s], pc, cot.to(eng.dtype).to(eng.device).contiguous())
         grads.append(grad)
     return loss, grads, stats
 
 
-def _energy_loss_cotangents(name, rng, hamil, ansatz, params, phys_conf, weight, clip_mask_fn):
+def _energy_loss_cotangents(name, rng, hamil, ansatz, params, phys_conf, weight, clip_mask_fn, static_io=False):
     """-> (r, Rs, loss, [cotangent c_s [B] per state], [clip mask [B] per state], stats) of the energy loss on a [1, S, B] batch."""
     r, Rs = _unpack(phys_conf)
     if r.shape[0] != 1:
         raise ValueError(f'{name}: one molecule per batch ([1, S, B])')
-    e_loc, stats = compute_local_energy(rng, hamil, ansatz, params, phys_conf)
+    e_loc, stats = compute_local_energy(rng, hamil, ansatz, params, phys_conf, static_io=static_io)
     S, B = r.shape[1], r.shape[2]
     e64 = e_loc.double()
     w = torch.ones_like(e64) if weight is None else torch.as_tensor(weight, dtype=torch.float64, device=e64.device).reshape(e64.shape)
@@ -174,7 +185,7 @@ def _state_conf(ansatz, params_s, r, Rs, s):
 
 
 def compute_energy_loss_and_natgrad(rng, hamil, ansatz, params: Sequence, phys_conf, damping=1e-3, weight=None,
-                                    clip_mask_fn=median_clip_and_mask):
+                                    clip_mask_fn=median_clip_and_mask, flat: bool = False):
     """compute_energy_loss_and_grad preconditioned by the damped Fisher matrix of the per-walker log|psi| gradients (natural
     gradient / stochastic reconfiguration), in the MinSR form that needs only a B x B solve.  Per state s, with the per-walker
     rows O_b = d log|psi_s(r_sb)| / d theta_s (NeuralNetworkWaveFunction.log_psi_jacobian), the clip mask m_b, its count n_s over
@@ -185,11 +196,12 @@ def compute_energy_loss_and_natgrad(rng, hamil, ansatz, params: Sequence, phys_c
     The Gram matrix A_s A_s^T is formed with torch.matmul in the Jacobian's dtype, its Cholesky solve runs in float64, and one
     step of iterative refinement removes the cancellation of the Woodbury form at small damping.
     Returns (loss, [delta_s tree per state], stats): stats as compute_energy_loss_and_grad's, plus 'grad' = [g_s tree per state].
+    flat=True: delta_s and g_s are float64 device vectors in parameter order instead of host trees.
     Single process only: the Jacobians of other ranks are not gathered."""
     if not damping > 0:
         raise ValueError('damping must be positive')
     r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_natgrad', rng, hamil, ansatz, params, phys_conf,
-                                                             weight, clip_mask_fn)
+                                                             weight, clip_mask_fn, static_io=flat)
     deltas, gs = [], []
     for s, cot in enumerate(cots):
         pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
@@ -214,8 +226,8 @@ def compute_energy_loss_and_natgrad(rng, hamil, ansatz, params: Sequence, phys_c
         delta = solve(g)
         delta = delta + solve(g - AtV(Av(delta)) - damping * delta)      # one step of iterative refinement
         prog = eng.program
-        deltas.append(prog.unflatten_params(delta))
-        gs.append(prog.unflatten_params(g))
+        deltas.append(delta.contiguous() if flat else prog.unflatten_params(delta))
+        gs.append(g.contiguous() if flat else prog.unflatten_params(g))
         del A, Jp
     stats['grad'] = gs
     return loss, deltas, stats

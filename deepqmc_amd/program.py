@@ -143,6 +143,19 @@ class Program:
             tree.setdefault(mod, {})[leaf] = v[sl].reshape(shape)
         return tree
 
+    def flatten_params(self, tree):
+        """The inverse of unflatten_params: a haiku tree {module: {leaf: array}} -> float64 [n_params] vector in grad_leaves
+        order (the theta of dqmc_weights_from_params).  Leaves the program does not read are ignored."""
+        if self.grad_unsupported:
+            raise NotImplementedError(f'flatten_params: unsupported for this program ({self.grad_unsupported})')
+        out = np.empty(self.n_params(), np.float64)
+        for (mod, leaf), (sl, shape) in self.leaf_slices().items():
+            v = np.asarray(tree[mod][leaf], np.float64)
+            if tuple(v.shape) != tuple(shape):
+                raise ValueError(f'leaf {mod}:{leaf} has shape {tuple(v.shape)}, the program was compiled for {tuple(shape)}')
+            out[sl] = v.reshape(-1)
+        return out
+
     def _jacobian_gather(self):
         """Per source multiplicity m, the flat weight entries that hold the m-th copy of each parameter element (ascending
         entry order, as np.add.at in unflatten_grad sums them) and the mask of elements that have one."""

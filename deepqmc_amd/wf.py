@@ -11,6 +11,11 @@ tree OBJECT: the cache holds a reference to the tree and matches it with `is`, s
 `id()` can never alias an engine holding other weights.  Pass a new tree object after an
 optimiser step and its weights are uploaded into the least recently used context; leaves
 mutated in place are not detected -- call `invalidate(params)` after doing that.
+
+A device-resident optimiser step (Engine.adam_step / apply_update / set_params_flat, deepqmc_amd/optimizer.py) changes a
+context's weights without touching the tree it is cached under: the engine is marked (`Engine.params_ahead`), and
+`sync_params(tree)` downloads the current values into the tree's leaves.  The cache does that by itself before it
+re-targets or drops such a context.
 """
 from __future__ import annotations
 
@@ -65,7 +70,8 @@ class NeuralNetworkWaveFunction:
                 return eng
         reuse = [k for k, (_, key, _) in enumerate(self._engines) if key == gkey]
         if len(self._engines) >= self.max_engines and reuse:
-            _, _, eng = self._engines.pop(reuse[0])
+            old_tree, _, eng = self._engines.pop(reuse[0])
+            self._sync_tree(old_tree, eng)      # (a context stepped on the device holds the only copy of its tree's current values)
             eng.set_params(params)
         else:
             if len(self._engines) >= self.max_engines:
@@ -73,7 +79,7 @@ class NeuralNetworkWaveFunction:
                 # when its LAST reference goes -- now, if the cache held the only one (Engine keeps no reference cycle:
                 # tests/test_facade_emu.py::test_engine_is_released_by_reference_count), otherwise when the caller that
                 # still holds it drops it.  Nothing is closed under a caller's feet.
-                self._engines.pop(0)
+                self._sync_tree(*self._engines.pop(0)[::2])
                 self._evictions += 1
                 if self._evictions == 4 * self.max_engines:
                     import warnings
@@ -91,6 +97,32 @@ class NeuralNetworkWaveFunction:
         an `Engine` obtained from `engine()` before this call raises a clear "engine closed" error afterwards."""
         while self._engines:
             self._engines.pop()[2].close()
+
+    @staticmethod
+    def _sync_tree(tree, eng):
+        if not eng.params_ahead:
+            return
+        theta = eng.params_flat().cpu().numpy()
+        import numpy as np
+        for (mod, leaf), (sl, shape) in eng.program.leaf_slices().items():
+            cur = tree[mod][leaf]
+            if isinstance(cur, np.ndarray) and cur.shape == tuple(shape) and cur.flags.writeable:
+                cur[...] = theta[sl].reshape(shape).astype(cur.dtype)
+            else:
+                tree[mod][leaf] = theta[sl].reshape(shape).copy()
+        eng.params_ahead = False
+
+    def sync_params(self, params=None):
+        """Bring the leaves of `params` (every cached tree if None) up to date with their context after device-resident
+        optimiser steps, in place: one device-to-host copy of the parameter vector per stale tree.  Returns `params`."""
+        for tree, _, eng in self._engines:
+            if params is None or tree is params:
+                self._sync_tree(tree, eng)
+        return params
+
+    def params_stale(self, params) -> bool:
+        """True if a cached context of `params` was stepped on the device since the tree's leaves were last written."""
+        return any(tree is params and eng.params_ahead for tree, _, eng in self._engines)
 
     def invalidate(self, params=None):
         """Re-upload the weights of `params` (all cached trees if None) after their leaves were changed in place."""

@@ -155,6 +155,43 @@ const char* dqmc_last_error(void);
 /* Replace the weight buffer (same length as at creation).  host double[]. */
 int dqmc_set_weights(dqmc_ctx* ctx, const double* weights_host, size_t n_weights);
 
+/* ---- Device-resident optimiser step ----
+ * The parameters live in a device vector theta (double[n_params], the order of Program.grad_leaves) that the caller owns.
+ * After dqmc_set_param_map, every call below only enqueues kernels on the context's stream: none synchronises it or touches
+ * host memory once its arguments are validated, and none invalidates a captured forward-Laplacian graph ("pass_graph") --
+ * a capture records pointers and shape-derived arguments, never weight values, and no buffer moves.  (dqmc_set_weights
+ * keeps dropping the graphs, as before.)  All pointers are device pointers unless marked host.
+ *
+ * dqmc_set_param_map: src_host int32[n_weights], the parameter element each flat weight entry (dqmc_set_weights layout) is a
+ * copy of, -1 for a constant or padding (Program.grad_src).  Builds the device tables of the re-packers; a setup call (it
+ * synchronises).  DQMC_E_ARG for n_weights other than the context's or an entry outside [-1, n_params). */
+int dqmc_set_param_map(dqmc_ctx* ctx, const int32_t* src_host, size_t n_weights, size_t n_params);
+/* w[j] = theta[src[j]] where src[j] >= 0; the other entries keep the value of creation / the last dqmc_set_weights.  From
+ * those doubles everything dqmc_set_weights refreshes is refreshed in place on the device -- the weights in the context's
+ * precision, the float64 twin's (a twin created later starts from the current values), the weight tape of a generated
+ * sub-step kernel, the packed planes of the fused kernel with their bf16 three-way split -- bit-identical to what
+ * dqmc_set_weights produces from the same doubles.  DQMC_E_ARG before a map is set. */
+int dqmc_weights_from_params(dqmc_ctx* ctx, const double* theta);
+/* The transpose of the packing: grad_theta[e] = sum over j with src[j] == e of grad_w[j] (double[n_weights], what
+ * dqmc_log_psi_vjp writes), in ascending j.  No atomics: identical calls give bit-identical results. */
+int dqmc_grad_to_params(dqmc_ctx* ctx, const double* grad_w, double* grad_theta);
+/* optax.adam over the flat vectors, in place: with t the 1-based count of this step,
+ *   mu = b1 mu + (1 - b1) g, nu = b2 nu + (1 - b2) g^2, theta += -lr (mu / (1 - b1^t)) / (sqrt(nu / (1 - b2^t)) + eps),
+ * followed by dqmc_weights_from_params(theta).  n must be the map's n_params.  norms3: double[3] or NULL, receives the
+ * 2-norms of theta before the step, of g and of the update from a fixed-order reduction. */
+int dqmc_adam_step(dqmc_ctx* ctx, double* theta, double* mu, double* nu, const double* grad_theta, size_t n, double lr,
+                   double b1, double b2, double eps, int64_t t, double* norms3);
+/* theta += scale * delta (both double[n_params]), then dqmc_weights_from_params(theta): the entry point for directions
+ * formed elsewhere on the device (natural gradient).  norms3 as above: theta before the step, delta, scale * delta. */
+int dqmc_apply_update(dqmc_ctx* ctx, double* theta, const double* delta, double scale, double* norms3);
+/* Test access to the weight buffers.  which: 0 = the flat weights in the context's precision, 1 = the weight tape of the
+ * generated sub-step kernel, 2 = the packed planes of the fused kernel, 3 = the flat weights of the float64 twin.
+ * out_host NULL: returns the size of the buffer in bytes (> 0).  Otherwise `bytes` must be exactly that size (DQMC_E_ARG);
+ * DQMC_E_UNSUPPORTED when the context has no such buffer.  Synchronises the stream. */
+int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t bytes);
+/* out2 (host) = {captures, replays} of the context's forward-Laplacian graphs since its creation. */
+int dqmc_graph_counters(dqmc_ctx* ctx, int64_t* out2);
+
 /* psi for B walkers.  r: real[B][N][3], R: real[n_nuc][3]; out logpsi: real[B],
  * sign: int32[B] (values -1, 0, +1; bit-exact item of the parity contract). */
 int dqmc_wf_eval(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logpsi, int32_t* sign);
