@@ -14,6 +14,15 @@ from .program import DqmcBuf, DqmcOp, DqmcSystem
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libdqmc_hip.so')
 
+
+class DqmcLossTerms(ctypes.Structure):
+    """dqmc_loss_terms of include/dqmc.h."""
+    _fields_ = [('S', c_int), ('B', c_int), ('w', c_void_p), ('e_clip', c_void_p), ('e_mask', c_void_p), ('e_stats', c_void_p),
+                ('alpha', c_double), ('r_clip', c_void_p), ('r_mask', c_void_p), ('r_stats', c_void_p), ('scale', c_void_p),
+                ('rank', c_void_p), ('spin_kind', c_int), ('lam', c_double), ('spin', c_void_p), ('spin_mask', c_void_p),
+                ('spin_stats', c_void_p), ('states_host', POINTER(c_int32)), ('n_states', c_int)]
+
+
 # every symbol include/dqmc.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ('dqmc_create', c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(DqmcSystem), POINTER(c_double),
@@ -30,6 +39,9 @@ SIGNATURES = [
     ('dqmc_apply_update', c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
     ('dqmc_debug_read_weights', c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     ('dqmc_graph_counters', c_int, [c_void_p, POINTER(c_int64)]),
+    ('dqmc_psi_ratio', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    ('dqmc_clip_rows', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    ('dqmc_loss_cotangents', c_int, [c_void_p, POINTER(DqmcLossTerms), c_void_p, c_void_p]),
     ('dqmc_wf_eval', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     ('dqmc_local_energy', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ('dqmc_psi_grad', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -86,6 +86,10 @@ struct dqmc_ctx {
   virtual int apply_update(double* theta, const double* delta, double scale, double* norms3) = 0;
   virtual int debug_read_weights(int which, void* out, size_t bytes) = 0;
   virtual void graph_counters(int64_t* out2) = 0;
+  virtual int psi_ratio(const double* lg, const double* sg, int S, long B, double* ratio) = 0;
+  virtual int clip_rows(const double* x, const double* w, int n_rows, long B, int center, int scale, double clip_width,
+                        double exclude_width, double* x_clip, uint8_t* mask, double* row_stats) = 0;
+  virtual int loss_cotangents(const dqmc_loss_terms* t, double* c, double* k) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -477,6 +481,7 @@ struct Engine : dqmc_ctx {
 #include "engine_coords.inl"
 #include "engine_pretrain.inl"
 #include "engine_optim.inl"
+#include "engine_loss.inl"
 };
 
 }  // namespace
@@ -638,6 +643,22 @@ int dqmc_graph_counters(dqmc_ctx* ctx, int64_t* out2) {
   if (!ctx || !out2) return fail(DQMC_E_ARG, "null argument");
   ctx->graph_counters(out2);
   return DQMC_OK;
+}
+int dqmc_psi_ratio(dqmc_ctx* ctx, const double* log_psi, const double* sign, int S, int B, double* ratio) {
+  if (!ctx || !log_psi || !sign || !ratio) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->psi_ratio(log_psi, sign, S, B, ratio);
+}
+int dqmc_clip_rows(dqmc_ctx* ctx, const double* x, const double* w, int n_rows, int B, int center, int scale, double clip_width,
+                   double exclude_width, double* x_clip, uint8_t* mask, double* row_stats) {
+  if (!ctx || !x || !x_clip || !mask || !row_stats) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->clip_rows(x, w, n_rows, B, center, scale, clip_width, exclude_width, x_clip, mask, row_stats);
+}
+int dqmc_loss_cotangents(dqmc_ctx* ctx, const dqmc_loss_terms* terms, double* c, double* k) {
+  if (!ctx || !terms || !c) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->loss_cotangents(terms, c, k);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

@@ -1232,3 +1232,4 @@ template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 #include "kernels_coords.inl"
 #include "kernels_pretrain.inl"
 #include "kernels_optim.inl"
+#include "kernels_loss.inl"

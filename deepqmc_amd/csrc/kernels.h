@@ -535,4 +535,34 @@ void launch_adam(hipStream_t st, double* theta, double* mu, double* nu, const do
 // theta += scale * delta; norms3 = 2-norms of theta (before), delta and scale * delta
 void launch_apply_update(hipStream_t st, double* theta, const double* delta, double scale, long n, double* part, double* norms3);
 
+// ---- kernels_loss.inl (included by kernel_linear.hip): loss assembly of multi-state training (dqmc_psi_ratio, dqmc_clip_rows, dqmc_loss_cotangents) ----
+constexpr int LOSS_BLOCK = 256;          // threads per workgroup = bins of a radix-select pass; one workgroup per row
+constexpr int LOSS_MAX_STATES = 32;      // electronic states of a batch at most
+enum { LOSS_CENTER_MEAN = 0, LOSS_CENTER_MEDIAN = 1 };
+enum { LOSS_SCALE_MEAN_ABS_DEV = 0, LOSS_SCALE_MEDIAN_ABS_DEV = 1 };
+enum { LOSS_SPIN_NONE = 0, LOSS_SPIN_SQUARED = 1, LOSS_SPIN_RAISING = 2 };
+// arguments of dqmc_loss_cotangents (device pointers; r_clip == nullptr: no overlap term)
+struct LossCotArgs {
+  int S;
+  long B;
+  const double* w;                 // [S][B] or nullptr (all ones)
+  const double* e_clip; const uint8_t* e_mask; const double* e_stats;       // [S][B], [S][B], [S][4]
+  double alpha;
+  const double* r_clip; const uint8_t* r_mask; const double* r_stats;       // [S][S][B], [S][S][B], [S*S][4]
+  const double* scale; const int32_t* rank;                                 // [S][S], [S]
+  int spin_kind;
+  double lambda;
+  const double* spin; const uint8_t* spin_mask; const double* spin_stats;   // [n_states][B]; raising: clipped rows, mask, [n_states][4]
+  int n_states;
+  int32_t states[LOSS_MAX_STATES];
+  double* c;                       // [S][B]
+  double* k;                       // [n_states][B] or nullptr (raising: the direct weights)
+};
+// ratio[i][j][b] = sign_ij sign_jj exp((log_ij - mean_i) - (log_jj - mean_j)); lg, sg, ratio: [S][S][B]
+void launch_psi_ratio(hipStream_t st, const double* lg, const double* sg, int S, long B, double* ratio);
+// per row of x[n_rows][B]: clip to centre +- clip_width x scale, mask = |x - centre| < exclude_width, row_stats[row][4]
+void launch_clip_rows(hipStream_t st, const double* x, const double* w, int n_rows, long B, int center_kind, int scale_kind,
+                      double clip_width, double exclude_width, double* x_clip, uint8_t* mask, double* row_stats);
+void launch_loss_cotangents(hipStream_t st, const LossCotArgs& a);
+
 }  // namespace dqmc

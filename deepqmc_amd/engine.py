@@ -230,6 +230,93 @@ class Engine:
         self._check(self.lib.dqmc_graph_counters(self._ctx, out))
         return {'captures': int(out[0]), 'replays': int(out[1])}
 
+    # ---- loss assembly of multi-state training (dqmc_psi_ratio, dqmc_clip_rows, dqmc_loss_cotangents) ----
+    def _f64(self, name, t, shape):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device.type != self.device.type \
+                or tuple(t.shape) != tuple(shape):
+            raise DqmcError(f"'{name}' must be a contiguous float64 tensor of shape {tuple(shape)} on {self.device}")
+        return t
+
+    def _u8(self, name, t, shape):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or t.device.type != self.device.type \
+                or tuple(t.shape) != tuple(shape):
+            raise DqmcError(f"'{name}' must be a contiguous bool / uint8 tensor of shape {tuple(shape)} on {self.device}")
+        return t
+
+    def psi_ratio(self, log, sign):
+        """ratio[S, S, B] from log|psi| and sign [S, S, B] (float64; element [i, j] = psi_i on the samples of state j) by the
+        log shift of loss.compute_psi_ratio (dqmc_psi_ratio).  Nothing waits for the host."""
+        if log.dim() != 3 or log.shape[0] != log.shape[1]:
+            raise DqmcError("'log' must have shape [S, S, B]")
+        S, _, B = log.shape
+        self._f64('log', log, (S, S, B))
+        self._f64('sign', sign, (S, S, B))
+        out = torch.empty_like(log)
+        self._check(self.lib.dqmc_psi_ratio(self._ctx, log.data_ptr(), sign.data_ptr(), S, B, out.data_ptr()))
+        return out
+
+    def clip_rows(self, x, w=None, *, median_center=True, median_scale=False, clip_width=5.0, exclude_width=float('inf')):
+        """Row-wise clip of x[n_rows, B] (float64) with each row's own centre (median or mean) and scale (mean or median absolute
+        deviation) (dqmc_clip_rows).  Returns (x_clip [n_rows, B], mask bool [n_rows, B], row_stats [n_rows, 4] = centre,
+        scale, mean_b(w x_clip), mask count).  A row with a non-finite element comes back non-finite."""
+        if x.dim() != 2:
+            raise DqmcError("'x' must have shape [n_rows, B]")
+        n, B = x.shape
+        self._f64('x', x, (n, B))
+        if w is not None:
+            self._f64('w', w, (n, B))
+        out = torch.empty_like(x)
+        mask = torch.empty(n, B, dtype=torch.uint8, device=self.device)
+        stats = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_clip_rows(self._ctx, x.data_ptr(), w.data_ptr() if w is not None else None, n, B,
+                                            int(bool(median_center)), int(bool(median_scale)), float(clip_width), float(exclude_width),
+                                            out.data_ptr(), mask.data_ptr(), stats.data_ptr()))
+        return out, mask.view(torch.bool), stats
+
+    def loss_cotangents(self, e_clip, e_mask, e_stats, w=None, *, alpha=0.0, r_clip=None, r_mask=None, r_stats=None, scale=None,
+                        rank=None, spin_kind=None, spin_penalty=0.0, spin=None, spin_mask=None, spin_stats=None, states=None):
+        """The cotangents c[S, B] of log|psi_s| on the states' own samples from the clipped energies, optionally the clipped
+        ratios and the spin rows (dqmc_loss_cotangents; formulas in include/dqmc.h).  spin_kind: None, 'squared' or 'raising'.
+        Returns (c, k): k [n_states, B] the direct weights of the raising kind (else None).  Everything stays on the device."""
+        S, B = e_clip.shape
+        t = _lib.DqmcLossTerms()
+        keep = []
+
+        def ptr(x):
+            keep.append(x)
+            return x.data_ptr()
+        t.S, t.B = S, B
+        t.w = ptr(self._f64('w', w, (S, B))) if w is not None else None
+        t.e_clip, t.e_mask, t.e_stats = ptr(self._f64('e_clip', e_clip, (S, B))), ptr(self._u8('e_mask', e_mask, (S, B))), \
+            ptr(self._f64('e_stats', e_stats, (S, 4)))
+        t.alpha = float(alpha)
+        if r_clip is not None:
+            if rank is None or rank.dtype != torch.int32 or tuple(rank.shape) != (S,) or rank.device.type != self.device.type:
+                raise DqmcError(f"'rank' must be an int32 tensor of shape ({S},) on {self.device}")
+            t.r_clip, t.r_mask = ptr(self._f64('r_clip', r_clip, (S, S, B))), ptr(self._u8('r_mask', r_mask, (S, S, B)))
+            t.r_stats, t.scale, t.rank = ptr(self._f64('r_stats', r_stats, (S * S, 4))), ptr(self._f64('scale', scale, (S, S))), \
+                ptr(rank.contiguous())
+        kinds = {None: 0, 'squared': 1, 'raising': 2}
+        if spin_kind not in kinds:
+            raise ValueError("spin_kind must be None, 'squared' or 'raising'")
+        t.spin_kind, t.lam = kinds[spin_kind], float(spin_penalty)
+        k = None
+        if spin_kind is not None:
+            states = list(range(S)) if states is None else [int(q) for q in states]
+            n = len(states)
+            arr = (ctypes.c_int32 * max(n, 1))(*states)
+            keep.append(arr)
+            t.states_host, t.n_states = arr, n
+            t.spin = ptr(self._f64('spin', spin, (n, B)))
+            if spin_kind == 'raising':
+                t.spin_mask, t.spin_stats = ptr(self._u8('spin_mask', spin_mask, (n, B))), ptr(self._f64('spin_stats', spin_stats, (n, 4)))
+                k = torch.empty(n, B, dtype=torch.float64, device=self.device)
+        c = torch.empty(S, B, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_loss_cotangents(self._ctx, ctypes.byref(t), c.data_ptr(), k.data_ptr() if k is not None else None))
+        return c, k
+
     # ---- ansatz.apply ---------------------------------------------------
     def wf_eval(self, r, R=None):
         r = self._t(r)

@@ -202,6 +202,12 @@ def compute_energy_loss_and_natgrad(rng, hamil, ansatz, params: Sequence, phys_c
         raise ValueError('damping must be positive')
     r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_natgrad', rng, hamil, ansatz, params, phys_conf,
                                                              weight, clip_mask_fn, static_io=flat)
+    return _natgrad_directions('compute_energy_loss_and_natgrad', ansatz, params, r, Rs, loss, cots, masks, stats, damping, flat)
+
+
+def _natgrad_directions(name, ansatz, params, r, Rs, loss, cots, masks, stats, damping, flat):
+    """The body of compute_energy_loss_and_natgrad for given cotangents c_s and masks m_s (the penalties of create_loss_fn
+    enter through c_s only)."""
     deltas, gs = [], []
     for s, cot in enumerate(cots):
         pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
@@ -352,3 +358,379 @@ def compute_energy_loss_and_kfac(rng, hamil, ansatz, params: Sequence, phys_conf
     stats['grad'] = gs
     stats['precon_grad_dot'] = torch.tensor(dots, dtype=torch.float64)
     return loss, deltas, stats, state
+
+
+# ---- the training loss of several electronic states: energy + overlap penalty + spin penalty (loss/loss_function.py:107-308) ----
+
+def psi_ratio_clip_and_mask(x: torch.Tensor, clip_width: float = 10.0, exclude_width: float = float('inf')):
+    """loss/clip.py:144-174 for one [B] batch of wave-function ratios: clip to median +- clip_width x the median absolute
+    deviation from it (both medians exact, the mean of the two middle values for even B); mask = deviation < exclude_width."""
+    def median(v):
+        vs = torch.sort(v).values
+        n = vs.shape[0]
+        return 0.5 * (vs[(n - 1) // 2] + vs[n // 2])
+    center = median(x)
+    deviation = (x - center).abs()
+    sigma = median(deviation)
+    return torch.clamp(x, center - clip_width * sigma, center + clip_width * sigma), deviation < exclude_width
+
+
+def no_scaling(data):
+    """loss/overlap.py:158-160."""
+    return torch.tensor(1.0, dtype=torch.float64)
+
+
+def scale_by_energy_gap(data, min_gap_scale_factor: float = 0.1):
+    """loss/overlap.py:163-170: clip(nan_to_num(|E_i - E_j|, nan=1), min_gap_scale_factor, 5) of the running energies
+    data['energy_ewm'] [M, S] -> [M, S, S]."""
+    e = data['energy_ewm']
+    return torch.clamp(torch.nan_to_num((e[:, :, None] - e[:, None]).abs(), nan=1.0), min_gap_scale_factor, 5.0)
+
+
+def scale_by_energy_std(data, min_gap_scale_factor: float = 0.01):
+    """loss/overlap.py:173-177: clip(nan_to_num(mean over molecules of data['std_ewm'], nan=5), min_gap_scale_factor, 5) -> [S, 1]."""
+    return torch.clamp(torch.nan_to_num(data['std_ewm'].mean(dim=0), nan=5.0), min_gap_scale_factor, 5.0)[:, None]
+
+
+def scale_by_max_gap_std(data, min_gap_scale_factor: float = 0.1):
+    """loss/overlap.py:180-184."""
+    return torch.maximum(scale_by_energy_gap(data, min_gap_scale_factor), scale_by_energy_std(data, min_gap_scale_factor))
+
+
+def _states(states, S):
+    return list(range(S)) if states is None else [int(s) for s in states]
+
+
+def compute_spin_contributions(hamil, ansatz, params: Sequence, phys_conf, states=None):
+    """loss/spin.py:13-46: <S^2> per walker (physics.evaluate_spin) of the states `states` (default: all) on their own
+    samples -> float64 [1, n_states, B]."""
+    r, Rs = _unpack(phys_conf)
+    if r.shape[0] != 1:
+        raise ValueError('compute_spin_contributions: one molecule per batch ([1, S, B])')
+    from .physics import evaluate_spin
+    spin = evaluate_spin(hamil, ansatz)
+    return torch.stack([spin(params[s], _state_conf(ansatz, params[s], r, Rs, s)[0]) for s in _states(states, r.shape[1])])[None]
+
+
+def spin_raising_down_idx(rng, hamil) -> int:
+    """The down electron of the stochastic spin-raising operator for the integer step seed `rng`: ONE index for the whole
+    batch, as the reference draws it (loss/spin.py:151-154), by the rule
+        down_idx = n_up + numpy.random.default_rng([rng mod 2^64, 0x5350494e]).integers(n_down)."""
+    if not isinstance(rng, (int, np.integer)):
+        raise ValueError('the spin-raising penalty needs an integer step seed `rng` (or an explicit down_idx)')
+    return hamil.n_up + int(np.random.default_rng([int(rng) & (2 ** 64 - 1), 0x5350494e]).integers(hamil.n_down))
+
+
+def compute_spin_raising_contributions(rng, hamil, ansatz, phys_conf, params: Sequence, states=None, down_idx=None, return_ratios=False):
+    """loss/spin.py:118-172: L_b = 1 - sum_{alpha in up} psi(P_{alpha beta} r_b) / psi(r_b) for one down electron beta of the
+    whole batch, drawn from the step seed by spin_raising_down_idx unless `down_idx` fixes it -> float64 [1, n_states, B].
+    return_ratios: also the ratios rho[n_states, B, n_up] the direct term of the gradient is weighted with."""
+    from .physics import _ratios
+    r, Rs = _unpack(phys_conf)
+    if r.shape[0] != 1:
+        raise ValueError('compute_spin_raising_contributions: one molecule per batch ([1, S, B])')
+    beta = spin_raising_down_idx(rng, hamil) if down_idx is None else int(down_idx)
+    if not hamil.n_up <= beta < hamil.n_up + hamil.n_down:
+        raise ValueError(f'down_idx must lie in [{hamil.n_up}, {hamil.n_up + hamil.n_down})')
+    rows, rhos = [], []
+    for s in _states(states, r.shape[1]):
+        pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
+        up = torch.arange(hamil.n_up, device=eng.device)
+        rho = _ratios(ansatz, params[s], pc, up, torch.full_like(up, beta))          # [B, n_up]
+        rows.append(1.0 - rho.sum(-1))
+        rhos.append(rho)
+    out = torch.stack(rows)[None]
+    return (out, torch.stack(rhos), beta) if return_ratios else out
+
+
+def compute_mean_spin(spin_contributions: torch.Tensor, weight: torch.Tensor, states=None):
+    """loss/spin.py:49-73: (mean over [1, n_states, B] of spin x weight, {'spin/mean', 'spin/std'}: the weighted average and
+    standard deviation per state [1, n_states])."""
+    sw = weight[:, _states(states, weight.shape[1])]
+    mean = (spin_contributions * sw).sum(-1) / sw.sum(-1)
+    var = ((spin_contributions - mean[..., None]) ** 2 * sw).sum(-1) / sw.sum(-1)
+    return (spin_contributions * sw).mean(), {'spin/mean': mean, 'spin/std': torch.sqrt(var)}
+
+
+def _library_clip(fn, base, defaults):
+    """The keyword values of `fn` if it is `base` itself or a functools.partial (of partials) of it, else None."""
+    import functools
+    import inspect
+    args, kw = (), {}
+    while isinstance(fn, functools.partial):
+        args, kw = fn.args + args, {**fn.keywords, **kw}
+        fn = fn.func
+    if fn is not base:
+        return None
+    try:
+        bound = inspect.signature(base).bind_partial(None, *args, **kw)
+    except TypeError:
+        return None
+    out = dict(defaults)
+    out.update({k: v for k, v in bound.arguments.items() if k != 'x'})
+    return out
+
+
+def _single_process(name):
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError(f'{name}: single process only (the medians and means of other ranks are not gathered)')
+
+
+class LossFunction:
+    """The object create_loss_fn returns; see there."""
+
+    def __init__(self, hamil, ansatz, clip_mask_fn, clip_mask_overlap_fn, alpha, spin_penalty, spin_penalty_type, spin_penalty_states,
+                 scale_overlap_by, sort_states_by, min_gap_scale_factor):
+        import functools
+        if spin_penalty_type not in ('squared', 'raising'):
+            raise ValueError("spin_penalty_type must be 'squared' or 'raising'")
+        scale_fns = {None: no_scaling, 'energy_gap': scale_by_energy_gap, 'energy_std': scale_by_energy_std, 'max_gap_std': scale_by_max_gap_std}
+        if scale_overlap_by not in scale_fns:
+            raise ValueError(f'scale_overlap_by must be one of {list(scale_fns)}')
+        if sort_states_by not in (None, 'energy'):
+            raise ValueError("sort_states_by must be None or 'energy'")
+        self.hamil, self.ansatz = hamil, ansatz
+        self.clip_mask_fn, self.clip_mask_overlap_fn = clip_mask_fn, clip_mask_overlap_fn
+        self.alpha, self.spin_penalty, self.spin_penalty_type = alpha, spin_penalty, spin_penalty_type
+        self.spin_penalty_states = None if spin_penalty_states is None else [int(s) for s in spin_penalty_states]
+        self.scale_overlap_by, self.sort_states_by = scale_overlap_by, sort_states_by
+        # (loss_function.py:121-135: every factory is called with THIS min_gap_scale_factor, scale_by_energy_std included)
+        self.scale_fn = no_scaling if scale_overlap_by is None else functools.partial(scale_fns[scale_overlap_by],
+                                                                                     min_gap_scale_factor=min_gap_scale_factor)
+        self._e_clip = _library_clip(clip_mask_fn, median_clip_and_mask, dict(clip_width=5.0, median_center=True, exclude_width=float('inf')))
+        self._r_clip = _library_clip(clip_mask_overlap_fn, psi_ratio_clip_and_mask, dict(clip_width=10.0, exclude_width=float('inf')))
+        self.kernel_path = self._e_clip is not None and (self._r_clip is not None or clip_mask_overlap_fn is None)
+        self._index_cache = {}
+
+    # -- pieces ------------------------------------------------------------
+    def _states_index(self, states, device):
+        """The spin states as an index tensor on `device`: uploaded once, so that no step copies it from the host."""
+        key = (tuple(states), str(device))
+        if key not in self._index_cache:
+            self._index_cache[key] = torch.tensor(states, dtype=torch.long, device=device)
+        return self._index_cache[key]
+
+    def ordering(self, data, S, device):
+        """data['ordering'] of loss_function.py:136-139, 228 for molecule 0 -> (ordering [S], rank [S] int32 = its inverse)."""
+        if self.sort_states_by == 'energy':
+            order = torch.argsort(data['energy_ewm'][0].to(device), dim=-1, stable=True)
+        else:
+            order = torch.arange(S, device=device)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(S, device=device)
+        return order, rank.to(torch.int32)
+
+    def overlap_scale(self, data, S, device):
+        """scale[S, S] of the configured factory for molecule 0."""
+        if self.scale_overlap_by is None:
+            return torch.ones(S, S, dtype=torch.float64, device=device)
+        sc = torch.as_tensor(self.scale_fn(data), dtype=torch.float64).to(device)
+        if sc.dim() == 3:
+            sc = sc[0]
+        return sc.expand(S, S).contiguous()
+
+    def cotangents(self, e_loc, weight, psi_ratio=None, spin=None, data=None, path=None, engine=None, return_mask=False):
+        """The loss assembly on its own: from E_loc [S, B], the weights [S, B], the ratios [S, S, B] (S > 1), the spin rows
+        [n_states, B] (squared: <S^2>, raising: L) and data -> (c [S, B], k [n_states, B] or None), float64 on the device
+        of the inputs.  path: 'kernel' (dqmc_clip_rows + dqmc_loss_cotangents on `engine`'s stream), 'torch' (the same formulas in
+        torch, any clip callable), default: the kernel path when the clip functions are the library's own.
+        return_mask: also the energy clip mask, bool [S, B] (what the natural gradient centres its Fisher matrix with).
+        Row q of `spin` belongs to state states[q], and so does row q of the raising kind's clip mask: the reference indexes
+        that [M, n_states, B] mask by the state NUMBERS once more (spin.py:207-209), which for a proper subset of the states
+        picks clamped or shifted rows; that is not reproduced."""
+        path = path or ('kernel' if self.kernel_path else 'torch')
+        S, B = e_loc.shape
+        if S > 1 and self.alpha is None:
+            raise ValueError('alpha must be set for the overlap loss of more than one state')
+        data = data or {}
+        if S > 1 and 'energy_ewm' not in data and (self.sort_states_by or self.scale_overlap_by in ('energy_gap', 'max_gap_std')):
+            raise ValueError("data['energy_ewm'] is required")
+        if path == 'kernel':
+            if not self.kernel_path:
+                raise ValueError('the kernel path needs the library\'s own clip functions (median_clip_and_mask, psi_ratio_clip_and_mask)')
+            c, k, e_mask = self._cotangents_kernel(engine, e_loc, weight, psi_ratio, spin, data)
+        elif path == 'torch':
+            c, k, e_mask = self._cotangents_torch(e_loc, weight, psi_ratio, spin, data)
+        else:
+            raise ValueError("path must be 'kernel' or 'torch'")
+        return (c, k, e_mask) if return_mask else (c, k)
+
+    def _cotangents_kernel(self, eng, e, w, ratio, spin, data):
+        S, B = e.shape
+        ec = self._e_clip
+        kw = {}
+        e_clip, e_mask, e_stats = eng.clip_rows(e, w, median_center=bool(ec['median_center']), median_scale=False,
+                                                clip_width=ec['clip_width'], exclude_width=ec['exclude_width'])
+        if S > 1:
+            rc = self._r_clip
+            w_rows = w[None].expand(S, S, B).reshape(S * S, B).contiguous()           # row (i, j) is weighted with w_j
+            r_clip, r_mask, r_stats = eng.clip_rows(ratio.reshape(S * S, B), w_rows, median_center=True, median_scale=True,
+                                                    clip_width=rc['clip_width'], exclude_width=rc['exclude_width'])
+            kw.update(alpha=self.alpha, r_clip=r_clip.view(S, S, B), r_mask=r_mask.view(S, S, B), r_stats=r_stats,
+                      scale=self.overlap_scale(data, S, e.device), rank=self.ordering(data, S, e.device)[1])
+        if self.spin_penalty is not None:
+            states = _states(self.spin_penalty_states, S)
+            kw.update(spin_kind=self.spin_penalty_type, spin_penalty=self.spin_penalty, states=states)
+            if self.spin_penalty_type == 'squared':
+                kw['spin'] = spin.contiguous()
+            else:
+                l_clip, l_mask, l_stats = eng.clip_rows(spin.contiguous(), w[self._states_index(states, w.device)], median_center=bool(ec['median_center']),
+                                                        median_scale=False, clip_width=ec['clip_width'], exclude_width=ec['exclude_width'])
+                kw.update(spin=l_clip, spin_mask=l_mask, spin_stats=l_stats)
+        c, k = eng.loss_cotangents(e_clip, e_mask, e_stats, w, **kw)
+        return c, k, e_mask
+
+    def _cotangents_torch(self, e, w, ratio, spin, data):
+        S, B = e.shape
+        f64 = torch.float64
+        clipped = [self.clip_mask_fn(e[s]) for s in range(S)]
+        e_clip = torch.stack([c for c, _ in clipped])
+        e_mask_b = torch.stack([m for _, m in clipped])
+        e_mask = e_mask_b.to(f64)
+        c = e_mask * w * (e_clip - (e_clip * w).mean(-1, keepdim=True)) / e_mask.sum()
+        if S > 1:
+            if self.clip_mask_overlap_fn is None:
+                raise ValueError('clip_mask_overlap_fn must be set for more than one state')
+            pairs = [[self.clip_mask_overlap_fn(ratio[i, j]) for j in range(S)] for i in range(S)]
+            r_clip = torch.stack([torch.stack([p[0] for p in row]) for row in pairs])
+            r_mask = torch.stack([torch.stack([p[1] for p in row]) for row in pairs]).to(f64)
+            x = (r_clip * w[None]).mean(-1)                                           # x_ij = mean_b(w_jb rho^_ijb)
+            scale = self.overlap_scale(data, S, e.device)
+            rank = self.ordering(data, S, e.device)[1]
+            lower = (rank[:, None] < rank[None, :]).to(f64)                           # [i, j]: rank(i) < rank(j)
+            coef = self.alpha * lower * 2.0 * x.transpose(0, 1) * scale / r_mask.sum(-1)
+            c = c + (coef[:, :, None] * r_mask * (r_clip - x[:, :, None]) * w[None]).sum(0)
+        k = None
+        if self.spin_penalty is not None:
+            states = _states(self.spin_penalty_states, S)
+            idx = self._states_index(states, w.device)
+            sw = w[idx]
+            if self.spin_penalty_type == 'squared':
+                m = e_mask[idx]
+                add = self.spin_penalty * m * sw * (spin - (spin * sw).mean(-1, keepdim=True)) / m.sum()
+            else:
+                clipped = [self.clip_mask_fn(spin[q]) for q in range(len(states))]
+                l_clip = torch.stack([cl for cl, _ in clipped])
+                m = torch.stack([mk for _, mk in clipped]).to(f64)
+                mu = (l_clip * sw).mean(-1, keepdim=True)
+                k = self.spin_penalty * m * mu * sw / m.sum()
+                add = k * 2.0 * (l_clip - mu)
+            c = c.index_add(0, idx, add)
+        return c, k, e_mask_b
+
+    def _psi_ratio(self, params, r, Rs):
+        """compute_psi_ratio with the log shift on the device (dqmc_psi_ratio) -> [1, S, S, B]."""
+        S, B = r.shape[1], r.shape[2]
+        eng0 = self.ansatz.engine(params[0], Rs[0])
+        sign = torch.empty(S, S, B, dtype=torch.float64, device=eng0.device)
+        log = torch.empty(S, S, B, dtype=torch.float64, device=eng0.device)
+        r_all = r[0].reshape(S * B, *r.shape[3:]).contiguous()
+        for i in range(S):
+            sg, lg = self.ansatz.engine(params[i], Rs[0]).wf_eval(r_all, Rs[0])
+            sign[i], log[i] = sg.reshape(S, B), lg.reshape(S, B)
+        return eng0.psi_ratio(log, sign)[None]
+
+    # -- the whole step --------------------------------------------------------
+    def evaluate(self, rng, params, batch, static_io=False, down_idx=None):
+        """The value side (loss_function.py:141-189): -> dict(loss, e_loc [1,S,B], weight [1,S,B], psi_ratio [1,S,S,B] or None,
+        spin [n_states, B] or None, rho, stats, r, Rs)."""
+        phys_conf, weight = batch[0], batch[1] if len(batch) > 1 else None
+        _single_process('create_loss_fn')
+        r, Rs = _unpack(phys_conf)
+        if r.shape[0] != 1:
+            raise ValueError('create_loss_fn: one molecule per batch ([1, S, B])')
+        S, B = r.shape[1], r.shape[2]
+        if S > 1 and self.alpha is None:
+            raise ValueError('alpha must be set for the overlap loss of more than one state')
+        e_loc, stats = compute_local_energy(rng, self.hamil, self.ansatz, params, phys_conf, static_io=static_io)
+        e64 = e_loc.double()
+        w = torch.ones_like(e64) if weight is None else torch.as_tensor(weight, dtype=torch.float64, device=e64.device).reshape(e64.shape)
+        out = dict(e_loc=e_loc, e64=e64, weight=w, r=r, Rs=Rs, psi_ratio=None, spin=None, rho=None, beta=None)
+        loss = (e64 * w).mean()
+        stats = dict(stats)
+        if S > 1:
+            psi_ratio = self._psi_ratio(params, r, Rs) if self.kernel_path else compute_psi_ratio(self.ansatz, params, phys_conf)[0]
+            overlap_loss, ostats = compute_mean_overlap(psi_ratio, w)
+            loss = loss + self.alpha * overlap_loss
+            stats.update(ostats)
+            out['psi_ratio'] = psi_ratio
+        if self.spin_penalty is not None:
+            if self.spin_penalty_type == 'squared':
+                spin = compute_spin_contributions(self.hamil, self.ansatz, params, phys_conf, self.spin_penalty_states)
+            else:
+                spin, out['rho'], out['beta'] = compute_spin_raising_contributions(rng, self.hamil, self.ansatz, phys_conf, params,
+                                                                                   self.spin_penalty_states, down_idx, return_ratios=True)
+            mean_spin, sstats = compute_mean_spin(spin, w, self.spin_penalty_states)
+            loss = loss + self.spin_penalty * mean_spin
+            stats.update(sstats)
+            out['spin'] = spin[0]
+        stats['E_loc'] = e_loc
+        out.update(loss=loss, stats=stats)
+        return out
+
+    def loss_and_cotangents(self, rng, params, batch, static_io=False, down_idx=None, path=None):
+        """evaluate + cotangents: -> (values dict of evaluate, which gains 'e_mask' bool [S, B], c [S, B], k or None)."""
+        v = self.evaluate(rng, params, batch, static_io=static_io, down_idx=down_idx)
+        data = batch[2] if len(batch) > 2 and batch[2] is not None else {}
+        eng = self.ansatz.engine(params[0], v['Rs'][0])
+        c, k, v['e_mask'] = self.cotangents(v['e64'][0].contiguous(), v['weight'][0].contiguous(),
+                                            None if v['psi_ratio'] is None else v['psi_ratio'][0], v['spin'], data, path=path, engine=eng,
+                                            return_mask=True)
+        return v, c, k
+
+    def loss_and_grad(self, rng, params, batch, flat: bool = False, down_idx=None, path=None):
+        """-> (loss, [grad per state], (E_loc [1,S,B], psi_ratio [1,S,S,B] or None, stats)).  Per state one dqmc_log_psi_vjp call with
+        the cotangent c_s; the raising kind runs it on the stack [r_s ; P_alpha r_s, alpha < n_up] with the cotangents
+        [c_sb + k_sb sum_alpha rho_b,alpha ; -k_sb rho_b,alpha].  flat=True: float64 device vectors in parameter order
+        (Engine.grad_to_params) and nothing waits for the host; else host trees."""
+        from .physics import _swapped
+        v, c, k = self.loss_and_cotangents(rng, params, batch, static_io=flat, down_idx=down_idx, path=path)
+        r, Rs = v['r'], v['Rs']
+        S, B = r.shape[1], r.shape[2]
+        states = _states(self.spin_penalty_states, S)
+        grads = []
+        for s in range(S):
+            eng = self.ansatz.engine(params[s], Rs[0])
+            if flat and eng.program.grad_unsupported:
+                raise NotImplementedError(f'create_loss_fn: unsupported for this program ({eng.program.grad_unsupported})')
+            rr, cot = r[0, s].contiguous(), c[s]
+            if k is not None and s in states:
+                q = states.index(s)
+                rho, n_up = v['rho'][q], self.hamil.n_up                               # [B, n_up]
+                up = torch.arange(n_up, device=eng.device)
+                rp = _swapped(torch.as_tensor(rr, dtype=eng.dtype, device=eng.device), up, torch.full_like(up, v['beta']))   # [B, n_up, N, 3]
+                rr = torch.cat([torch.as_tensor(rr, dtype=eng.dtype, device=eng.device), rp.reshape(B * n_up, *rp.shape[2:])])
+                cot = torch.cat([cot + k[q] * rho.sum(-1), (-k[q][:, None] * rho).reshape(-1)])
+            _, _, g = eng.log_psi_vjp(rr, cot.to(eng.dtype).contiguous(), Rs[0])
+            grads.append(eng.grad_to_params(g) if flat else eng.program.unflatten_grad(g))
+        return v['loss'], grads, (v['e_loc'], v['psi_ratio'], v['stats'])
+
+    __call__ = loss_and_grad
+
+
+def create_loss_fn(hamil, ansatz, clip_mask_fn=median_clip_and_mask, clip_mask_overlap_fn=psi_ratio_clip_and_mask, alpha=None,
+                   spin_penalty=None, spin_penalty_type='squared', spin_penalty_states=None, scale_overlap_by=None, sort_states_by=None,
+                   min_gap_scale_factor=0.1):
+    """loss/loss_function.py:107-308 for a [1, S, B] batch: the energy loss of compute_energy_loss_and_grad plus
+    alpha x the overlap penalty between the states and spin_penalty x a spin penalty ('squared': <S^2> of physics.evaluate_spin,
+    'raising': the stochastic spin-raising estimator), over `spin_penalty_states` (default: all).  Returns a LossFunction whose
+        loss_and_grad(rng, params, batch, flat=False) -> (loss, [grad per state], (E_loc [1,S,B], psi_ratio [1,S,S,B] or None, stats))
+    takes batch = (phys_conf, weight, data), data = {'energy_ewm': [1, S], 'std_ewm': [1, S]} float64 device tensors (the
+    running averages of fit_wf; NaN before the first update).  The loss VALUE uses the unclipped overlap and spin means
+    (loss_function.py:141-189); stats gains 'overlap/pairwise/mean' [1,S,S], 'spin/mean' and 'spin/std' [1, n_states].
+
+    Every penalty tangent is a linear functional of the tangent of log|psi_s| on state s's own samples, so the gradient of
+    state s is ONE vector-Jacobian product with the cotangent (w weights, hats clipped values, m masks)
+        c_sb  = m_sb w_sb (E^_sb - mean_b(E^_s w_s)) / sum_{s,b} m_sb
+        c_jb += alpha sum_{i: rank(i) < rank(j)} 2 x_ji scale_ij m_ijb (rho^_ijb - x_ij) w_jb / sum_b m_ijb,  x_ij = mean_b(w_jb rho^_ijb)
+        c_sb += lambda m_sb w_sb (s_sb - mean_b(s_s w_s)) / sum_{s in states, b} m_sb                              ('squared')
+        c_sb += lambda m_sb mu_s w_sb 2 (L^_sb - mu_s) / n, mu_s = mean_b(L^_s w_s), plus the direct term sum_b k_sb dL_sb,
+                k_sb = lambda m_sb mu_s w_sb / n                                                                   ('raising')
+    rank = the inverse of the state ordering (sort_states_by='energy': argsort of data['energy_ewm']), scale_ij from
+    scale_overlap_by (None, 'energy_gap', 'energy_std', 'max_gap_std').  The assembly runs as HIP kernels (dqmc_clip_rows,
+    dqmc_loss_cotangents) when the clip functions are median_clip_and_mask / psi_ratio_clip_and_mask or functools.partial of
+    them, and as the same formulas in torch for any other callable.  One molecule, single process (NotImplementedError under
+    an initialised process group of more than one rank); S > 1 without alpha is a ValueError."""
+    return LossFunction(hamil, ansatz, clip_mask_fn, clip_mask_overlap_fn, alpha, spin_penalty, spin_penalty_type, spin_penalty_states,
+                        scale_overlap_by, sort_states_by, min_gap_scale_factor)

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import torch
 
-from .loss import _unpack, compute_energy_loss_and_grad, compute_energy_loss_and_natgrad, compute_local_energy, median_clip_and_mask
+from .loss import _natgrad_directions, _unpack, compute_energy_loss_and_grad, compute_energy_loss_and_natgrad, compute_local_energy, median_clip_and_mask
 
 __all__ = ['NoOptimizer', 'AdamOptimizer', 'NaturalGradientOptimizer', 'merge_states_flat']
 
@@ -25,8 +25,12 @@ __all__ = ['NoOptimizer', 'AdamOptimizer', 'NaturalGradientOptimizer', 'merge_st
 class _Optimizer:
     changes_params = True
 
-    def __init__(self, *, hamil=None, ansatz=None, clip_mask_fn=median_clip_and_mask):
-        self.hamil, self.ansatz, self.clip_mask_fn = hamil, ansatz, clip_mask_fn
+    def __init__(self, *, hamil=None, ansatz=None, clip_mask_fn=median_clip_and_mask, loss_fn=None):
+        """loss_fn: a loss.create_loss_fn object (energy + overlap + spin penalties, its own clip functions); None: the energy
+        loss of compute_energy_loss_and_grad with `clip_mask_fn`, exactly as without the argument."""
+        self.hamil, self.ansatz, self.clip_mask_fn, self.loss_fn = hamil, ansatz, clip_mask_fn, loss_fn
+        if loss_fn is not None and hamil is None:
+            self.hamil, self.ansatz = loss_fn.hamil, loss_fn.ansatz
 
     def bind(self, hamil, ansatz):
         """The Hamiltonian and the wave function the loss is evaluated with (fit_wf binds an optimiser built without them)."""
@@ -72,6 +76,11 @@ class NoOptimizer(_Optimizer):
 
     def step(self, rng, params, opt_state, batch):
         phys_conf, _ = self._batch(batch)
+        if self.loss_fn is not None:       # the loss value and the ratios, no gradient
+            v = self.loss_fn.evaluate(rng, params, batch, static_io=True)
+            stats = dict(v['stats'])
+            e_loc = stats.pop('E_loc')
+            return params, opt_state, e_loc, v['psi_ratio'], {'loss': v['loss'], **stats}
         e_loc, stats = compute_local_energy(rng, self.hamil, self.ansatz, params, phys_conf, static_io=True)
         return params, opt_state, e_loc, None, dict(stats)
 
@@ -90,8 +99,13 @@ class AdamOptimizer(_Optimizer):
 
     def step(self, rng, params, opt_state, batch):
         phys_conf, weight = self._batch(batch)
-        _, grads, stats = compute_energy_loss_and_grad(rng, self.hamil, self.ansatz, params, phys_conf, weight, self.clip_mask_fn,
-                                                       flat=True)
+        ratios, extra = None, {}
+        if self.loss_fn is not None:
+            loss, grads, (_, ratios, stats) = self.loss_fn.loss_and_grad(rng, params, batch, flat=True)
+            extra = {'loss': loss}
+        else:
+            _, grads, stats = compute_energy_loss_and_grad(rng, self.hamil, self.ansatz, params, phys_conf, weight, self.clip_mask_fn,
+                                                           flat=True)
         for eng, st, g in zip(self._engines(params, phys_conf), opt_state, grads):
             lr = self.lr(st['count']) if callable(self.lr) else self.lr
             eng.adam_step(st['theta'], st['mu'], st['nu'], g, lr=lr, b1=self.b1, b2=self.b2, eps=self.eps, t=st['count'] + 1,
@@ -99,7 +113,7 @@ class AdamOptimizer(_Optimizer):
             st['count'] += 1
         stats = dict(stats)
         e_loc = stats.pop('E_loc')
-        return params, opt_state, e_loc, None, {**self._opt_stats(opt_state), **stats}
+        return params, opt_state, e_loc, ratios, {**self._opt_stats(opt_state), **extra, **stats}
 
 
 class NaturalGradientOptimizer(_Optimizer):
@@ -110,14 +124,25 @@ class NaturalGradientOptimizer(_Optimizer):
     def __init__(self, learning_rate=1e-2, damping=1e-3, **kw):
         super().__init__(**kw)
         self.lr, self.damping = learning_rate, damping
+        if self.loss_fn is not None and self.loss_fn.spin_penalty is not None and self.loss_fn.spin_penalty_type == 'raising':
+            raise NotImplementedError("NaturalGradientOptimizer: the 'raising' spin penalty has a direct term that is not a "
+                                      'contraction with the Jacobian of log|psi|')
 
     def init(self, rng, params, batch):
         return self._new_state(params, batch, moments=False)
 
     def step(self, rng, params, opt_state, batch):
         phys_conf, weight = self._batch(batch)
-        _, deltas, stats = compute_energy_loss_and_natgrad(rng, self.hamil, self.ansatz, params, phys_conf, self.damping, weight,
-                                                           self.clip_mask_fn, flat=True)
+        ratios, extra = None, {}
+        if self.loss_fn is not None:
+            # g_s = c_s J_s with the cotangent of the whole loss, preconditioned by the Fisher matrix of the energy path
+            v, c, _ = self.loss_fn.loss_and_cotangents(rng, params, batch, static_io=True)
+            ratios, extra = v['psi_ratio'], {'loss': v['loss']}
+            _, deltas, stats = _natgrad_directions('NaturalGradientOptimizer', self.ansatz, params, v['r'], v['Rs'], v['loss'],
+                                                   list(c), list(v['e_mask']), dict(v['stats']), self.damping, flat=True)
+        else:
+            _, deltas, stats = compute_energy_loss_and_natgrad(rng, self.hamil, self.ansatz, params, phys_conf, self.damping, weight,
+                                                               self.clip_mask_fn, flat=True)
         for eng, st, d in zip(self._engines(params, phys_conf), opt_state, deltas):
             lr = self.lr(st['count']) if callable(self.lr) else self.lr
             eng.apply_update(st['theta'], d, scale=-lr, norms=st['norms'])
@@ -125,7 +150,7 @@ class NaturalGradientOptimizer(_Optimizer):
         stats = dict(stats)
         e_loc = stats.pop('E_loc')
         stats.pop('grad', None)
-        return params, opt_state, e_loc, None, {**self._opt_stats(opt_state), **stats}
+        return params, opt_state, e_loc, ratios, {**self._opt_stats(opt_state), **extra, **stats}
 
 
 def merge_states_flat(ansatz, params, opt_state, merge_keys, phys_conf=None):

@@ -192,6 +192,65 @@ int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t byt
 /* out2 (host) = {captures, replays} of the context's forward-Laplacian graphs since its creation. */
 int dqmc_graph_counters(dqmc_ctx* ctx, int64_t* out2);
 
+/* ---- Loss assembly of multi-state training: between the value passes and dqmc_log_psi_vjp ----
+ * All buffers are device memory of the caller, double (masks: uint8, 0 or 1).  The calls run on the context's stream, allocate
+ * nothing, copy nothing to the host and do not synchronise; any context serves (it supplies the stream and nothing else).
+ * Every sum has a fixed order: identical calls give bit-identical results.  One molecule, one process. */
+
+/* Wave-function ratios from log-shifted values.  log_psi, sign, ratio: double[S][S][B], element [i][j][b] = psi_i on sample b
+ * of state j.  With mean_i the mean of log_psi[i] over all S B samples:
+ *   ratio[i][j][b] = sign[i][j][b] sign[j][j][b] exp((log_psi[i][j][b] - mean_i) - (log_psi[j][j][b] - mean_j)). */
+int dqmc_psi_ratio(dqmc_ctx* ctx, const double* log_psi, const double* sign, int S, int B, double* ratio);
+
+#define DQMC_CLIP_CENTER_MEAN 0
+#define DQMC_CLIP_CENTER_MEDIAN 1       /* exact; even B: the mean of the two middle values */
+#define DQMC_CLIP_SCALE_MEAN_ABS_DEV 0  /* mean_b |x - centre| */
+#define DQMC_CLIP_SCALE_MEDIAN_ABS_DEV 1 /* median_b |x - centre|, exact */
+/* Per row of x[n_rows][B] (any B >= 1), with the row's own centre and scale:
+ *   x_clip = min(max(x, centre - clip_width scale), centre + clip_width scale),  mask = |x - centre| < exclude_width,
+ *   row_stats[row] = {centre, scale, (1/B) sum_b w[row][b] x_clip[row][b], number of mask bits set}.
+ * w: double[n_rows][B] or NULL (all ones).  A row with a non-finite element gets NaN for centre, scale, every clipped value
+ * and the weighted mean; the call returns as for any other input.  x_clip must not alias x. */
+int dqmc_clip_rows(dqmc_ctx* ctx, const double* x, const double* w, int n_rows, int B, int center, int scale, double clip_width,
+                   double exclude_width, double* x_clip, uint8_t* mask, double* row_stats);
+
+#define DQMC_SPIN_NONE 0
+#define DQMC_SPIN_SQUARED 1
+#define DQMC_SPIN_RAISING 2
+/* What dqmc_loss_cotangents reads.  Hats are clipped values, m masks, w the sample weights, *_stats the row_stats of
+ * dqmc_clip_rows called WITH the weights (entry 2 is the weighted mean, entry 3 the mask count). */
+typedef struct dqmc_loss_terms {
+  int S, B;
+  const double* w;           /* [S][B] or NULL (all ones) */
+  const double* e_clip;      /* [S][B] clipped local energies */
+  const uint8_t* e_mask;     /* [S][B] */
+  const double* e_stats;     /* [S][4] */
+  double alpha;
+  const double* r_clip;      /* [S][S][B] clipped ratios, or NULL: no overlap term */
+  const uint8_t* r_mask;     /* [S][S][B] */
+  const double* r_stats;     /* [S*S][4] */
+  const double* scale;       /* [S][S] */
+  const int32_t* rank;       /* [S] device: position of every state in the ordering */
+  int spin_kind;             /* DQMC_SPIN_* */
+  double lambda;
+  const double* spin;        /* [n_states][B]: squared kind: the spin contributions; raising kind: the CLIPPED contributions */
+  const uint8_t* spin_mask;  /* [n_states][B], raising kind */
+  const double* spin_stats;  /* [n_states][4], raising kind */
+  const int32_t* states_host;/* [n_states] HOST: the distinct states the spin rows belong to */
+  int n_states;
+} dqmc_loss_terms;
+/* The cotangent of log|psi_s| on state s's own samples, c[S][B]: the whole loss gradient of state s is
+ * dqmc_log_psi_vjp with cot = c[s] (the raising kind adds a direct term, below).
+ *   energy:   c_sb  = m_sb w_sb (E^_sb - mean_b(E^_s w_s)) / sum_{s,b} m_sb
+ *   overlap:  c_jb += alpha sum_{i: rank(i) < rank(j)} 2 x_ji scale_ij m_ijb (rho^_ijb - x_ij) w_jb / sum_b m_ijb,
+ *             x_ij = mean_b(w_jb rho^_ijb)
+ *   squared:  c_sb += lambda m_sb w_sb (s_sb - mean_b(s_s w_s)) / sum_{s in states, b} m_sb       (m: the energy mask)
+ *   raising:  c_sb += lambda m_sb mu_s w_sb 2 (L^_sb - mu_s) / n,  mu_s = mean_b(L^_s w_s), n = sum_{s in states, b} m_sb
+ *             (m: the mask of the clipped L), and k[q][b] = lambda m_sb mu_s w_sb / n for s = states[q]: the weights of the
+ *             direct term sum_b k_sb dL_sb/dtheta.  k: double[n_states][B], may be NULL.
+ *             Row q of spin / spin_mask / spin_stats belongs to state states[q]. */
+int dqmc_loss_cotangents(dqmc_ctx* ctx, const dqmc_loss_terms* terms, double* c, double* k);
+
 /* psi for B walkers.  r: real[B][N][3], R: real[n_nuc][3]; out logpsi: real[B],
  * sign: int32[B] (values -1, 0, +1; bit-exact item of the parity contract). */
 int dqmc_wf_eval(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logpsi, int32_t* sign);
