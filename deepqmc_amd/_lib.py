@@ -23,6 +23,13 @@ class DqmcLossTerms(ctypes.Structure):
                 ('spin_stats', c_void_p), ('states_host', POINTER(c_int32)), ('n_states', c_int)]
 
 
+class DqmcKfacMap(ctypes.Structure):
+    """dqmc_kfac_map of include/dqmc.h."""
+    _fields_ = [('n_modules', c_int), ('mod', POINTER(c_int64)), ('n_ops', c_int), ('op', POINTER(c_int64)), ('n_maps', c_size_t),
+                ('maps', POINTER(c_int32)), ('n_diag', c_size_t), ('diag_pos', POINTER(c_int64)), ('diag_row', POINTER(c_int64)),
+                ('diag_col', POINTER(c_int64))]
+
+
 # every symbol include/dqmc.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ('dqmc_create', c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(DqmcSystem), POINTER(c_double),
@@ -37,6 +44,11 @@ SIGNATURES = [
     ('dqmc_adam_step', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_double, c_double, c_double, c_double,
                                c_int64, c_void_p]),
     ('dqmc_apply_update', c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
+    ('dqmc_set_kfac_map', c_int, [c_void_p, POINTER(DqmcKfacMap)]),
+    ('dqmc_kfac_state_size', c_int, [c_void_p, POINTER(c_size_t)]),
+    ('dqmc_kfac_direction', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double,
+                                    c_double, c_void_p, c_void_p]),
+    ('dqmc_kfac_apply', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
     ('dqmc_debug_read_weights', c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     ('dqmc_graph_counters', c_int, [c_void_p, POINTER(c_int64)]),
     ('dqmc_psi_ratio', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -7,7 +7,7 @@
 // float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
 // engine_coords.inl, with the force estimators), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
-// step (engine_optim.inl) -- and
+// step (engine_optim.inl), the KFAC preconditioner on its vectors (engine_kfacopt.inl) -- and
 // are included inside the struct body: one translation unit, as before.
 #include <hip/hip_runtime.h>
 
@@ -84,6 +84,11 @@ struct dqmc_ctx {
   virtual int adam_step(double* theta, double* mu, double* nu, const double* g, size_t n, double lr, double b1, double b2, double eps,
                         int64_t t, double* norms3) = 0;
   virtual int apply_update(double* theta, const double* delta, double scale, double* norms3) = 0;
+  virtual int set_kfac_map(const dqmc_kfac_map* m) = 0;
+  virtual int kfac_state_size(size_t* n_doubles) = 0;
+  virtual int kfac_direction(const double* g, const double* factors, const void* rest, const void* logpsi, const int32_t* sign, int B,
+                             double* state, int first, double ema, double damping, double* delta, double* dot) = 0;
+  virtual int kfac_apply(double* theta, const double* delta, const double* dot, double lr, double norm_constraint, double* norms4) = 0;
   virtual int debug_read_weights(int which, void* out, size_t bytes) = 0;
   virtual void graph_counters(int64_t* out2) = 0;
   virtual int psi_ratio(const double* lg, const double* sg, int S, long B, double* ratio) = 0;
@@ -432,6 +437,7 @@ struct Engine : dqmc_ctx {
     if (d_wpk) (void)hipFree(d_wpk);
     if (d_tape) (void)hipFree(d_tape);
     free_optim();
+    free_kfacopt();
   }
 
   int init(const dqmc_system* s, const double* charges, const dqmc_buf* b, int nb, const dqmc_op* o, int no,
@@ -481,6 +487,7 @@ struct Engine : dqmc_ctx {
 #include "engine_coords.inl"
 #include "engine_pretrain.inl"
 #include "engine_optim.inl"
+#include "engine_kfacopt.inl"
 #include "engine_loss.inl"
 };
 
@@ -633,6 +640,27 @@ int dqmc_apply_update(dqmc_ctx* ctx, double* theta, const double* delta, double 
   if (!ctx || !theta || !delta) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->apply_update(theta, delta, scale, norms3);
+}
+int dqmc_set_kfac_map(dqmc_ctx* ctx, const dqmc_kfac_map* map_host) {
+  if (!ctx || !map_host) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->set_kfac_map(map_host);
+}
+int dqmc_kfac_state_size(dqmc_ctx* ctx, size_t* n_doubles) {
+  if (!ctx || !n_doubles) return fail(DQMC_E_ARG, "null argument");
+  return ctx->kfac_state_size(n_doubles);
+}
+int dqmc_kfac_direction(dqmc_ctx* ctx, const double* grad_theta, const double* factors, const void* rest, const void* logpsi,
+                        const int32_t* sign, int B, double* state, int first, double ema, double damping, double* delta, double* dot) {
+  if (!ctx || !grad_theta || !factors || !logpsi || !sign || !state || !delta || !dot) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->kfac_direction(grad_theta, factors, rest, logpsi, sign, B, state, first, ema, damping, delta, dot);
+}
+int dqmc_kfac_apply(dqmc_ctx* ctx, double* theta, const double* delta, const double* dot, double lr, double norm_constraint,
+                    double* norms4) {
+  if (!ctx || !theta || !delta || !dot) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->kfac_apply(theta, delta, dot, lr, norm_constraint, norms4);
 }
 int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t bytes) {
   if (!ctx) return fail(DQMC_E_ARG, "null argument");

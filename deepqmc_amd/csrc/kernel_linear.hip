@@ -1232,4 +1232,5 @@ template void launch_linear_chain<double>(hipStream_t, const LinArgs<double>&);
 #include "kernels_coords.inl"
 #include "kernels_pretrain.inl"
 #include "kernels_optim.inl"
+#include "kernels_kfacopt.inl"
 #include "kernels_loss.inl"

@@ -535,6 +535,46 @@ void launch_adam(hipStream_t st, double* theta, double* mu, double* nu, const do
 // theta += scale * delta; norms3 = 2-norms of theta (before), delta and scale * delta
 void launch_apply_update(hipStream_t st, double* theta, const double* delta, double scale, long n, double* part, double* norms3);
 
+// ---- kernels_kfacopt.inl (included by kernel_linear.hip): the KFAC preconditioner on flat device vectors (dqmc_kfac_direction, dqmc_kfac_apply) ----
+constexpr int KF_NB = 32;     // panel width of the blocked Cholesky factorisation and of the blocked triangular solves
+constexpr int KF_ROWS = 64;   // rows behind a panel per workgroup (one thread each)
+constexpr int KF_RB = 16;     // right-hand sides per workgroup of a triangular solve
+// One Kronecker module: A_hat (da x da, bias = last row) and G_hat (dg x dg) at a_st / g_st of the state (and of the two
+// workspaces M, L, which share the state's layout); its block [W; b] at w_pos (n_in x dg, row-major) and b_pos (-1: none) of a
+// parameter-ordered vector; its ops are op[op0 .. op1).
+struct KfMod { long a_st, g_st, w_pos, b_pos; int da, dg, n_in, R, op0, op1; };
+// One LINEAR op: A_l (d_a x d_a) and G_l (d_g x d_g) at a_off / g_off of the factor buffer; inv[inv_row + i] is the row of A_l
+// that holds row i of the module's A, inv[inv_col + j] the column of G_l that holds column j of its G.
+struct KfOp { long a_off, g_off; int d_a, d_g, inv_row, inv_col; };
+struct KfMat { long ws; int n, pad; };       // a matrix of the factorisation list (sorted by n, descending): offset in M / L
+struct KfTables {
+  const KfMod* mod; const KfOp* op; const int32_t* inv;
+  const long* mat_start;      // [2 n_mod + 1] first state element of A_0, G_0, A_1, ...; the last entry = n_mat_elems
+  const KfMat* mats;          // [2 n_mod]
+  const long* diag_pos;       // [n_diag] parameter element of every diagonal entry
+  const long* diag_row;       // [n_diag + 1] CSR over diag_col
+  const long* diag_col;       // rest columns that hold the copies of an element, ascending
+  int n_mod;
+  long n_diag, n_mat_elems;
+};
+struct KfacDirArgs {
+  KfTables t;
+  const double* g; const double* factors; const void* rest; long n_rest; const void* logpsi; const int32_t* sign; int B;
+  double* state; int first; double ema, damping;
+  double* delta; double* dot;
+  double* M; double* L;       // [n_mat_elems] each
+  double* scal;               // [1 + n_mod]: n_v, pi per module
+  double* part;               // [3][OPT_MAX_BLOCKS]
+  long n_params;
+  int max_n, max_da, max_dg, n_panels;
+  const int* active;          // host, [n_panels + 1]: matrices that have panel k (a prefix of mats)
+};
+// delta must already hold a copy of g; `real` is the type of rest and logpsi
+template <typename real> void launch_kfac_direction(hipStream_t st, const KfacDirArgs& a);
+// theta += -lr min(1, sqrt(norm_constraint / (lr^2 dot))) delta; norms4 (or nullptr) = |theta before|, |delta|, |update|, lr^2 dot
+void launch_kfac_apply(hipStream_t st, double* theta, const double* delta, const double* dot, double lr, double norm_constraint, long n,
+                       double* part, double* norms4);
+
 // ---- kernels_loss.inl (included by kernel_linear.hip): loss assembly of multi-state training (dqmc_psi_ratio, dqmc_clip_rows, dqmc_loss_cotangents) ----
 constexpr int LOSS_BLOCK = 256;          // threads per workgroup = bins of a radix-select pass; one workgroup per row
 constexpr int LOSS_MAX_STATES = 32;      // electronic states of a batch at most

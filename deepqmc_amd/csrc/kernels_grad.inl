@@ -96,7 +96,11 @@ __global__ void __launch_bounds__(64) k_lin_dw(const real* __restrict__ X, int l
       const int rr = (int)(m - b * nrows);
       if (kk < K) a = X ? X[(b * rpw + r0 + (bcast ? 0 : rr)) * ld + kk] : (real)1;
       if (n < ldw) bv = dZ[m * ldw + n];
-      if (wt) { const double w = wt[b]; bv = w == 0 ? (real)0 : (real)((double)bv * w); }
+      if (wt) {      // a walker of weight 0 contributes exactly nothing, whatever its inputs hold (a NaN coordinate makes X NaN)
+        const double w = wt[b];
+        bv = w == 0 ? (real)0 : (real)((double)bv * w);
+        if (w == 0) a = 0;
+      }
     }
     acc = Mfma<real>::run(a, bv, acc);
   }

@@ -212,6 +212,120 @@ class Engine:
                                                norms.data_ptr() if norms is not None else None))
         self.params_ahead, self._theta_ref = True, theta
 
+    # ---- KFAC preconditioner on the flat device vectors (dqmc_set_kfac_map, dqmc_kfac_direction, dqmc_kfac_apply) ----
+    KFAC_PANEL = 32     # DQMC_KFAC_PANEL: panel width of the blocked Cholesky factorisation and triangular solves
+
+    def _kfac_tables(self):
+        """The host tables of dqmc_set_kfac_map from Program.kfac_blocks / kfac_layout / leaf_slices and loss._rest_gather,
+        and the layout of the state they imply."""
+        from .loss import _rest_gather
+        prog = self.program
+        blocks, _ = prog.kfac_blocks()
+        lay = prog.kfac_layout()
+        sl = prog.leaf_slices()
+        mod, op, maps, n_maps = [], [], [], 0
+        layout = {'modules': {}, 'diag': None}
+        off = 0
+        for name, blk in blocks.items():
+            da, dg = blk['n_in'] + int(blk['has_bias']), blk['n_out']
+            b_pos = sl[(name, 'b')][0].start if blk['has_bias'] else -1
+            mod.append([blk['n_in'], blk['n_out'], int(blk['has_bias']), blk['R'], sl[(name, 'w')][0].start, b_pos, len(op), len(blk['ops'])])
+            for q, rows, cols in zip(blk['ops'], blk['rows'], blk['cols']):
+                o = lay['ops'][q]
+                op.append([o['a_off'], o['g_off'], o['d_a'], o['d_g'], n_maps, n_maps + len(rows)])
+                maps += [np.asarray(rows, np.int32), np.asarray(cols, np.int32)]
+                n_maps += len(rows) + len(cols)
+            layout['modules'][name] = {'A': (off, da), 'G': (off + da * da, dg)}
+            off += da * da + dg * dg
+        elems = np.concatenate([np.arange(base, base + int(np.prod(shape))) for (m, _), (base, shape) in prog.grad_leaves.items()
+                                if m not in blocks] or [np.zeros(0, np.int64)]).astype(np.int64)
+        row = np.zeros(elems.size + 1, np.int64)
+        col = np.zeros(0, np.int64)
+        if elems.size:
+            tabs = np.stack(_rest_gather(prog, elems), 1) if prog._jacobian_gather() else np.zeros((elems.size, 0), np.int64)
+            row[1:] = np.cumsum((tabs >= 0).sum(1))
+            col = tabs[tabs >= 0].astype(np.int64)        # row-major: per element, ascending multiplicity = ascending column
+        layout['diag'] = (off, int(elems.size))
+        layout['diag_elems'] = elems
+        layout['size'] = off + int(elems.size)
+        tabs = dict(mod=np.ascontiguousarray(np.asarray(mod, np.int64).reshape(-1, 8)), op=np.ascontiguousarray(np.asarray(op, np.int64).reshape(-1, 6)),
+                    maps=np.ascontiguousarray(np.concatenate(maps or [np.zeros(0, np.int32)]).astype(np.int32)),
+                    diag_pos=np.ascontiguousarray(elems), diag_row=row, diag_col=np.ascontiguousarray(col))
+        return tabs, layout
+
+    def _ensure_kfac_map(self):
+        """Upload the KFAC tables on first use (dqmc_set_kfac_map), after the parameter map."""
+        self._ensure_param_map()
+        if not self.__dict__.get('_kfac_map_set', False):
+            self.set_kfac_tables(*self._kfac_tables())
+
+    def set_kfac_tables(self, tabs, layout):
+        """Install explicit tables (the dict and layout of _kfac_tables) with dqmc_set_kfac_map: what _ensure_kfac_map does with
+        the program's own tables; tests use it with tables of their own."""
+        self._ensure_param_map()
+        m = _lib.DqmcKfacMap()
+        p64 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        m.n_modules, m.mod, m.n_ops, m.op = tabs['mod'].shape[0], p64(tabs['mod']), tabs['op'].shape[0], p64(tabs['op'])
+        m.n_maps, m.maps = tabs['maps'].size, tabs['maps'].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        m.n_diag, m.diag_pos, m.diag_row, m.diag_col = tabs['diag_pos'].size, p64(tabs['diag_pos']), p64(tabs['diag_row']), p64(tabs['diag_col'])
+        self._check(self.lib.dqmc_set_kfac_map(self._ctx, ctypes.byref(m)))
+        n = ctypes.c_size_t()
+        self._check(self.lib.dqmc_kfac_state_size(self._ctx, ctypes.byref(n)))
+        assert n.value == layout['size'], (n.value, layout['size'])
+        self._kfac_layout, self._kfac_map_set = layout, True
+
+    def kfac_state_layout(self):
+        """The layout of the caller-owned state of kfac_direction (dqmc_kfac_state_size doubles): {'modules': {module:
+        {'A': (offset, dim), 'G': (offset, dim)}} in Program.kfac_blocks order (row-major dim x dim matrices, the bias the last
+        row of A), 'diag': (offset, n) the F of the elements outside the modules, 'diag_elems': their positions in theta,
+        'size'}."""
+        self._ensure_kfac_map()
+        return self._kfac_layout
+
+    def kfac_state(self):
+        """A new state vector for kfac_direction (zeros; a call with first=True overwrites it)."""
+        return torch.zeros(self.kfac_state_layout()['size'], dtype=torch.float64, device=self.device)
+
+    def kfac_direction(self, grad_theta, factors_buf, rest, logpsi, sign, state, first, ema, damping, out=None):
+        """The KFAC-preconditioned direction of loss.compute_energy_loss_and_kfac on the device (dqmc_kfac_direction):
+        grad_theta float64 [n_params] (grad_to_params); factors_buf, rest, logpsi, sign as log_psi_kfac wrote them
+        (factors_buf: the flat factor buffer); state: float64 [kfac_state_layout()['size']], updated in place (first: it is
+        overwritten, not mixed).  Returns (delta [n_params], dot [1] = <delta, grad_theta>), float64 device tensors; `out`:
+        preallocated (delta, dot).  Nothing waits for the host."""
+        self._ensure_kfac_map()
+        lay = self.program.kfac_layout()
+        n = self.program.n_params()
+        self._theta_arg('grad_theta', grad_theta)
+        self._theta_arg('factors_buf', factors_buf, lay['n_factor_doubles'])
+        self._theta_arg('state', state, self._kfac_layout['size'])
+        B = logpsi.shape[0]
+        if logpsi.dtype != self.dtype or not logpsi.is_contiguous() or sign.dtype != torch.int32 or sign.shape[0] != B or not sign.is_contiguous():
+            raise DqmcError(f"'logpsi' must be a contiguous {self.dtype} vector and 'sign' an int32 vector of the same length")
+        if rest is not None and (rest.dtype != self.dtype or tuple(rest.shape) != (B, lay['n_rest']) or not rest.is_contiguous()):
+            raise DqmcError(f"'rest' must be a contiguous [{B}, {lay['n_rest']}] {self.dtype} tensor")
+        delta, dot = out if out is not None else (torch.empty(n, dtype=torch.float64, device=self.device),
+                                                  torch.empty(1, dtype=torch.float64, device=self.device))
+        self._theta_arg('delta', delta)
+        self._theta_arg('dot', dot, 1)
+        self._check(self.lib.dqmc_kfac_direction(self._ctx, grad_theta.data_ptr(), factors_buf.data_ptr(),
+                                                 rest.data_ptr() if rest is not None else None, logpsi.data_ptr(), sign.data_ptr(), B,
+                                                 state.data_ptr(), int(bool(first)), float(ema), float(damping), delta.data_ptr(),
+                                                 dot.data_ptr()))
+        return delta, dot
+
+    def kfac_apply(self, theta, delta, dot, lr, norm_constraint, norms=None):
+        """theta += -lr min(1, sqrt(norm_constraint / (lr^2 dot))) delta on the device, then the re-pack (dqmc_kfac_apply);
+        norms: optional float64 [4] receiving (param, direction, update) 2-norms and lr^2 dot."""
+        self._ensure_param_map()
+        self._theta_arg('theta', theta)
+        self._theta_arg('delta', delta)
+        self._theta_arg('dot', dot, 1)
+        if norms is not None:
+            self._theta_arg('norms', norms, 4)
+        self._check(self.lib.dqmc_kfac_apply(self._ctx, theta.data_ptr(), delta.data_ptr(), dot.data_ptr(), float(lr),
+                                             float(norm_constraint), norms.data_ptr() if norms is not None else None))
+        self.params_ahead, self._theta_ref = True, theta
+
     def debug_read_weights(self, which: int):
         """Raw bytes (np.uint8) of a weight buffer of the context (dqmc_debug_read_weights): 0 flat weights, 1 the sub-step
         kernel's tape, 2 the fused kernel's planes, 3 the float64 twin's flat weights.  None if the context has no such buffer."""

@@ -276,7 +276,7 @@ def _rest_gather(prog, elems):
 
 
 def compute_energy_loss_and_kfac(rng, hamil, ansatz, params: Sequence, phys_conf, state=None, damping=1e-3, ema=0.95, weight=None,
-                                 clip_mask_fn=median_clip_and_mask):
+                                 clip_mask_fn=median_clip_and_mask, flat: bool = False):
     """compute_energy_loss_and_grad preconditioned by KFAC (Kronecker-factored approximate curvature of the Fisher matrix of
     log|psi|), one dqmc_log_psi_kfac call per state.  With n_v valid walkers (sign != 0, finite log|psi|) and, per module of
     Program.kfac_blocks, R_mod the rows per walker of its ops:
@@ -290,11 +290,21 @@ def compute_energy_loss_and_kfac(rng, hamil, ansatz, params: Sequence, phys_conf
     may, for instance, scale G by a constant of its predictive distribution.
     Returns (loss, [delta tree per state], stats, state): stats as compute_energy_loss_and_grad's plus 'grad' (the gradient
     trees) and 'precon_grad_dot' = [<delta_s, g_s>] (what the reference's norm constraint needs); state = one dict of factors
-    per electronic state, to pass to the next call.  Single process only: the factors of other ranks are not summed."""
+    per electronic state, to pass to the next call.  Single process only: the factors of other ranks are not summed.
+    flat=True: the same arithmetic on the device (Engine.kfac_direction): the deltas and 'grad' are float64 device vectors in
+    parameter order, 'precon_grad_dot' is a device tensor [S], and `state` is one float64 device tensor per electronic
+    state (Engine.kfac_state_layout) that is updated in place; nothing of the call waits for the host."""
     if not damping > 0:
         raise ValueError('damping must be positive')
     r, Rs, loss, cots, masks, stats = _energy_loss_cotangents('compute_energy_loss_and_kfac', rng, hamil, ansatz, params, phys_conf,
-                                                             weight, clip_mask_fn)
+                                                             weight, clip_mask_fn, static_io=flat)
+    if flat:
+        return _kfac_directions_flat(ansatz, params, r, Rs, loss, cots, stats, state, damping, ema)
+    return _kfac_directions_tree(ansatz, params, r, Rs, loss, cots, stats, state, damping, ema)
+
+
+def _kfac_directions_tree(ansatz, params, r, Rs, loss, cots, stats, state, damping, ema):
+    """The body of compute_energy_loss_and_kfac(flat=False) for given cotangents c_s: host trees, torch Cholesky per module."""
     S = len(cots)
     state = list(state) if state is not None else [None] * S
     if len(state) != S:
@@ -357,6 +367,37 @@ def compute_energy_loss_and_kfac(rng, hamil, ansatz, params: Sequence, phys_conf
         dots.append(sum(float(np.sum(delta[m][k] * gtree[m][k])) for m in gtree for k in gtree[m]))
     stats['grad'] = gs
     stats['precon_grad_dot'] = torch.tensor(dots, dtype=torch.float64)
+    return loss, deltas, stats, state
+
+
+def _kfac_directions_flat(ansatz, params, r, Rs, loss, cots, stats, state, damping, ema):
+    """compute_energy_loss_and_kfac(flat=True) for given cotangents c_s (the penalties of create_loss_fn enter through c_s
+    only; the factors are those of the unit cotangent either way).  state: None or a list with, per electronic state, None
+    (first call) or the device tensor of the last call."""
+    S = len(cots)
+    state = list(state) if state is not None else [None] * S
+    if len(state) != S:
+        raise ValueError('state holds the factors of a different number of states')
+    deltas, gs, dots = [], [], []
+    for s, cot in enumerate(cots):
+        pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
+        if eng.program.grad_unsupported:
+            raise NotImplementedError(f'compute_energy_loss_and_kfac: unsupported for this program ({eng.program.grad_unsupported})')
+        lay = eng.program.kfac_layout()
+        rr = r[0, s].contiguous()
+        fac = torch.empty(lay['n_factor_doubles'], dtype=torch.float64, device=eng.device)
+        rest = torch.empty(rr.shape[0], lay['n_rest'], dtype=eng.dtype, device=eng.device)
+        sign, logpsi, g, _, rest = eng.log_psi_kfac(rr, cot.to(eng.dtype).to(eng.device).contiguous(), Rs[0], out=(fac, rest))
+        gt = eng.grad_to_params(g)
+        first = state[s] is None
+        if first:
+            state[s] = eng.kfac_state()
+        delta, dot = eng.kfac_direction(gt, fac, rest, logpsi, sign, state[s], first, ema, damping)
+        deltas.append(delta)
+        gs.append(gt)
+        dots.append(dot)
+    stats['grad'] = gs
+    stats['precon_grad_dot'] = torch.cat(dots)
     return loss, deltas, stats, state
 
 

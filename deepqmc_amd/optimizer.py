@@ -11,15 +11,39 @@ context stays valid.  The parameter TREES handed to `step` are returned as the s
 steps and when it ends).
 
 `batch` = `(phys_conf, weight)` or `(phys_conf, weight, data)` as in the reference: phys_conf r[1, S, B, N, 3] or a
-PhysicalConfiguration of it, weight [1, S, B] or None.  KFAC directions stay tree-based (loss.compute_energy_loss_and_kfac).
+PhysicalConfiguration of it, weight [1, S, B] or None.  KFACOptimizer forms its direction on the device as well
+(loss.compute_energy_loss_and_kfac(..., flat=True), dqmc_kfac_direction / dqmc_kfac_apply); the tree-based KFAC direction
+(flat=False) remains for host-side use.
 """
 from __future__ import annotations
 
 import torch
 
-from .loss import _natgrad_directions, _unpack, compute_energy_loss_and_grad, compute_energy_loss_and_natgrad, compute_local_energy, median_clip_and_mask
+from .loss import (_kfac_directions_flat, _natgrad_directions, _unpack, compute_energy_loss_and_grad, compute_energy_loss_and_kfac,
+                   compute_energy_loss_and_natgrad, compute_local_energy, median_clip_and_mask)
 
-__all__ = ['NoOptimizer', 'AdamOptimizer', 'NaturalGradientOptimizer', 'merge_states_flat']
+__all__ = ['NoOptimizer', 'AdamOptimizer', 'NaturalGradientOptimizer', 'KFACOptimizer', 'InverseSchedule', 'ConstantSchedule',
+           'merge_states_flat']
+
+
+class InverseSchedule:
+    """optimizer.py (reference): init_value / (1 + n / decay_rate) at step count n."""
+
+    def __init__(self, init_value, decay_rate):
+        self.init_value, self.decay_rate = init_value, decay_rate
+
+    def __call__(self, n):
+        return self.init_value / (1 + n / self.decay_rate)
+
+
+class ConstantSchedule:
+    """The same value at every step count."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __call__(self, n):
+        return self.value
 
 
 class _Optimizer:
@@ -151,6 +175,64 @@ class NaturalGradientOptimizer(_Optimizer):
         e_loc = stats.pop('E_loc')
         stats.pop('grad', None)
         return params, opt_state, e_loc, ratios, {**self._opt_stats(opt_state), **extra, **stats}
+
+
+class KFACOptimizer(_Optimizer):
+    """The reference's default optimiser (conf/task/opt/kfac.yaml: kfac_jax with learning rate InverseSchedule(0.05, 10000),
+    norm_constraint 1e-3, damping 1e-3, inverse_update_period 1, momentum 0) on the flat device vectors: the direction of
+    loss.compute_energy_loss_and_kfac (its docstring is the definition) formed by dqmc_kfac_direction with the factors in a
+    device state, and theta <- theta - lr min(1, sqrt(norm_constraint / (lr^2 <delta, g>))) delta applied by
+    dqmc_kfac_apply.  `learning_rate` and `damping` may be callables of the count of steps taken so far.  State per electronic
+    state: {'theta', 'kfac' (the factor state, Engine.kfac_state_layout), 'count', 'norms' [4]}.  Stats: 'opt/param_norm',
+    'opt/grad_norm' (the norm of the preconditioned direction, as the reference reports), 'opt/update_norm' and
+    'opt/scaled_grad_norm_sq' = lr^2 <delta, g>.  Momentum, adaptive damping and an inverse_update_period other than 1 are
+    not implemented; single process, one molecule per batch."""
+
+    def __init__(self, learning_rate=InverseSchedule(0.05, 10000), norm_constraint=1e-3, damping=1e-3, ema=0.95, **kw):
+        super().__init__(**kw)
+        self.lr, self.norm_constraint, self.damping, self.ema = learning_rate, norm_constraint, damping, ema
+        if self.loss_fn is not None and self.loss_fn.spin_penalty is not None and self.loss_fn.spin_penalty_type == 'raising':
+            raise NotImplementedError("KFACOptimizer: the 'raising' spin penalty has a direct term that is not a "
+                                      'contraction with the Jacobian of log|psi|')
+
+    def init(self, rng, params, batch):
+        state = self._new_state(params, batch, moments=False)
+        for st in state:
+            st['kfac'] = None          # allocated by the first step (Engine.kfac_state), which overwrites it
+            st['norms'] = torch.zeros(4, dtype=torch.float64, device=st['theta'].device)
+        return state
+
+    def step(self, rng, params, opt_state, batch):
+        phys_conf, weight = self._batch(batch)
+        ratios, extra = None, {}
+        count = opt_state[0]['count']
+        damping = self.damping(count) if callable(self.damping) else self.damping
+        kstate = [st['kfac'] for st in opt_state]
+        if self.loss_fn is not None:
+            # the cotangent of the whole loss enters the reverse pass; the factors are those of the unit cotangent either way
+            v, c, _ = self.loss_fn.loss_and_cotangents(rng, params, batch, static_io=True)
+            ratios, extra = v['psi_ratio'], {'loss': v['loss']}
+            if not damping > 0:
+                raise ValueError('damping must be positive')
+            _, deltas, stats, kstate = _kfac_directions_flat(self.ansatz, params, v['r'], v['Rs'], v['loss'], list(c), dict(v['stats']),
+                                                             kstate, damping, self.ema)
+        else:
+            _, deltas, stats, kstate = compute_energy_loss_and_kfac(rng, self.hamil, self.ansatz, params, phys_conf, kstate, damping,
+                                                                    self.ema, weight, self.clip_mask_fn, flat=True)
+        dots = stats['precon_grad_dot']
+        for s, (eng, st, d) in enumerate(zip(self._engines(params, phys_conf), opt_state, deltas)):
+            lr = self.lr(st['count']) if callable(self.lr) else self.lr
+            st['kfac'] = kstate[s]
+            eng.kfac_apply(st['theta'], d, dots[s:s + 1], lr, self.norm_constraint, norms=st['norms'])
+            st['count'] += 1
+        stats = dict(stats)
+        e_loc = stats.pop('E_loc')
+        stats.pop('grad', None)
+        stats.pop('precon_grad_dot', None)
+        norms = torch.stack([st['norms'] for st in opt_state])
+        opt = {'opt/param_norm': norms[:, 0], 'opt/grad_norm': norms[:, 1], 'opt/update_norm': norms[:, 2],
+               'opt/scaled_grad_norm_sq': norms[:, 3]}
+        return params, opt_state, e_loc, ratios, {**opt, **extra, **stats}
 
 
 def merge_states_flat(ansatz, params, opt_state, merge_keys, phys_conf=None):

@@ -184,6 +184,59 @@ int dqmc_adam_step(dqmc_ctx* ctx, double* theta, double* mu, double* nu, const d
 /* theta += scale * delta (both double[n_params]), then dqmc_weights_from_params(theta): the entry point for directions
  * formed elsewhere on the device (natural gradient).  norms3 as above: theta before the step, delta, scale * delta. */
 int dqmc_apply_update(dqmc_ctx* ctx, double* theta, const double* delta, double scale, double* norms3);
+/* ---- KFAC preconditioner on the flat device vectors ----
+ * The join between dqmc_log_psi_kfac and the device-resident optimiser step: the direction
+ *   A_hat = sum_l A_l / (n_v R_mod),  G_hat = sum_l G_l / n_v      (per module, scattered through the row / column maps)
+ *   F <- ema F_old + (1 - ema) F_new                               (first != 0: F_new)
+ *   pi = sqrt((tr A_hat / dim A_hat) / (tr G_hat / dim G_hat))
+ *   delta[W; b] = (A_hat + pi sqrt(damping) I)^-1 [g_W; g_b] (G_hat + sqrt(damping) / pi I)^-1
+ *   diagonal elements:  F_ii = sum_b o_bi^2 / n_v (same EMA),  delta_i = g_i / (F_ii + damping)
+ * is formed in float64 (also in a float32 context) by fixed-order reductions and a blocked Cholesky factorisation (panel
+ * width DQMC_KFAC_PANEL) with triangular solves; there are no atomics and identical calls are bit-identical.  A factor that is
+ * not positive definite (it can only be so when it is not finite) turns that module's part of delta into NaN.
+ *
+ * dqmc_set_kfac_map: host tables that say where a module's factors, gradient and diagonal partials live (a setup call: it
+ * synchronises and allocates the workspace of the later calls; it needs dqmc_set_param_map first).
+ *   mod   int64[n_modules][8]: n_in, n_out, has_bias, R (rows per walker of its ops), first element of w ([n_in][n_out]
+ *         row-major) in theta, of b ([n_out], -1 without a bias), its first op in `op`, its number of ops
+ *   op    int64[n_ops][6]: offsets of A_l and G_l in the factor buffer, d_A, d_G (dqmc_kfac_layout), the first entry in `maps`
+ *         of its row map (d_A entries: the row of the module's A, the bias row being n_in, or -1 for padding) and of its column
+ *         map (d_G entries: the column of the module's G or -1); every map is a permutation onto the module's rows / columns
+ *   diag_pos  int64[n_diag] the parameter elements outside the modules; diag_row int64[n_diag + 1], diag_col: CSR of the
+ *         rest columns that hold an element's copies (they are summed in the order given: ascending)
+ * DQMC_E_ARG for tables that are inconsistent with each other, with the factor layout or with the parameter map (every
+ * parameter element has to be covered exactly once); DQMC_E_UNSUPPORTED where dqmc_log_psi_kfac is.
+ * dqmc_kfac_state_size: the doubles of the caller-owned state: per module A_hat (d x d, d = n_in + has_bias) then G_hat
+ * (n_out x n_out), row-major, in the order of `mod`; then F of the diagonal elements, in the order of diag_pos.
+ * dqmc_kfac_direction: all pointers are device memory.  grad_theta double[n_params] (dqmc_grad_to_params); factors, rest,
+ * logpsi, sign exactly as dqmc_log_psi_kfac wrote them for B walkers (rest and logpsi in the context's precision; n_v is
+ * counted from sign and logpsi on the device); state as above, read unless first != 0, and written; damping > 0;
+ * delta double[n_params] and dot[1] = <delta, grad_theta> are written.
+ * dqmc_kfac_apply: theta += -lr coeff delta with coeff = min(1, sqrt(norm_constraint / (lr^2 dot[0]))) -- the norm
+ * constraint of kfac_jax with momentum 0; coeff = 1 when norm_constraint <= 0 or dot[0] <= 0 -- evaluated on the device,
+ * then dqmc_weights_from_params(theta).  norms4: double[4] or NULL = the 2-norms of theta before the step, of delta and of
+ * the update, and lr^2 dot[0].
+ * dqmc_kfac_direction and dqmc_kfac_apply only enqueue kernels on the context's stream: no synchronisation, no host memory
+ * traffic, no allocation, and captured forward-Laplacian graphs stay valid. */
+#define DQMC_KFAC_PANEL 32
+typedef struct dqmc_kfac_map {
+  int n_modules;
+  const int64_t* mod;
+  int n_ops;
+  const int64_t* op;
+  size_t n_maps;
+  const int32_t* maps;
+  size_t n_diag;
+  const int64_t* diag_pos;
+  const int64_t* diag_row;
+  const int64_t* diag_col;
+} dqmc_kfac_map;
+int dqmc_set_kfac_map(dqmc_ctx* ctx, const dqmc_kfac_map* map_host);
+int dqmc_kfac_state_size(dqmc_ctx* ctx, size_t* n_doubles);
+int dqmc_kfac_direction(dqmc_ctx* ctx, const double* grad_theta, const double* factors, const void* rest, const void* logpsi,
+                        const int32_t* sign, int B, double* state, int first, double ema, double damping, double* delta, double* dot);
+int dqmc_kfac_apply(dqmc_ctx* ctx, double* theta, const double* delta, const double* dot, double lr, double norm_constraint,
+                    double* norms4);
 /* Test access to the weight buffers.  which: 0 = the flat weights in the context's precision, 1 = the weight tape of the
  * generated sub-step kernel, 2 = the packed planes of the fused kernel, 3 = the flat weights of the float64 twin.
  * out_host NULL: returns the size of the buffer in bytes (> 0).  Otherwise `bytes` must be exactly that size (DQMC_E_ARG);
