@@ -1,8 +1,9 @@
 // engine.hip -- the C ABI of include/dqmc.h: context, layer-program executor, MCMC driver,
 // per-kernel timing.  Host code only; every arithmetic step is one of the kernels in
 // kernel_linear.hip / kernels_graph.hip / kernels_head.hip / kernels_mcmc.hip.
-// This file: the context base, the state of Engine<real> (members, options' storage, captured-graph bookkeeping), and
-// the extern "C" entry points.  The member functions live in engine_*.inl by concern -- program analyses
+// This file: DevBuf, the one type that owns device memory here (every allocation of a context is a DevBuf member and is
+// released by it), the context base, the state of Engine<real> (members, options' storage, captured-graph bookkeeping),
+// and the extern "C" entry points.  The member functions live in engine_*.inl by concern -- program analyses
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
 // float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
@@ -53,10 +54,56 @@ struct TimingRec {
                           // lanes padded to TP, widths padded to 4 (matrix-pipe utilisation = this / time / peak)
 };
 
+// One device allocation and its capacity in elements, released with its owner.  Converts to T*, so argument structs, launches
+// and pointer arithmetic read as with a raw pointer, and `if (!buf)` asks whether it holds anything.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  operator T*() const { return p; }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+  }
+  hipError_t alloc(size_t n) {      // into the empty buffer; p and cap change on success only
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, sizeof(T) * n);
+    if (e == hipSuccess) { p = static_cast<T*>(q); cap = n; }
+    return e;
+  }
+  // exactly n elements in a fresh block (a table that a setup call replaces; the caller has synchronised what may read the old one)
+  int assign(size_t n) {
+    reset();
+    HIP_TRY(alloc(n));
+    return DQMC_OK;
+  }
+  int upload(const T* host, size_t n) {      // assign + blocking copy
+    const int rc = assign(n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(p, host, sizeof(T) * n, hipMemcpyHostToDevice));
+    return DQMC_OK;
+  }
+  // at least n elements, grow-only and exact: a call that fits performs no allocation and keeps the pointer; one that does not
+  // drains `st` (a kernel in flight may read the old block), and a failed growth leaves (nullptr, 0), never a stale capacity.
+  // With `what` the failure is DQMC_E_NOMEM "<what> of <bytes> bytes: ...", without it the DQMC_E_HIP of HIP_TRY.
+  int reserve(size_t n, hipStream_t st, const char* what = nullptr) {
+    if (n <= cap) return DQMC_OK;
+    if (p) { HIP_TRY(hipStreamSynchronize(st)); reset(); }
+    if (!what) HIP_TRY(alloc(n));
+    else if (const hipError_t e = alloc(n); e != hipSuccess)
+      return fail(DQMC_E_NOMEM, std::string(what) + " of " + std::to_string(sizeof(T) * n) + " bytes: " + hipGetErrorString(e));
+    return DQMC_OK;
+  }
+};
+
 }  // namespace
 
 struct dqmc_ctx {
-  virtual ~dqmc_ctx() { if (d_gather) (void)hipFree(d_gather); }
+  virtual ~dqmc_ctx() = default;
   virtual int set_weights(const double* w, size_t n) = 0;
   virtual int wf_eval(const void* r, const void* R, int B, void* logpsi, int32_t* sign) = 0;
   virtual int local_energy(const void* r, const void* R, int B, void* e_loc, void* stats, void* grad, void* logpsi,
@@ -125,8 +172,7 @@ struct dqmc_ctx {
   int64_t ecp_last_counts[3] = {0, 0, 0};   // (nucleus, electron) pairs of the last mixed-precision quadrature: float32, float64, dropped
   int last_chunks[2] = {0, 0};   // walker chunks of the last Laplacian-mode evaluation: this context's own pass, its float64 twin's (max over its passes)
   int device = 0;           // every entry point makes this the calling thread's current device
-  double* d_gather = nullptr;   // all-gathered energy records (dqmc_energy_stats_allgather)
-  size_t gather_cap = 0;
+  DevBuf<double> d_gather;      // all-gathered energy records (dqmc_energy_stats_allgather)
   // timing
   bool timing = false;
   std::map<std::string, TimingRec> trec;
@@ -178,32 +224,29 @@ struct Engine : dqmc_ctx {
   std::vector<double> charges_h;
   size_t n_weights = 0, n_itable = 0;
   std::vector<int32_t> h_itable;
-  real* d_w = nullptr;
-  int32_t* d_it = nullptr;
-  double* d_charges = nullptr;
+  DevBuf<real> d_w;
+  DevBuf<int32_t> d_it;
+  DevBuf<double> d_charges;
   // workspace
-  char* d_ws = nullptr;
-  size_t ws_bytes = 0;
+  DevBuf<char> d_ws;
   std::vector<size_t> buf_off;  // byte offsets for the current (B, TP)
   size_t off_logdet = 0, off_signk = 0, off_z = 0, off_cond = 0, off_kappa = 0;
   int split_bcast = 1;           // option "split_bcast": per-walker pieces of a linear layer multiplied once per walker
   int last_B = 0;
   // mcmc scratch
-  char* d_mc = nullptr;
-  size_t mc_bytes = 0;
-  int32_t* d_nacc = nullptr;
-  void* d_tau_ring = nullptr;   // real[2]: step sizes of the last two one-launch sub-steps
-  double* d_acc = nullptr;     // [1] acceptance, then [7] stats, then [7] energy record
+  DevBuf<char> d_mc;
+  DevBuf<int32_t> d_nacc;
+  DevBuf<double> d_tau_ring;    // holds real[2]: step sizes of the last two one-launch sub-steps
+  DevBuf<double> d_acc;        // [1] acceptance, then [7] stats, then [7] energy record
   std::vector<real> wtmp;
   // fused value-only plan
   int fused_enabled = 1;      // 0 off, 1 where it is the faster value path (fused_pays), 2 always
   int fused_n_ops = 0, fused_wt_req = 0, fused_dbg = 0, fused_sched_mode = 3, fused_occ_req = 0;
-  size_t wpk_cap = 0;
   std::vector<int> f_order, f_level;   // fused schedule: op index and dependency level per slot
-  dqmc_op* d_ops = nullptr;
-  int32_t* d_wpk_off = nullptr;   // per scheduled op: {packed-weight offset, barrier-after flag}
-  real* d_wpk = nullptr;
-  long long* d_prof = nullptr;
+  DevBuf<dqmc_op> d_ops;
+  DevBuf<int32_t> d_wpk_off;      // per scheduled op: {packed-weight offset, barrier-after flag}
+  DevBuf<real> d_wpk;            // cap counts reals
+  DevBuf<long long> d_prof;
   // pair-compact edge buffers (common.h: PAIR_LANES): which buffers carry 8 lanes in Laplacian mode, and the
   // (receiver, sender) of each of their rows (for the lane maps of debug_read)
   size_t ws_budget = (size_t)32 << 30;   // activation workspace per evaluation chunk (option "ws_budget_mb"); several contexts
@@ -253,15 +296,14 @@ struct Engine : dqmc_ctx {
   std::vector<std::vector<dqmc::FDesc>> plan_lists;   // the four wave lists (kept for "fused_print")
   // plan-specialised sub-step kernel (csrc/gen/*.hip, spec_device.h): found by the hash of the program; its weight tape
   const dqmc::SpecKernel* spec_k = nullptr;
-  uint32_t* d_tape = nullptr;
+  DevBuf<uint32_t> d_tape;
   int fused_spec = 1;            // option "fused_spec": 0 = always the descriptor-driven kernel
-  dqmc::FDesc* d_descs = nullptr;
-  int32_t* d_wave_begin = nullptr;
-  dqmc::FusedBuf* d_fbufs2 = nullptr;
+  DevBuf<dqmc::FDesc> d_descs;
+  DevBuf<int32_t> d_wave_begin;
+  DevBuf<dqmc::FusedBuf> d_fbufs2;
   // effective core potential (dqmc_set_ecp): local terms for k_final, non-local channels per nucleus
-  double* d_ecp_loc = nullptr;
-  double* d_ecp_nl = nullptr;
-  int32_t* d_ecp_nuc = nullptr;
+  DevBuf<double> d_ecp_loc, d_ecp_nl;
+  DevBuf<int32_t> d_ecp_nuc;
   int ecp_nt_loc = 0, ecp_n_nl = 0, ecp_L = 0, ecp_nt_nl = 0;
   uint64_t ecp_seed = 0;
   const void* ecp_phi = nullptr;
@@ -269,8 +311,7 @@ struct Engine : dqmc_ctx {
   bool ecp_phi_f32 = false;
   std::vector<double> ecp_nl_h;       // host copy of the non-local tables for the float64 twin
   int ecp_nl_L_h = 0, ecp_nl_nt_h = 0;
-  char* d_ecp = nullptr;        // quadrature walkers + their psi + psi of the walkers themselves
-  size_t ecp_bytes = 0;
+  DevBuf<char> d_ecp;           // quadrature walkers + their psi + psi of the walkers themselves
   // mixed-precision quadrature of a float32 context (ecp_mixed): "ecp_mixed" 1 (default) with "refine" 1; a triple whose
   // weight w = max_l (2l+1)|V_l| exceeds ecp_w_heavy ("ecp_heavy_e6", in 1e-6 Ha) gets float64 psi ratios, one below
   // ecp_w_skip ("ecp_skip_e12", in 1e-12 Ha) is dropped
@@ -284,8 +325,7 @@ struct Engine : dqmc_ctx {
   // weights alone 1.2e-5 (one walker beyond the tolerance) / 1.7e-6; floor 1e-4: 9.8e-6 / 1.7e-6 at + 0.6 %; floor 3e-5:
   // 3.5e-6 / 5.9e-7 at + 3 % -- the same as tightening "ecp_heavy_e6" to 3e-3 at + 6 %.
   double ecp_dlog_floor = 3e-5;
-  char* d_ecpm = nullptr;
-  size_t ecpm_bytes = 0;
+  DevBuf<char> d_ecpm;
   size_t ecp_max_cfg = 1 << 16; // quadrature walkers per value-mode batch
   // float64 refinement (float32 build): walkers flagged by k_final as ill conditioned (near a node of psi the kinetic
   // energy is a difference of huge numbers and float32 round-off is amplified by the CI cancellation) are
@@ -345,7 +385,7 @@ struct Engine : dqmc_ctx {
   std::vector<PassGraph> pgraphs;
   uint64_t graph_epoch = 0, graph_clock = 0, graph_captures = 0, graph_hits = 0;
   std::vector<int> graph_warm;          // batch sizes that have run eagerly
-  double* d_thresh = nullptr;           // device copy of refine_thresh (read by k_final: graphs must not bake it in)
+  DevBuf<double> d_thresh;              // device copy of refine_thresh (read by k_final: graphs must not bake it in)
   double thresh_uploaded = -1.0;
   bool graphs_active() const {
     return pass_graph && !graph_broken && !timing && !fused_dbg && ph_n == 0 && ecp_n_nl == 0;
@@ -373,9 +413,8 @@ struct Engine : dqmc_ctx {
   std::vector<double> w64_h, ecp_loc_h;
   int ecp_loc_nt_h = 0;
   // pseudo-Hamiltonian (dqmc_set_pseudo_hamiltonian): radial tables of the PH nuclei, compacted
-  double* d_ph_loc = nullptr;
-  double* d_ph_l2 = nullptr;
-  int32_t* d_ph_nuc = nullptr;
+  DevBuf<double> d_ph_loc, d_ph_l2;
+  DevBuf<int32_t> d_ph_nuc;
   int ph_n = 0, ph_grid = 0;
   double ph_rmax = 0.0;
   size_t off_phq = 0;
@@ -386,58 +425,25 @@ struct Engine : dqmc_ctx {
   int no_twin = 0;        // option "no_twin" 1: this float32 context never creates its float64 twin -- ensure_twin answers like a program
                           // without a float64 kernel set (DQMC_E_UNSUPPORTED): plain float32 everywhere (refinement off by itself,
                           // float32 ECP quadrature)
-  int32_t* d_flag = nullptr;     // [0] = count, [1..] = walker indices
-  double* d_score = nullptr;     // [B] error predictor of the last flagged pass
-  size_t flag_cap = 0;
-  char* d_ref = nullptr;
-  size_t ref_bytes = 0;
-  size_t score_cap = 0;
+  DevBuf<int32_t> d_flag;        // [0] = count, [1..] = walker indices
+  DevBuf<double> d_score;        // [B] error predictor of the last flagged pass
+  DevBuf<char> d_ref;
   const double* ref_e64 = nullptr;   // float64 local energies of the last refine_listed pass (device)
   std::vector<double> probe_sample_e;          // ... of the calibration sample of a probe call (host)
   std::function<void()> probe_rethreshold;     // set by the probe call: derives refine_thresh from probe_sample_e
 
-  ~Engine() override {
+  ~Engine() override {      // what is not memory, before the members release theirs
     delete twin;
     drop_graphs();
     if (st_g) (void)hipStreamDestroy(st_g);
     if (ev_g0) (void)hipEventDestroy(ev_g0);
     if (ev_g1) (void)hipEventDestroy(ev_g1);
-    if (d_thresh) (void)hipFree(d_thresh);
     if (st2) (void)hipStreamDestroy(st2);
     for (auto x : st_extra) if (x) (void)hipStreamDestroy(x);
     for (auto e : ms_events) if (e) (void)hipEventDestroy(e);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (auto e : buf_ev) if (e) (void)hipEventDestroy(e);
-    if (d_molz) (void)hipFree(d_molz);
-    if (d_flag) (void)hipFree(d_flag);
-    if (d_score) (void)hipFree(d_score);
-    if (d_ref) (void)hipFree(d_ref);
-    if (d_descs) (void)hipFree(d_descs);
-    if (d_wave_begin) (void)hipFree(d_wave_begin);
-    if (d_fbufs2) (void)hipFree(d_fbufs2);
-    if (d_ecp_loc) (void)hipFree(d_ecp_loc);
-    if (d_ecp_nl) (void)hipFree(d_ecp_nl);
-    if (d_ecp_nuc) (void)hipFree(d_ecp_nuc);
-    if (d_ph_loc) (void)hipFree(d_ph_loc);
-    if (d_ph_l2) (void)hipFree(d_ph_l2);
-    if (d_ph_nuc) (void)hipFree(d_ph_nuc);
-    if (d_ecp) (void)hipFree(d_ecp);
-    if (d_ecpm) (void)hipFree(d_ecpm);
     for (auto e : ev_pool) (void)hipEventDestroy(e);
-    if (d_w) (void)hipFree(d_w);
-    if (d_it) (void)hipFree(d_it);
-    if (d_charges) (void)hipFree(d_charges);
-    if (d_ws) (void)hipFree(d_ws);
-    if (d_mc) (void)hipFree(d_mc);
-    if (d_nacc) (void)hipFree(d_nacc);
-    if (d_tau_ring) (void)hipFree(d_tau_ring);
-    if (d_acc) (void)hipFree(d_acc);
-    if (d_ops) (void)hipFree(d_ops);
-    if (d_wpk_off) (void)hipFree(d_wpk_off);
-    if (d_wpk) (void)hipFree(d_wpk);
-    if (d_tape) (void)hipFree(d_tape);
-    free_optim();
-    free_kfacopt();
   }
 
   int init(const dqmc_system* s, const double* charges, const dqmc_buf* b, int nb, const dqmc_op* o, int no,
@@ -451,18 +457,16 @@ struct Engine : dqmc_ctx {
     for (auto& bb : bufs)
       if (bb.rows < 1 || bb.width < 4 || bb.width % 4) return fail(DQMC_E_ARG, "buffer width must be a positive multiple of 4");
     n_weights = nw; n_itable = nit;
-    HIP_TRY(hipMalloc((void**)&d_w, sizeof(real) * (nw ? nw : 1)));
-    HIP_TRY(hipMalloc((void**)&d_it, sizeof(int32_t) * (nit ? nit : 1)));
-    HIP_TRY(hipMalloc((void**)&d_charges, sizeof(double) * sys.n_nuc));
-    HIP_TRY(hipMalloc((void**)&d_nacc, sizeof(int32_t) * 4));
-    HIP_TRY(hipMalloc((void**)&d_tau_ring, sizeof(double) * 2));
-    HIP_TRY(hipMalloc((void**)&d_acc, sizeof(double) * 16));
+    int rc;
+    if ((rc = d_w.assign(nw ? nw : 1)) || (rc = d_it.assign(nit ? nit : 1)) || (rc = d_charges.assign(sys.n_nuc)) ||
+        (rc = d_nacc.assign(4)) || (rc = d_tau_ring.assign(2)) || (rc = d_acc.assign(16)))
+      return rc;
     HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(int32_t) * 4, st));
     HIP_TRY(hipMemcpyAsync(d_charges, charges, sizeof(double) * sys.n_nuc, hipMemcpyHostToDevice, st));
     if (nit) HIP_TRY(hipMemcpyAsync(d_it, it, sizeof(int32_t) * nit, hipMemcpyHostToDevice, st));
     h_itable.assign(it, it + nit);
     HIP_TRY(hipStreamSynchronize(st));
-    int rc = validate();
+    rc = validate();
     if (rc) return rc;
     analyse_lanes();
     analyse_chains();
@@ -757,11 +761,8 @@ int dqmc_energy_stats_allgather(dqmc_ctx* ctx, void* rccl_comm, int n_ranks, con
   double* rec = nullptr;
   int rc = ctx->energy_stats_dev(e_loc, w, B, &rec);
   if (rc) return rc;
-  if ((size_t)n_ranks * 7 > ctx->gather_cap) {
-    if (ctx->d_gather) HIP_TRY(hipFree(ctx->d_gather));
-    HIP_TRY(hipMalloc((void**)&ctx->d_gather, sizeof(double) * 7 * (size_t)n_ranks));
-    ctx->gather_cap = (size_t)n_ranks * 7;
-  }
+  rc = ctx->d_gather.reserve((size_t)n_ranks * 7, ctx->st);
+  if (rc) return rc;
   const int nrc = nccl_all_gather(rec, ctx->d_gather, 7, /* ncclFloat64 */ 8, rccl_comm, ctx->st);
   if (nrc != 0) return fail(DQMC_E_HIP, "ncclAllGather failed with code " + std::to_string(nrc));
   std::vector<double> host((size_t)n_ranks * 7);

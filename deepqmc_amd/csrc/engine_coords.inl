@@ -5,7 +5,7 @@
 // (FEAT_EN, FEAT_EE, ORBITALS, the cusps of FINAL) turn their adjoints into one 3-vector per coordinate difference they read
 // ("slots", kernels_coords.inl); one gather per particle then sums them in the fixed order of c_tab, which is built here.
 
-  GradDev c_tab;                 // int32 [N + n_nuc][c_S][2]: (slot, +1 / -1) per particle, slot -1 = end of the list
+  DevBuf<int32_t> c_tab;         // [N + n_nuc][c_S][2]: (slot, +1 / -1) per particle, slot -1 = end of the list
   std::vector<int> c_slot0;      // per op: first slot of its range, -1: none
   int c_n_slots = 0, c_S = 1;
   bool c_tab_built = false;
@@ -53,8 +53,7 @@
     std::vector<int32_t> t((size_t)P * c_S * 2, -1);
     for (int p = 0; p < P; ++p)
       for (size_t e = 0; e < l[p].size(); ++e) { t[((size_t)p * c_S + e) * 2] = l[p][e].first; t[((size_t)p * c_S + e) * 2 + 1] = l[p][e].second; }
-    HIP_TRY(hipMalloc(&c_tab.p, sizeof(int32_t) * t.size()));
-    HIP_TRY(hipMemcpy(c_tab.p, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice));
+    { const int rc = c_tab.upload(t.data(), t.size()); if (rc) return rc; }
     c_n_slots = std::max(ns, 1);
     c_tab_built = true;
     return DQMC_OK;

@@ -18,12 +18,8 @@
                  o_r32 = o_cnt + 256, o_l32 = o_r32 + al(4 * n_cfg * N * 3), o_s32 = o_l32 + al(4 * n_cfg),
                  o_r64 = o_s32 + al(4 * n_cfg), o_l64 = o_r64 + al(8 * n_cfg * N * 3), o_s64 = o_l64 + al(8 * n_cfg),
                  o_R64 = o_s64 + al(4 * n_cfg), tot = o_R64 + al(8 * 3 * (size_t)sys.n_nuc);
-    if (tot > ecpm_bytes) {
-      if (d_ecpm) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(d_ecpm)); d_ecpm = nullptr; ecpm_bytes = 0; }
-      hipError_t e = hipMalloc((void**)&d_ecpm, tot);
-      if (e != hipSuccess) return fail(DQMC_E_NOMEM, "ECP scratch of " + std::to_string(tot) + " bytes: " + hipGetErrorString(e));
-      ecpm_bytes = tot;
-    }
+    rc = d_ecpm.reserve(tot, st, "ECP scratch");
+    if (rc) return rc;
     int32_t* cls = (int32_t*)(d_ecpm + o_cls); int32_t* list_l = (int32_t*)(d_ecpm + o_ll); int32_t* list_h = (int32_t*)(d_ecpm + o_lh);
     int32_t* cnt = (int32_t*)(d_ecpm + o_cnt);
     float* rq32 = (float*)(d_ecpm + o_r32); float* lq32 = (float*)(d_ecpm + o_l32); int32_t* sq32 = (int32_t*)(d_ecpm + o_s32);
@@ -85,9 +81,7 @@
     ++graph_epoch; drop_graphs();          // (captured passes hold the table pointers)
     if (ph_n && nl && n_l > 0 && n_t_nl > 0) return fail(DQMC_E_ARG, "a pseudo-Hamiltonian and a non-local Gaussian ECP cannot both be set");
     HIP_TRY(hipStreamSynchronize(st));
-    if (d_ecp_loc) { HIP_TRY(hipFree(d_ecp_loc)); d_ecp_loc = nullptr; }
-    if (d_ecp_nl) { HIP_TRY(hipFree(d_ecp_nl)); d_ecp_nl = nullptr; }
-    if (d_ecp_nuc) { HIP_TRY(hipFree(d_ecp_nuc)); d_ecp_nuc = nullptr; }
+    d_ecp_loc.reset(); d_ecp_nl.reset(); d_ecp_nuc.reset();
     ecp_nt_loc = ecp_n_nl = ecp_L = ecp_nt_nl = 0;
     ecp_loc_h.clear(); ecp_loc_nt_h = 0;
     ecp_nl_h.clear(); ecp_nl_L_h = ecp_nl_nt_h = 0;
@@ -96,8 +90,8 @@
     if (twin) { const int rc = twin->set_ecp(n_t_loc, loc, n_l, n_t_nl, nl); if (rc) return rc; }
     if (loc && n_t_loc > 0) {
       const size_t n = (size_t)sys.n_nuc * 6 * n_t_loc;
-      HIP_TRY(hipMalloc((void**)&d_ecp_loc, sizeof(double) * n));
-      HIP_TRY(hipMemcpy(d_ecp_loc, loc, sizeof(double) * n, hipMemcpyHostToDevice));
+      const int rc = d_ecp_loc.upload(loc, n);
+      if (rc) return rc;
       ecp_nt_loc = n_t_loc;
     }
     if (nl && n_l > 0 && n_t_nl > 0) {
@@ -112,10 +106,9 @@
         compact.insert(compact.end(), nl + a * blk, nl + (a + 1) * blk);
       }
       if (!nuc.empty()) {
-        HIP_TRY(hipMalloc((void**)&d_ecp_nl, sizeof(double) * compact.size()));
-        HIP_TRY(hipMalloc((void**)&d_ecp_nuc, sizeof(int32_t) * nuc.size()));
-        HIP_TRY(hipMemcpy(d_ecp_nl, compact.data(), sizeof(double) * compact.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_ecp_nuc, nuc.data(), sizeof(int32_t) * nuc.size(), hipMemcpyHostToDevice));
+        int rc = d_ecp_nl.upload(compact.data(), compact.size());
+        if (!rc) rc = d_ecp_nuc.upload(nuc.data(), nuc.size());
+        if (rc) return rc;
         ecp_n_nl = (int)nuc.size(); ecp_L = n_l; ecp_nt_nl = n_t_nl;
       }
     }
@@ -129,9 +122,7 @@
   int set_ph(int n_grid, double r_max, const double* rv_loc, const double* rv_l2, const int32_t* mask) override {
     ++graph_epoch; drop_graphs();
     HIP_TRY(hipStreamSynchronize(st));
-    if (d_ph_loc) { HIP_TRY(hipFree(d_ph_loc)); d_ph_loc = nullptr; }
-    if (d_ph_l2) { HIP_TRY(hipFree(d_ph_l2)); d_ph_l2 = nullptr; }
-    if (d_ph_nuc) { HIP_TRY(hipFree(d_ph_nuc)); d_ph_nuc = nullptr; }
+    d_ph_loc.reset(); d_ph_l2.reset(); d_ph_nuc.reset();
     ph_n = ph_grid = 0; ph_rmax = 0.0;
     ph_loc_h.clear(); ph_l2_h.clear(); ph_mask_h.clear();
     std::vector<int32_t> nuc;
@@ -144,12 +135,10 @@
       loc.insert(loc.end(), rv_loc + (size_t)a * n_grid, rv_loc + (size_t)(a + 1) * n_grid);
       l2.insert(l2.end(), rv_l2 + (size_t)a * n_grid, rv_l2 + (size_t)(a + 1) * n_grid);
     }
-    HIP_TRY(hipMalloc((void**)&d_ph_loc, sizeof(double) * loc.size()));
-    HIP_TRY(hipMalloc((void**)&d_ph_l2, sizeof(double) * l2.size()));
-    HIP_TRY(hipMalloc((void**)&d_ph_nuc, sizeof(int32_t) * nuc.size()));
-    HIP_TRY(hipMemcpy(d_ph_loc, loc.data(), sizeof(double) * loc.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ph_l2, l2.data(), sizeof(double) * l2.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ph_nuc, nuc.data(), sizeof(int32_t) * nuc.size(), hipMemcpyHostToDevice));
+    int rc = d_ph_loc.upload(loc.data(), loc.size());
+    if (!rc) rc = d_ph_l2.upload(l2.data(), l2.size());
+    if (!rc) rc = d_ph_nuc.upload(nuc.data(), nuc.size());
+    if (rc) return rc;
     ph_n = (int)nuc.size(); ph_grid = n_grid; ph_rmax = r_max;
     if (sizeof(real) == 4) {
       ph_loc_h.assign(rv_loc, rv_loc + (size_t)sys.n_nuc * n_grid);
@@ -172,16 +161,12 @@
     const size_t o_rq = 0, o_lq = o_rq + al(sizeof(real) * n_cfg * N * 3), o_sq = o_lq + al(sizeof(real) * n_cfg),
                  o_l0 = o_sq + al(sizeof(int32_t) * n_cfg), o_s0 = o_l0 + al(sizeof(real) * B),
                  tot = o_s0 + al(sizeof(int32_t) * B);
-    if (tot > ecp_bytes) {
-      if (d_ecp) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(d_ecp)); d_ecp = nullptr; ecp_bytes = 0; }
-      hipError_t e = hipMalloc((void**)&d_ecp, tot);
-      if (e != hipSuccess) return fail(DQMC_E_NOMEM, "ECP scratch of " + std::to_string(tot) + " bytes: " + hipGetErrorString(e));
-      ecp_bytes = tot;
-    }
+    int rc = d_ecp.reserve(tot, st, "ECP scratch");
+    if (rc) return rc;
     real* rq = (real*)(d_ecp + o_rq); real* lq = (real*)(d_ecp + o_lq); int32_t* sq = (int32_t*)(d_ecp + o_sq);
     real* l0 = logpsi ? logpsi : (real*)(d_ecp + o_l0);
     int32_t* s0 = sign ? sign : (int32_t*)(d_ecp + o_s0);
-    int rc = run(r, R, B, true, l0, s0, e_loc, stats, grad);
+    rc = run(r, R, B, true, l0, s0, e_loc, stats, grad);
     if (rc) return rc;
     dqmc::EcpArgs a{};
     a.r = r; a.R = R; a.nl_nuc = d_ecp_nuc; a.nl = d_ecp_nl; a.phi = ecp_phi; a.seed = ecp_seed;

@@ -232,9 +232,10 @@
     } else {
       fused_schedule();
     }
-    if (!d_ops) {
-      HIP_TRY(hipMalloc((void**)&d_ops, sizeof(dqmc_op) * ops.size()));
-      HIP_TRY(hipMalloc((void**)&d_wpk_off, 2 * sizeof(int32_t) * ops.size()));
+    {
+      int rc = d_ops.reserve(ops.size(), st);
+      if (!rc) rc = d_wpk_off.reserve(2 * ops.size(), st);
+      if (rc) return rc;
     }
     std::vector<dqmc_op> sched(fused_n_ops);
     for (int j = 0; j < fused_n_ops; ++j) sched[j] = ops[f_order[j]];
@@ -382,11 +383,12 @@
       dqmc::FDesc e{}; e.kind = 0; flat.push_back(e);
     }
     plan_lists = lists;
-    if (d_descs) { HIP_TRY(hipFree(d_descs)); d_descs = nullptr; }
-    HIP_TRY(hipMalloc((void**)&d_descs, sizeof(dqmc::FDesc) * flat.size()));
-    if (!d_wave_begin) HIP_TRY(hipMalloc((void**)&d_wave_begin, sizeof(int32_t) * 8));
-    if (!d_fbufs2) HIP_TRY(hipMalloc((void**)&d_fbufs2, sizeof(dqmc::FusedBuf) * bufs.size()));
-    HIP_TRY(hipMemcpy(d_descs, flat.data(), sizeof(dqmc::FDesc) * flat.size(), hipMemcpyHostToDevice));
+    {
+      int rc = d_descs.upload(flat.data(), flat.size());
+      if (!rc) rc = d_wave_begin.reserve(8, st);
+      if (!rc) rc = d_fbufs2.reserve(bufs.size(), st);
+      if (rc) return rc;
+    }
     HIP_TRY(hipMemcpy(d_wave_begin, begin, sizeof(begin), hipMemcpyHostToDevice));
     fbufs2_h = fb;
     fbufs2_uploaded = false;
@@ -425,7 +427,7 @@
     a.descs = d_descs; a.wave_begin = d_wave_begin; a.ops = d_ops; a.fbufs = d_fbufs2;
     a.w = d_w; a.wpk = d_wpk; a.itable = d_it; a.ws = d_ws; a.r = r; a.R = R;
     a.B = B; a.WT = fused2_WT; a.wt_shift = fused2_shift; a.n_up = sys.n_up; a.n_nuc = sys.n_nuc; a.K = sys.n_det;
-    a.li = li; a.eps = sys.norm_eps; a.prof = fused_dbg ? d_prof : nullptr;
+    a.li = li; a.eps = sys.norm_eps; a.prof = fused_dbg ? d_prof.p : nullptr;
     a.prof_wg = (fused_dbg & 2) ? d_prof + 9 * ops.size() + 80 + 1024 : nullptr;
     a.scratch_off = (int)((fused2_lds - (size_t)dqmc::fused2_scratch_bytes(fused2_WT, N, sys.n_det, (int)sizeof(real), (int)n_itable)) / sizeof(real));
     a.it_off = (int)(fused2_lds - (size_t)((4 * n_itable + 15) / 16 * 16));
@@ -547,11 +549,7 @@
         },
         [&](long s) { pk.push_back(s >= 0 ? wtmp[s] : (real)0); });
     wpk_len = pk.size();
-    if (pk.size() > wpk_cap) {
-      if (d_wpk) HIP_TRY(hipFree(d_wpk));
-      HIP_TRY(hipMalloc((void**)&d_wpk, sizeof(real) * pk.size()));
-      wpk_cap = pk.size();
-    }
+    { const int rc = d_wpk.reserve(pk.size(), st); if (rc) return rc; }
     HIP_TRY(hipMemcpyAsync(d_wpk, pk.data(), sizeof(real) * pk.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_wpk_off, words.data(), sizeof(int32_t) * words.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));

@@ -3,14 +3,9 @@
 // CONV and EDGE_SUM -- and the entry point of the plain mode, the parameter gradient of log|psi| contracted with a cotangent
 // per walker (dqmc_log_psi_vjp).
 
-  struct GradDev {               // device allocation released with the context
-    void* p = nullptr;
-    ~GradDev() { if (p) (void)hipFree(p); }
-  };
-  GradDev g_ws, g_tab;
-  size_t g_ws_bytes = 0;
+  DevBuf<char> g_ws;             // the adjoint workspace, addressed by byte offset
+  DevBuf<int32_t> g_tab;
   std::vector<int> g_tab_of;     // per op: {rows table offset, Sr, senders table offset, Ss} into g_tab (CONV, EDGE_SUM)
-  bool g_tab_built = false;
 
   bool has_attention() const {
     for (const auto& o : ops) if (o.kind == DQMC_OP_ATTENTION) return true;
@@ -52,18 +47,11 @@
     return sizeof(double) * m;
   }
 
-  int grad_ws_reserve(size_t bytes) {      // the adjoint workspace holds at least `bytes`
-    if (bytes <= g_ws_bytes) return DQMC_OK;
-    if (g_ws.p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(g_ws.p)); g_ws.p = nullptr; g_ws_bytes = 0; }
-    const hipError_t e = hipMalloc(&g_ws.p, bytes);
-    if (e != hipSuccess) return fail(DQMC_E_NOMEM, "gradient workspace of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-    g_ws_bytes = bytes;
-    return DQMC_OK;
-  }
+  int grad_ws_reserve(size_t bytes) { return g_ws.reserve(bytes, st, "gradient workspace"); }
 
   // receiver / sender gather tables of the CONV and EDGE_SUM ops (the transposes of their (edge row, sender) lists)
   int grad_tables() {
-    if (g_tab_built) return DQMC_OK;
+    if (g_tab) return DQMC_OK;
     std::vector<int32_t> t;
     g_tab_of.assign(4 * ops.size(), 0);
     for (size_t k = 0; k < ops.size(); ++k) {
@@ -94,10 +82,7 @@
       emit(sl, g_tab_of[4 * k + 2], g_tab_of[4 * k + 3]);
     }
     if (t.empty()) t.push_back(-1);
-    HIP_TRY(hipMalloc(&g_tab.p, sizeof(int32_t) * t.size()));
-    HIP_TRY(hipMemcpy(g_tab.p, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice));
-    g_tab_built = true;
-    return DQMC_OK;
+    return g_tab.upload(t.data(), t.size());
   }
 
   int log_psi_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* logpsi, int32_t* sign) override {

@@ -5,7 +5,7 @@
 // ops do not read back, padding of the buffer) are zeroed first.  If two ops ever wrote the same entries, every row would
 // be zeroed first and the ops would add in op order instead.
 
-  GradDev g_jac_cols;            // the columns of J no op writes (int32, device)
+  DevBuf<int32_t> g_jac_cols;    // the columns of J no op writes
   int g_jac_ncols = 0;
   bool jac_accum = false;        // some weight entry is written by more than one op
   bool jac_planned = false;
@@ -49,16 +49,13 @@
     if (!jac_accum)
       for (size_t j = 0; j < n_weights; ++j) if (!cover[j]) cols.push_back((int32_t)j);
     g_jac_ncols = jac_accum ? (int)n_weights : (int)cols.size();
-    if (!cols.empty()) {
-      HIP_TRY(hipMalloc(&g_jac_cols.p, sizeof(int32_t) * cols.size()));
-      HIP_TRY(hipMemcpy(g_jac_cols.p, cols.data(), sizeof(int32_t) * cols.size(), hipMemcpyHostToDevice));
-    }
+    if (!cols.empty()) { const int rc = g_jac_cols.upload(cols.data(), cols.size()); if (rc) return rc; }
     jac_planned = true;
     return DQMC_OK;
   }
 
   void jac_zero_rows(real* jac, size_t ld_jac, int B) {
-    dqmc::launch_jac_zero<real>(st, jac, (long)ld_jac, jac_accum ? nullptr : (const int32_t*)g_jac_cols.p, g_jac_ncols, B);
+    dqmc::launch_jac_zero<real>(st, jac, (long)ld_jac, jac_accum ? nullptr : g_jac_cols.p, g_jac_ncols, B);
   }
 
   int log_psi_jacobian(const void* r, const void* R, int B, void* jac, size_t ld_jac, void* logpsi, int32_t* sign) override {

@@ -16,7 +16,7 @@
   int k_n_linear = 0;
   std::vector<long> k_rest_pos;       // per weight entry: its rest column, -1 when a LINEAR op owns it
   size_t k_n_rest = 0;
-  GradDev k_rest_zero;                // rest columns no op writes (int32, device)
+  DevBuf<int32_t> k_rest_zero;        // rest columns no op writes
   int k_rest_nzero = 0;
   bool k_planned = false;
 
@@ -57,16 +57,13 @@
       k_rest_pos[j] = (long)k_n_rest++;
     }
     k_rest_nzero = (int)zero.size();
-    if (!zero.empty()) {
-      HIP_TRY(hipMalloc(&k_rest_zero.p, sizeof(int32_t) * zero.size()));
-      HIP_TRY(hipMemcpy(k_rest_zero.p, zero.data(), sizeof(int32_t) * zero.size(), hipMemcpyHostToDevice));
-    }
+    if (!zero.empty()) { const int rc = k_rest_zero.upload(zero.data(), zero.size()); if (rc) return rc; }
     k_planned = true;
     return DQMC_OK;
   }
 
   void kfac_zero_rest(real* rest, int B) {
-    dqmc::launch_jac_zero<real>(st, rest, (long)k_n_rest, (const int32_t*)k_rest_zero.p, k_rest_nzero, B);
+    dqmc::launch_jac_zero<real>(st, rest, (long)k_n_rest, k_rest_zero, k_rest_nzero, B);
   }
 
   int kfac_layout(int* n_linear, size_t* n_factor_doubles, size_t* n_rest) override {

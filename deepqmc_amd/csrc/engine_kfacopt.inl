@@ -11,22 +11,14 @@
 // The state's matrix part, M and L share one layout: A_hat then G_hat of every module in table order (mat_start).  Keeping the
 // factors L in a buffer of their own, laid out like the state, is what lets a later inverse_update_period > 1 reuse them.
 
-  void* kf_tab = nullptr;               // one allocation: every device table of KfTables
-  double* kf_M = nullptr;               // [n_mat_elems]
-  double* kf_L = nullptr;               // [n_mat_elems]
-  double* kf_scal = nullptr;            // [1 + n_mod]
+  DevBuf<char> kf_tab;                  // one allocation: every device table of KfTables
+  DevBuf<double> kf_M, kf_L;            // [n_mat_elems] each
+  DevBuf<double> kf_scal;               // [1 + n_mod]
   dqmc::KfTables kf_t{};
   std::vector<int> kf_active;           // [n_panels + 1] matrices with a panel k (prefix of the sorted list)
   int kf_max_n = 0, kf_max_da = 0, kf_max_dg = 0, kf_panels = 0;
   size_t kf_state = 0;
   bool kf_set = false;
-
-  void free_kfacopt() {
-    for (void* p : {kf_tab, (void*)kf_M, (void*)kf_L, (void*)kf_scal})
-      if (p) (void)hipFree(p);
-    kf_tab = nullptr; kf_M = kf_L = kf_scal = nullptr;
-    kf_set = false;
-  }
 
   int set_kfac_map(const dqmc_kfac_map* hm) override {
     if (has_attention()) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: no reverse pass for ATTENTION ops");
@@ -115,7 +107,7 @@
       for (const auto& mt : mats) if (mt.n > k * dqmc::KF_NB) ++kf_active[k];
     // one device allocation for the tables
     HIP_TRY(hipStreamSynchronize(st));
-    free_kfacopt();
+    kf_set = false;
     const size_t n_cols = nd ? (size_t)hm->diag_row[nd] : 0;
     auto up8 = [](size_t b) { return (b + 15) / 16 * 16; };
     size_t o_mod = 0, o_op = o_mod + up8(sizeof(dqmc::KfMod) * mods.size()), o_inv = o_op + up8(sizeof(dqmc::KfOp) * kops.size()),
@@ -133,12 +125,12 @@
     put(o_dp, hm->diag_pos, sizeof(long) * (size_t)nd);
     if (nd) put(o_dr, hm->diag_row, sizeof(long) * (size_t)(nd + 1));
     put(o_dc, hm->diag_col, sizeof(long) * n_cols);
-    HIP_TRY(hipMalloc(&kf_tab, blob.size()));
-    HIP_TRY(hipMemcpy(kf_tab, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&kf_M, sizeof(double) * (size_t)(n_mat ? n_mat : 1)));
-    HIP_TRY(hipMalloc((void**)&kf_L, sizeof(double) * (size_t)(n_mat ? n_mat : 1)));
-    HIP_TRY(hipMalloc((void**)&kf_scal, sizeof(double) * (size_t)(1 + nm)));
-    char* base = (char*)kf_tab;
+    int rc = kf_tab.upload(blob.data(), blob.size());
+    if (!rc) rc = kf_M.assign((size_t)(n_mat ? n_mat : 1));
+    if (!rc) rc = kf_L.assign((size_t)(n_mat ? n_mat : 1));
+    if (!rc) rc = kf_scal.assign((size_t)(1 + nm));
+    if (rc) return rc;
+    char* base = kf_tab;
     kf_t.mod = (const dqmc::KfMod*)(base + o_mod); kf_t.op = (const dqmc::KfOp*)(base + o_op); kf_t.inv = (const int32_t*)(base + o_inv);
     kf_t.mat_start = (const long*)(base + o_ms); kf_t.mats = (const dqmc::KfMat*)(base + o_mats);
     kf_t.diag_pos = (const long*)(base + o_dp); kf_t.diag_row = (const long*)(base + o_dr); kf_t.diag_col = (const long*)(base + o_dc);

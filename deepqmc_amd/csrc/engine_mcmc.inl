@@ -31,11 +31,7 @@
     const size_t o_rp = 0, o_lp = o_rp + al(sizeof(real) * n_r), o_sp = o_lp + al(sizeof(real) * B),
                  o_nz = o_sp + al(sizeof(int32_t) * B), o_un = o_nz + al(sizeof(real) * n_r * (size_t)(n_sub > 0 ? n_sub : 1)),
                  tot = o_un + al(sizeof(real) * B * (size_t)(n_sub > 0 ? n_sub : 1));
-    if (tot > mc_bytes) {
-      if (d_mc) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(d_mc)); d_mc = nullptr; }
-      HIP_TRY(hipMalloc((void**)&d_mc, tot));
-      mc_bytes = tot;
-    }
+    { const int rc = d_mc.reserve(tot, st); if (rc) return rc; }
     real* r_prop = (real*)(d_mc + o_rp); real* lp_prop = (real*)(d_mc + o_lp);
     int32_t* s_prop = (int32_t*)(d_mc + o_sp);
     real* nz = (real*)(d_mc + o_nz); real* un = (real*)(d_mc + o_un);
@@ -65,7 +61,7 @@
         const dqmc_op& fin = ops[fused_n_ops + 1];
         dqmc::FusedMc mc{};
         mc.enabled = 1; mc.noise = noise_s; mc.unif = unif_s; mc.r = r; mc.logpsi = logpsi; mc.sign = sign; mc.age = age;
-        mc.tau_in = tau; mc.tau_ring = d_tau_ring; mc.counters = d_nacc; mc.s = s; mc.target = target;
+        mc.tau_in = tau; mc.tau_ring = d_tau_ring.p; mc.counters = d_nacc; mc.s = s; mc.target = target;
         mc.accept_out = accept_out ? accept_out + (size_t)s * B : nullptr;
         mc.max_age = max_age;
         mc.orb_op = -1;
@@ -78,9 +74,9 @@
           // the plan-specialised kernel of this program (csrc/gen, spec_device.h): one wave per tile of 16 / N walkers
           if constexpr (sizeof(real) == 4) {
             dqmc::SpecArgs sa{};
-            sa.tape = d_tape; sa.w = reinterpret_cast<const float*>(d_w); sa.R = reinterpret_cast<const float*>(R);
+            sa.tape = d_tape; sa.w = reinterpret_cast<const float*>(d_w.p); sa.R = reinterpret_cast<const float*>(R);
             sa.B = B; sa.eps = sys.norm_eps; sa.mc = mc;
-            sa.prof = fused_dbg ? d_prof : nullptr;
+            sa.prof = fused_dbg ? d_prof.p : nullptr;
             t_begin("fused_substep", (double)B * substep_flops());
             spec_k->launch(st, sa, (B + spec_k->walkers_per_block - 1) / spec_k->walkers_per_block);
             t_end();
@@ -91,7 +87,7 @@
         }
         if (s + 1 == n_sub) {
           t_begin("mcmc", 0);
-          dqmc::launch_tau_finalize<real>(st, tau, (const real*)d_tau_ring, d_nacc, s, B, target, d_acc);
+          dqmc::launch_tau_finalize<real>(st, tau, (const real*)d_tau_ring.p, d_nacc, s, B, target, d_acc);
           t_end();
         }
         continue;
@@ -123,19 +119,11 @@
   }
 
   // ---- Langevin (MALA) and exchange steps (electron_samplers.py:176-330, sampling_utils.py:72-101) ----
-  double* d_molz = nullptr;     // device copy of the full nuclear charges the drift cleaning uses
+  DevBuf<double> d_molz;        // device copy of the full nuclear charges the drift cleaning uses
   int upload_molz(const double* z) {
-    if (!d_molz) HIP_TRY(hipMalloc((void**)&d_molz, sizeof(double) * sys.n_nuc));
+    { const int rc = d_molz.reserve(sys.n_nuc, st); if (rc) return rc; }
     HIP_TRY(hipMemcpyAsync(d_molz, z, sizeof(double) * sys.n_nuc, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));     // `z` is pageable host memory of the caller
-    return DQMC_OK;
-  }
-  int ensure_mc(size_t tot) {
-    if (tot > mc_bytes) {
-      if (d_mc) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(d_mc)); d_mc = nullptr; }
-      HIP_TRY(hipMalloc((void**)&d_mc, tot));
-      mc_bytes = tot;
-    }
     return DQMC_OK;
   }
   int langevin_update(const void* r_, const void* R_, const double* molz, int B, const void* tau_, void* logpsi, int32_t* sign,
@@ -144,9 +132,9 @@
     int rc = upload_molz(molz);
     if (rc) return rc;
     const size_t n_r = (size_t)B * N * 3;
-    rc = ensure_mc(sizeof(real) * n_r + 256);
+    rc = d_mc.reserve(sizeof(real) * n_r + 256, st);
     if (rc) return rc;
-    real* g = (real*)d_mc;
+    real* g = (real*)d_mc.p;
     rc = lap_refined((const real*)r_, (const real*)R_, B, nullptr, nullptr, g, (real*)logpsi, sign);
     if (rc) return rc;
     t_begin("mcmc", 0);
@@ -169,7 +157,7 @@
     const size_t o_rp = 0, o_g = o_rp + al(sizeof(real) * n_r), o_fp = o_g + al(sizeof(real) * n_r), o_lp = o_fp + al(sizeof(real) * n_r),
                  o_sp = o_lp + al(sizeof(real) * B), o_nz = o_sp + al(sizeof(int32_t) * B), o_un = o_nz + al(sizeof(real) * n_r * ns),
                  tot = o_un + al(sizeof(real) * B * ns);
-    rc = ensure_mc(tot);
+    rc = d_mc.reserve(tot, st);
     if (rc) return rc;
     real* r_prop = (real*)(d_mc + o_rp); real* g_prop = (real*)(d_mc + o_g); real* f_prop = (real*)(d_mc + o_fp);
     real* lp_prop = (real*)(d_mc + o_lp); int32_t* s_prop = (int32_t*)(d_mc + o_sp);
@@ -210,7 +198,7 @@
     const size_t n_r = (size_t)B * N * 3;
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t o_rp = 0, o_lp = o_rp + al(sizeof(real) * n_r), o_sp = o_lp + al(sizeof(real) * B), tot = o_sp + al(sizeof(int32_t) * B);
-    int rc = ensure_mc(tot);
+    int rc = d_mc.reserve(tot, st);
     if (rc) return rc;
     real* r_prop = (real*)(d_mc + o_rp); real* lp_prop = (real*)(d_mc + o_lp); int32_t* s_prop = (int32_t*)(d_mc + o_sp);
     t_begin("mcmc", 0);

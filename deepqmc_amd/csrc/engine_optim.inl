@@ -14,24 +14,19 @@
 // weight VALUE.  No buffer is reallocated here (d_w, d_wpk and d_tape keep their sizes), op_bf is decided from the shapes
 // alone, and the refinement threshold is read from device memory.  graph_epoch therefore stays as it is.
 
-  int32_t* d_pm_src = nullptr;          // [n_weights] parameter element of every flat weight entry, -1: none
-  int32_t* d_pm_row = nullptr;          // [n_params + 1] transpose of the map, CSR: entries of element e are d_pm_col[row[e] .. row[e + 1])
-  int32_t* d_pm_col = nullptr;          // ascending within an element
+  DevBuf<int32_t> d_pm_src;             // [n_weights] parameter element of every flat weight entry, -1: none
+  DevBuf<int32_t> d_pm_row;             // [n_params + 1] transpose of the map, CSR: entries of element e are d_pm_col[row[e] .. row[e + 1])
+  DevBuf<int32_t> d_pm_col;             // ascending within an element
   size_t pm_n_params = 0;
   std::vector<int32_t> pm_src_h;
-  double* d_w64 = nullptr;              // float32 contexts: the weights in double (what w64_h is to dqmc_set_weights)
-  dqmc::PackSrc* d_tape_src = nullptr;  // [tape words]
-  dqmc::PackSrc* d_wpk_src = nullptr;   // [wpk_len]
-  size_t wpk_src_cap = 0, wpk_len = 0;
+  DevBuf<double> d_w64;                 // float32 contexts: the weights in double (what w64_h is to dqmc_set_weights)
+  DevBuf<dqmc::PackSrc> d_tape_src;     // [tape words]
+  DevBuf<dqmc::PackSrc> d_wpk_src;      // [wpk_len]
+  size_t wpk_len = 0;
   std::vector<int32_t> tab_words;       // what the table of d_wpk_src was built for
   std::vector<char> tab_op_bf;
-  double* d_opt_part = nullptr;         // [3][OPT_MAX_BLOCKS] partial sums of the norms
+  DevBuf<double> d_opt_part;            // [3][OPT_MAX_BLOCKS] partial sums of the norms
   bool dev_ahead = false;               // the device weights are newer than wtmp / w64_h
-
-  void free_optim() {
-    for (void* p : {(void*)d_pm_src, (void*)d_pm_row, (void*)d_pm_col, (void*)d_w64, (void*)d_tape_src, (void*)d_wpk_src, (void*)d_opt_part})
-      if (p) (void)hipFree(p);
-  }
 
   int set_param_map(const int32_t* src, size_t n, size_t n_params) override {
     if (n != n_weights) return fail(DQMC_E_ARG, "parameter map length differs from the weight buffer's");
@@ -50,16 +45,16 @@
       std::vector<int32_t> at(row.begin(), row.end() - 1);
       for (size_t j = 0; j < n; ++j) if (src[j] >= 0) col[at[src[j]]++] = (int32_t)j;      // ascending j within an element
     }
-    for (void** p : {(void**)&d_pm_src, (void**)&d_pm_row, (void**)&d_pm_col}) if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; }
-    HIP_TRY(hipMalloc((void**)&d_pm_src, sizeof(int32_t) * (n ? n : 1)));
-    HIP_TRY(hipMalloc((void**)&d_pm_row, sizeof(int32_t) * row.size()));
-    HIP_TRY(hipMalloc((void**)&d_pm_col, sizeof(int32_t) * col.size()));
+    d_pm_src.reset(); d_pm_row.reset(); d_pm_col.reset();
+    int rc = d_pm_src.assign(n ? n : 1);
+    if (!rc) rc = d_pm_row.upload(row.data(), row.size());
+    if (!rc) rc = d_pm_col.upload(col.data(), col.size());
+    if (!rc) rc = d_opt_part.reserve((size_t)3 * dqmc::OPT_MAX_BLOCKS, st);
+    if (rc) return rc;
     HIP_TRY(hipMemcpy(d_pm_src, src, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pm_row, row.data(), sizeof(int32_t) * row.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pm_col, col.data(), sizeof(int32_t) * col.size(), hipMemcpyHostToDevice));
-    if (!d_opt_part) HIP_TRY(hipMalloc((void**)&d_opt_part, sizeof(double) * 3 * dqmc::OPT_MAX_BLOCKS));
     if (sizeof(real) == 4 && !d_w64) {
-      HIP_TRY(hipMalloc((void**)&d_w64, sizeof(double) * (n ? n : 1)));
+      rc = d_w64.assign(n ? n : 1);
+      if (rc) return rc;
       HIP_TRY(hipMemcpy(d_w64, w64_h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     }
     if constexpr (sizeof(real) == 4) {
@@ -68,11 +63,11 @@
         dqmc::spec_tape_sources(*spec_k, tab.data());
         for (const auto& t : tab)
           if (t.src0 >= (long)n || t.src1 >= (long)n) return fail(DQMC_E_ARG, "weight tape refers to an entry beyond the weight buffer");
-        HIP_TRY(hipMalloc((void**)&d_tape_src, sizeof(dqmc::PackSrc) * tab.size()));
-        HIP_TRY(hipMemcpy(d_tape_src, tab.data(), sizeof(dqmc::PackSrc) * tab.size(), hipMemcpyHostToDevice));
+        rc = d_tape_src.upload(tab.data(), tab.size());
+        if (rc) return rc;
       }
     }
-    if (fused_n_ops > 0) { tab_words.clear(); const int rc = upload_fused_sources(); if (rc) return rc; }
+    if (fused_n_ops > 0) { tab_words.clear(); rc = upload_fused_sources(); if (rc) return rc; }
     if (twin) return twin->set_param_map(src, n, n_params);
     return DQMC_OK;
   }
@@ -88,11 +83,7 @@
     for (const auto& t : tab)
       if (t.src0 >= (long)n_weights || t.src1 >= (long)n_weights) return fail(DQMC_E_ARG, "packed weights refer to an entry beyond the weight buffer");
     HIP_TRY(hipStreamSynchronize(st));
-    if (tab.size() > wpk_src_cap) {
-      if (d_wpk_src) HIP_TRY(hipFree(d_wpk_src));
-      HIP_TRY(hipMalloc((void**)&d_wpk_src, sizeof(dqmc::PackSrc) * tab.size()));
-      wpk_src_cap = tab.size();
-    }
+    { const int rc = d_wpk_src.reserve(tab.size(), st); if (rc) return rc; }
     if (!tab.empty()) HIP_TRY(hipMemcpy(d_wpk_src, tab.data(), sizeof(dqmc::PackSrc) * tab.size(), hipMemcpyHostToDevice));
     wpk_len = tab.size();
     tab_words = words; tab_op_bf = op_bf;
@@ -101,13 +92,9 @@
   // pack_fused_weights of a context whose host copy of the weights is stale (an option rebuilt the plan after a device update)
   int repack_fused_on_device() {
     tab_words.clear();
-    const int rc = upload_fused_sources();
+    int rc = upload_fused_sources();
+    if (!rc) rc = d_wpk.reserve(wpk_len, st);
     if (rc) return rc;
-    if (wpk_len > wpk_cap) {
-      if (d_wpk) HIP_TRY(hipFree(d_wpk));
-      HIP_TRY(hipMalloc((void**)&d_wpk, sizeof(real) * wpk_len));
-      wpk_cap = wpk_len;
-    }
     HIP_TRY(hipMemcpy(d_wpk_off, tab_words.data(), sizeof(int32_t) * tab_words.size(), hipMemcpyHostToDevice));
     if (wpk_len) dqmc::launch_pack_words<real>(st, d_wpk_src, d_w, d_wpk, (long)wpk_len);
     HIP_TRY(hipStreamSynchronize(st));
@@ -117,7 +104,7 @@
   // tape and planes from d_w, in place, on the stream
   void repack_from_dw() {
     if constexpr (sizeof(real) == 4) {
-      if (d_tape_src) dqmc::launch_pack_words<float>(st, d_tape_src, d_w, reinterpret_cast<float*>(d_tape), (long)spec_k->tape_bytes / 4);
+      if (d_tape_src) dqmc::launch_pack_words<float>(st, d_tape_src, d_w, reinterpret_cast<float*>(d_tape.p), (long)spec_k->tape_bytes / 4);
     }
     if (fused_n_ops > 0 && wpk_len) dqmc::launch_pack_words<real>(st, d_wpk_src, d_w, d_wpk, (long)wpk_len);
   }

@@ -22,12 +22,7 @@
     off_cond = bump(sizeof(double) * (size_t)B * sys.n_det);      // conditioning record per determinant (Laplacian mode)
     off_kappa = bump(sizeof(double) * (size_t)B);                 // ... and its psi-weighted sum per walker
     if (ph_n && TP > 1) off_phq = bump(sizeof(double) * (size_t)B * N * dqmc::PH_STRIDE);
-    if (off > ws_bytes) {
-      if (d_ws) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(d_ws)); d_ws = nullptr; ws_bytes = 0; }
-      hipError_t e = hipMalloc((void**)&d_ws, off);
-      if (e != hipSuccess) return fail(DQMC_E_NOMEM, "workspace of " + std::to_string(off) + " bytes: " + hipGetErrorString(e));
-      ws_bytes = off;
-    }
+    { const int rc = d_ws.reserve(off, st, "workspace"); if (rc) return rc; }
     last_B = B; last_TP = TP;
     return DQMC_OK;
   }

@@ -3,7 +3,8 @@
 // the device (dqmc_orbitals), and the two entry points of the Orbs mode of the reverse pass (engine_reverse.inl): the VJP of
 // the Slater matrices with a given cotangent (dqmc_orbitals_vjp) and the fused loss + gradient step (dqmc_pretrain_loss_grad).
 
-  GradDev pt_shells, pt_prims, pt_mo, pt_confs, pt_fac;      // device tables of the target (kernels.h: launch_pretrain_target)
+  DevBuf<int32_t> pt_shells, pt_confs;      // device tables of the target (kernels.h: launch_pretrain_target)
+  DevBuf<real> pt_prims, pt_mo, pt_fac;
   int pt_n_shell = 0, pt_n_ao = 0, pt_n_mo = 0, pt_n_conf = 0;
   std::vector<char> orb_live;    // per op: a path leads from it to the ORBITALS destination buffer
   int orb_op = -1;               // the ORBITALS op
@@ -33,13 +34,6 @@
       for (int b : rd) live_buf[b] = 1;
     }
     orb_tab_built = true;
-    return DQMC_OK;
-  }
-
-  static int pt_upload(GradDev& d, const void* src, size_t bytes) {
-    if (d.p) { HIP_TRY(hipFree(d.p)); d.p = nullptr; }
-    HIP_TRY(hipMalloc(&d.p, bytes ? bytes : 1));
-    if (bytes) HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
     return DQMC_OK;
   }
 
@@ -81,18 +75,19 @@
       fac[2 * c + 1] = (real)(conf_coeffs[c] > 0 ? 1 : conf_coeffs[c] < 0 ? -1 : 0);
     }
     HIP_TRY(hipStreamSynchronize(st));      // (a call that reads the old tables may still run)
-    { const int rc = pt_upload(pt_shells, sh.data(), sizeof(int32_t) * sh.size()); if (rc) return rc; }
-    { const int rc = pt_upload(pt_prims, pr.data(), sizeof(real) * pr.size()); if (rc) return rc; }
-    { const int rc = pt_upload(pt_mo, mo.data(), sizeof(real) * mo.size()); if (rc) return rc; }
-    { const int rc = pt_upload(pt_confs, confs, sizeof(int32_t) * (size_t)n_conf * N); if (rc) return rc; }
-    { const int rc = pt_upload(pt_fac, fac.data(), sizeof(real) * fac.size()); if (rc) return rc; }
+    int rc = pt_shells.upload(sh.data(), sh.size());      // (none of the five is empty: the sizes were checked above)
+    if (!rc) rc = pt_prims.upload(pr.data(), pr.size());
+    if (!rc) rc = pt_mo.upload(mo.data(), mo.size());
+    if (!rc) rc = pt_confs.upload(confs, (size_t)n_conf * N);
+    if (!rc) rc = pt_fac.upload(fac.data(), fac.size());
+    if (rc) return rc;
     pt_n_shell = n_shells; pt_n_ao = n_ao; pt_n_mo = n_mo; pt_n_conf = n_conf;
     return DQMC_OK;
   }
 
   void pt_launch_target(const real* r, const real* R, int B, real* target) {
-    dqmc::launch_pretrain_target<real>(st, r, R, (const int32_t*)pt_shells.p, (const real*)pt_prims.p, (const real*)pt_mo.p,
-                                       (const int32_t*)pt_confs.p, (const real*)pt_fac.p, target, B, N, pt_n_shell, pt_n_ao, pt_n_mo,
+    dqmc::launch_pretrain_target<real>(st, r, R, pt_shells, pt_prims, pt_mo,
+                                       pt_confs, pt_fac, target, B, N, pt_n_shell, pt_n_ao, pt_n_mo,
                                        pt_n_conf);
   }
 
@@ -122,7 +117,7 @@
     for (int b0 = 0; b0 < B; b0 += (int)chunk) {
       const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
       const int rc = run_chunk(r + (size_t)b0 * N * 3, (const real*)R, nb, false, reinterpret_cast<real*>(g_ws.p),
-                               reinterpret_cast<int32_t*>((char*)g_ws.p + o_sg), nullptr, nullptr, nb, nullptr, 0);
+                               reinterpret_cast<int32_t*>(g_ws + o_sg), nullptr, nullptr, nb, nullptr, 0);
       if (rc) return rc;
       dqmc::launch_orbitals_copy<real>(st, bptr(ob), bufs[ob].width, orb + (size_t)b0 * sys.n_det * NN, NN, NN, (long)nb * sys.n_det);
     }

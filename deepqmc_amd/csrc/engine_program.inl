@@ -294,7 +294,7 @@
       if (!spec_k) return DQMC_OK;
       std::vector<uint32_t> tape((size_t)spec_k->tape_bytes / 4);
       dqmc::spec_pack_tape(*spec_k, reinterpret_cast<const float*>(wtmp.data()), tape.data());
-      if (!d_tape) HIP_TRY(hipMalloc((void**)&d_tape, (size_t)spec_k->tape_bytes));
+      { const int rc = d_tape.reserve((size_t)spec_k->tape_bytes / 4, st); if (rc) return rc; }
       HIP_TRY(hipMemcpyAsync(d_tape, tape.data(), (size_t)spec_k->tape_bytes, hipMemcpyHostToDevice, st));
       HIP_TRY(hipStreamSynchronize(st));
     }
@@ -372,7 +372,11 @@
     if (s == "fused_sched") { fused_sched_mode = value; return build_fused_plan(); }
     if (s == "fused_dbg") {
       fused_dbg = value;
-      if (value && !d_prof) { HIP_TRY(hipMalloc((void**)&d_prof, sizeof(long long) * (9 * ops.size() + 80 + 1024 + 2 * 8192))); HIP_TRY(hipMemsetAsync(d_prof, 0, sizeof(long long) * (9 * ops.size() + 80 + 1024 + 2 * 8192), st)); }
+      if (value && !d_prof) {
+        const int rc = d_prof.assign(9 * ops.size() + 80 + 1024 + 2 * 8192);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(d_prof, 0, sizeof(long long) * d_prof.cap, st));
+      }
       return DQMC_OK;
     }
     if (s == "fused_lds_kb") { fused2_lds_budget = (size_t)value * 1024; return build_fused_plan(); }

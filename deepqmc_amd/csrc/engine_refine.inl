@@ -34,11 +34,7 @@
                  o_s = o_e + al(sizeof(double) * n), o_g = o_s + al(sizeof(double) * 6 * (size_t)n),
                  o_l = o_g + al(sizeof(double) * (size_t)n * n3), o_sg = o_l + al(sizeof(double) * n),
                  tot = o_sg + al(sizeof(int32_t) * n);
-    if (tot > ref_bytes) {
-      if (d_ref) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(d_ref)); d_ref = nullptr; ref_bytes = 0; }
-      HIP_TRY(hipMalloc((void**)&d_ref, tot));
-      ref_bytes = tot;
-    }
+    { const int rc = d_ref.reserve(tot, st); if (rc) return rc; }
     double* r64 = (double*)(d_ref + o_r); double* R64 = (double*)(d_ref + o_R); double* e64 = (double*)(d_ref + o_e);
     double* s64 = (double*)(d_ref + o_s); double* g64 = (double*)(d_ref + o_g); double* l64 = (double*)(d_ref + o_l);
     int32_t* sg64 = (int32_t*)(d_ref + o_sg);
@@ -72,7 +68,7 @@
       if (probe_rethreshold) probe_rethreshold();
       n_scatter = n;                       // every evaluated walker above the NEW threshold is written back
     }
-    dqmc::launch_refine_scatter(st, d_list, d_count, n, n_scatter, use_score ? d_score : nullptr, refine_thresh, n3, e64, s64, g64, l64, sg64,
+    dqmc::launch_refine_scatter(st, d_list, d_count, n, n_scatter, use_score ? d_score.p : nullptr, refine_thresh, n3, e64, s64, g64, l64, sg64,
                                 (float*)e_loc, (float*)stats, (long)B, (float*)grad, (float*)logpsi, sign);
     t_end();
     if (!d_count && !use_score) last_refined += n_scatter;
@@ -143,19 +139,9 @@
       return pass_own(r, R, B, logpsi, sign, e_loc, stats, grad);
     } else {
       if (!refine) return pass_own(r, R, B, logpsi, sign, e_loc, stats, grad);
-      if ((size_t)B + 1 > flag_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (d_flag) { HIP_TRY(hipFree(d_flag)); d_flag = nullptr; }
-        HIP_TRY(hipMalloc((void**)&d_flag, sizeof(int32_t) * ((size_t)B + 1)));
-        flag_cap = (size_t)B + 1;
-      }
-      if ((size_t)B > score_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (d_score) { HIP_TRY(hipFree(d_score)); d_score = nullptr; }
-        HIP_TRY(hipMalloc((void**)&d_score, sizeof(double) * (size_t)B));
-        score_cap = (size_t)B;
-      }
-      int rc = DQMC_OK;
+      int rc = d_flag.reserve((size_t)B + 1, st);
+      if (!rc) rc = d_score.reserve((size_t)B, st);
+      if (rc) return rc;
       // mode 1 on a system where most walkers get flagged (deep attention networks, ill-conditioned Slater matrices of a
       // random-init TransPsiformer): the float32 pass would be wasted, so the following 15 calls go to float64 directly,
       // then the float32 pass is probed again
@@ -173,7 +159,8 @@
         return refine_listed(r, R, B, B, e_loc, stats, grad, logpsi, sign);
       }
       HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), st));
-      if (!d_thresh) HIP_TRY(hipMalloc((void**)&d_thresh, sizeof(double)));
+      rc = d_thresh.reserve(1, st);
+      if (rc) return rc;
       if (thresh_uploaded != refine_thresh) {      // (k_final reads the threshold from here: a captured pass must follow a re-calibration)
         HIP_TRY(hipMemcpyAsync(d_thresh, &refine_thresh, sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -211,7 +198,7 @@
         const bool padded = n < B && static_cast<Engine<double>*>(twin)->graph_fits((n + 63) / 64 * 64);
         int n_eval = padded ? (n + 63) / 64 * 64 : n;
         if (n_eval > B) n_eval = B;
-        const int32_t* d_cnt = padded ? d_flag : nullptr;
+        const int32_t* d_cnt = padded ? d_flag.p : nullptr;
         rc = refine_listed(r, R, B, n_eval, e_loc, stats, grad, logpsi, sign, d_cnt);
         last_refined = n;
         HIP_TRY(hipGetLastError());

@@ -129,7 +129,7 @@
     const size_t o_slot = bump(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
     const size_t o_tgt = bump(orbs && !q.cot_orb ? (size_t)B * pt_target_bytes_per_walker() : 0);
     { const int rc = grad_ws_reserve(off); if (rc) return rc; }
-    char* gw = (char*)g_ws.p;
+    char* gw = g_ws;
     auto A = [&](int b) { return reinterpret_cast<real*>(gw + adj[b]); };
     real* lp = q.logpsi ? q.logpsi : reinterpret_cast<real*>(gw + o_lp);
     int32_t* sg = q.sign ? q.sign : reinterpret_cast<int32_t*>(gw + o_sg);
@@ -175,7 +175,7 @@
           else dqmc::launch_colsum_f64(st, src, B, stride, n, q.grad + w_off, kw);
       }
     };
-    const int32_t* gt = (const int32_t*)g_tab.p;
+    const int32_t* gt = g_tab;
     double* dL = reinterpret_cast<double*>(gw + o_dl);
     double* slot = coords ? reinterpret_cast<double*>(gw + o_slot) : nullptr;   // coordinate-difference adjoints (kernels_coords.inl)
     for (size_t opi = ops.size(); opi-- > 0;) {
@@ -306,7 +306,7 @@
       }
     }
     if (coords)
-      dqmc::launch_coords_gather<real>(st, slot, c_n_slots, (const int32_t*)c_tab.p, c_S, lp, sg, B, N, sys.n_nuc, q.grad_r, q.grad_R);
+      dqmc::launch_coords_gather<real>(st, slot, c_n_slots, c_tab, c_S, lp, sg, B, N, sys.n_nuc, q.grad_r, q.grad_R);
     HIP_TRY(hipGetLastError());
     return DQMC_OK;
   }

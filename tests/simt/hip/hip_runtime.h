@@ -41,8 +41,16 @@ enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDevi
 inline const char* hipGetErrorString(hipError_t) { return "simt-emu"; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
-inline hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : 2; }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+// allocation bookkeeping for the tests (simt_runtime.cpp): blocks alive, blocks ever allocated, and a size above which
+// hipMalloc fails (0: no limit)
+extern "C" long long simt_live_allocs, simt_total_allocs, simt_alloc_limit;
+inline hipError_t hipMalloc(void** p, size_t n) {
+  *p = (simt_alloc_limit > 0 && n > (size_t)simt_alloc_limit) ? nullptr : calloc(n ? n : 1, 1);
+  if (!*p) return 2;
+  ++simt_live_allocs; ++simt_total_allocs;
+  return hipSuccess;
+}
+inline hipError_t hipFree(void* p) { if (p) --simt_live_allocs; free(p); return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }

@@ -220,6 +220,28 @@ def test_captured_pass_replays_bit_exactly():
         assert torch.equal(e, out[1][0][seq.index(k)])
 
 
+def test_workspace_growth_keeps_answers_and_graphs():
+    """A context whose workspace, flag list and score buffer grow between calls (64 -> 128 walkers) and are then used below
+    their capacity (64 again): every local energy equals that of a fresh context which only ever saw that batch size, and
+    the last call is a graph replay.  64 walkers is the smallest batch the graph path accepts."""
+    spec, mol, h, tree, eng, it = setup(paulinet, 'LiH', torch.float32)
+    eng.set_option('refine_probe', 0)                  # (fixed threshold: every context flags the same walkers)
+    rs = {B: torch.as_tensor(synthetic_walkers(h, B, seed=30 + B).astype(np.float32), device=DEV) for B in (64, 128)}
+    want = {}
+    for B, r in rs.items():
+        fresh = setup(paulinet, 'LiH', torch.float32)[4]
+        fresh.set_option('refine_probe', 0)
+        want[B] = fresh.local_energy(r)[0].clone()
+        fresh.close()
+    replays = 0
+    for B in (64, 128, 64):
+        for _ in range(3):
+            replays = eng.graph_counters()['replays']
+            e, _ = eng.local_energy(rs[B])
+            assert torch.equal(e, want[B]), B
+    assert eng.graph_counters()['replays'] > replays
+
+
 def test_full_size_properties():
     """BASELINE size (4096 walkers): determinism, batch-split invariance, and fermionic
     antisymmetry (swapping two same-spin electrons flips the sign, keeps log|psi| and E_loc)."""
