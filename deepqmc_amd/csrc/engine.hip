@@ -9,7 +9,8 @@
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
 // engine_coords.inl, with the force estimators), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
 // step (engine_optim.inl), the KFAC preconditioner on its vectors (engine_kfacopt.inl) -- and
-// are included inside the struct body: one translation unit, as before.
+// are included inside the struct body: one translation unit, as before.  The slot layout of dqmc_op lives in op_view.h: all of
+// the above read an op through its named views, never by slot number.
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -25,6 +26,7 @@
 
 #include "../../include/dqmc.h"
 #include "kernels.h"
+#include "op_view.h"
 #include "spec_device.h"
 
 namespace {
@@ -44,7 +46,7 @@ int fail(int code, const std::string& msg) {
                                   ":" + std::to_string(__LINE__) + ")");                                \
   } while (0)
 
-inline int pad4(int n) { return (n + 3) / 4 * 4; }
+using dqmc::pad4;
 
 struct TimingRec {
   double ms = 0;

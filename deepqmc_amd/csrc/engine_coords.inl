@@ -22,7 +22,7 @@
       ns += N * n_nuc;
     };
     for (size_t k = 0; k < ops.size(); ++k) {
-      const int32_t* i = ops[k].i;
+      const dqmc::OpViews v(ops[k]);
       switch (ops[k].kind) {
         case DQMC_OP_FEAT_EN: case DQMC_OP_ORBITALS:
           c_slot0[k] = ns;
@@ -30,16 +30,16 @@
           break;
         case DQMC_OP_FEAT_EE:
           c_slot0[k] = ns;
-          for (int row = 0; row < i[2]; ++row) {
-            const int rc = h_itable[i[1] + 2 * row], sd = h_itable[i[1] + 2 * row + 1];
+          for (int row = 0; row < v.feat_ee.n_rows(); ++row) {
+            const int rc = h_itable[v.feat_ee.table() + 2 * row], sd = h_itable[v.feat_ee.table() + 2 * row + 1];
             if (rc == sd) continue;                    // a self edge: d = 0 whatever the coordinates
             l[rc].push_back({ns + row, 1});
             l[sd >= 0 ? sd : N - 1 - sd].push_back({ns + row, -1});
           }
-          ns += i[2];
+          ns += v.feat_ee.n_rows();
           break;
         case DQMC_OP_FINAL:
-          if (!i[2]) break;
+          if (!v.fin.cusp_kind()) break;
           c_slot0[k] = ns;
           for (int a = 0, p = 0; a < N; ++a)
             for (int b = a + 1; b < N; ++b, ++p) { l[a].push_back({ns + p, 1}); l[b].push_back({ns + p, -1}); }

@@ -3,20 +3,23 @@
 // fragment-major weight packing, the launch.
 
   static void op_io(const dqmc_op& op, std::vector<int>& rd, std::vector<int>& wr) {
-    const int32_t* i = op.i;
+    const dqmc::OpViews v(op);
     rd.clear(); wr.clear();
     switch (op.kind) {
-      case DQMC_OP_FEAT_EN: case DQMC_OP_FEAT_EE: case DQMC_OP_CONST: wr.push_back(i[0]); break;
+      case DQMC_OP_FEAT_EN: wr.push_back(v.feat_en.dst()); break;
+      case DQMC_OP_FEAT_EE: wr.push_back(v.feat_ee.dst()); break;
+      case DQMC_OP_CONST: wr.push_back(v.cst.dst()); break;
       case DQMC_OP_LINEAR:
-        for (int p = 0; p < i[0]; ++p) rd.push_back(i[1 + 4 * p]);
-        if (i[25] >= 0) rd.push_back(i[25]);
-        wr.push_back(i[17]); break;
-      case DQMC_OP_SPIN_MEAN: case DQMC_OP_ROW_SUM: rd.push_back(i[0]); wr.push_back(i[1]); break;
-      case DQMC_OP_CONV: rd.push_back(i[0]); rd.push_back(i[1]); wr.push_back(i[2]); break;
-      case DQMC_OP_EDGE_SUM: rd.push_back(i[0]); wr.push_back(i[2]); break;
-      case DQMC_OP_ORBITALS: rd.push_back(i[0]); wr.push_back(i[1]); break;
-      case DQMC_OP_SLOGDET: rd.push_back(i[0]); break;
-      case DQMC_OP_FINAL: if (i[0] >= 0) rd.push_back(i[0]); break;
+        for (int p = 0; p < v.lin.n_pieces(); ++p) rd.push_back(v.lin.src(p));
+        if (v.lin.has_residual()) rd.push_back(v.lin.res());
+        wr.push_back(v.lin.dst()); break;
+      case DQMC_OP_SPIN_MEAN: rd.push_back(v.spin_mean.src()); wr.push_back(v.spin_mean.dst()); break;
+      case DQMC_OP_ROW_SUM: rd.push_back(v.row_sum.src()); wr.push_back(v.row_sum.dst()); break;
+      case DQMC_OP_CONV: rd.push_back(v.conv.edge()); rd.push_back(v.conv.node()); wr.push_back(v.conv.dst()); break;
+      case DQMC_OP_EDGE_SUM: rd.push_back(v.edge_sum.edge()); wr.push_back(v.edge_sum.dst()); break;
+      case DQMC_OP_ORBITALS: rd.push_back(v.orb.src()); wr.push_back(v.orb.dst()); break;
+      case DQMC_OP_SLOGDET: rd.push_back(v.slogdet.src()); break;
+      case DQMC_OP_FINAL: if (v.fin.has_jastrow()) rd.push_back(v.fin.jastrow()); break;
       default: break;
     }
   }
@@ -214,9 +217,10 @@
     if (n_f < 0) return DQMC_OK;
     for (int k = 0; k < n_f; ++k) {       // the LDS-resident kernel implements tanh / silu layers over electron senders only
       if (ops[k].kind == DQMC_OP_CONST) return DQMC_OK;
-      if (ops[k].kind == DQMC_OP_LINEAR && ops[k].i[24] > 2) return DQMC_OK;
+      if (ops[k].kind == DQMC_OP_LINEAR && dqmc::LinearOp(ops[k]).act() > 2) return DQMC_OK;
+      const dqmc::FeatEeOp e(ops[k]);
       if (ops[k].kind == DQMC_OP_FEAT_EE)
-        for (int r = 0; r < ops[k].i[2]; ++r) if (h_itable[ops[k].i[1] + 2 * r + 1] < 0) return DQMC_OK;
+        for (int r = 0; r < e.n_rows(); ++r) if (h_itable[e.table() + 2 * r + 1] < 0) return DQMC_OK;
     }
     fused_n_ops = n_f;
     if (fused_sched_mode == 3) {
@@ -293,48 +297,48 @@
     };
     for (int j = 0; j < fused_n_ops; ++j) {
       const dqmc_op& op = ops[f_order[j]];
-      const int32_t* i = op.i;
+      const dqmc::LinearOp l(op);
       if (op.kind != DQMC_OP_LINEAR) {
         level_generic.push_back(j);
       } else {
-        const int ldw = pad4(i[21]), Rtot = WT * i[20];
+        const int ldw = l.ldw(), Rtot = WT * l.nrows();
         const int NRB = (Rtot + 15) / 16, NCB = (ldw + 15) / 16, n_cg = (NCB + 1) / 2;
         int rpu = NRB * n_cg / n_waves;
         rpu = rpu < 1 ? 1 : (rpu > 4 ? 4 : rpu);
         dqmc::FDesc t{};
-        t.kind = 1; t.op = j; t.n_pieces = i[0]; t.rtot = Rtot; t.ldw = ldw;
+        t.kind = 1; t.op = j; t.n_pieces = l.n_pieces(); t.rtot = Rtot; t.ldw = ldw;
         long kq = 0;
         bool bf = op_bf[j] != 0;
-        for (int p = 0; p < i[0]; ++p) {
-          const dqmc::FusedBuf& sb = fb[i[1 + 4 * p]];
+        for (int p = 0; p < l.n_pieces(); ++p) {
+          const dqmc::FusedBuf& sb = fb[l.src(p)];
           if (sb.is_global) { fused2_WT = 0; return DQMC_OK; }
-          t.a_base[p] = sb.off + i[2 + 4 * p] * WT * sb.stride;
+          t.a_base[p] = sb.off + l.r0(p) * WT * sb.stride;
           t.a_stride[p] = sb.stride;
           if ((t.a_base[p] | t.a_stride[p]) & 1) bf = false;        // (8-byte LDS reads of the A octets)
         }
         if (op_bf[j] && !bf) return fail(DQMC_E_UNSUPPORTED, "fused plan: odd LDS offset under a bf16-packed layer");
-        for (int p = 0; p < i[0]; ++p) {
+        for (int p = 0; p < l.n_pieces(); ++p) {
           if (bf) {       // bf16 matrix pipe: octets of k, chunks of 32 k
-            t.a_ks[p] = i[3 + 4 * p] / 8;
-            t.a_nq[p] = (i[3 + 4 * p] + 31) / 32;
+            t.a_ks[p] = l.K(p) / 8;
+            t.a_nq[p] = (l.K(p) + 31) / 32;
           } else {
-            t.a_ks[p] = pad4(i[3 + 4 * p]) / 4;
+            t.a_ks[p] = pad4(l.K(p)) / 4;
             t.a_nq[p] = (t.a_ks[p] + 3) / 4;
           }
-          if (i[4 + 4 * p]) t.bcast |= 1 << p;
+          if (l.bcast(p)) t.bcast |= 1 << p;
           kq += t.a_nq[p];
         }
         t.qstride = bf ? NCB * 192 : NCB * 64;
-        t.bias_off = i[23];
-        const dqmc::FusedBuf& db = fb[i[17]];
-        t.flags = (i[24] & 3) | (i[27] ? 4 : 0);
-        if (db.is_global) { t.flags |= 8; t.dst_base = i[17]; t.g_r0 = i[18]; t.g_col0 = i[19]; }
-        else { t.dst_base = db.off + i[18] * WT * db.stride + i[19]; t.dst_stride = db.stride; }
+        t.bias_off = l.bias();
+        const dqmc::FusedBuf& db = fb[l.dst()];
+        t.flags = (l.act() & 3) | (l.res_norm() ? 4 : 0);
+        if (db.is_global) { t.flags |= 8; t.dst_base = l.dst(); t.g_r0 = l.dst_r0(); t.g_col0 = l.dst_col0(); }
+        else { t.dst_base = db.off + l.dst_r0() * WT * db.stride + l.dst_col0(); t.dst_stride = db.stride; }
         t.res_base = -1;
-        if (i[25] >= 0) {
-          const dqmc::FusedBuf& rb = fb[i[25]];
+        if (l.has_residual()) {
+          const dqmc::FusedBuf& rb = fb[l.res()];
           if (rb.is_global) { fused2_WT = 0; return DQMC_OK; }
-          t.res_base = rb.off + i[26] * WT * rb.stride + i[19];
+          t.res_base = rb.off + l.res_r0() * WT * rb.stride + l.dst_col0();
           t.res_stride = rb.stride;
         }
         for (int rb0 = 0; rb0 < NRB; rb0 += rpu)
@@ -348,7 +352,7 @@
             if ((rb0 + u.d.ma) * 16 <= Rtot && cg * 32 + 32 <= ldw) u.d.flags |= 16;
             if (bf) u.d.kind = 6;
             // small layers take the lean unit body (kernel_fused2.hip: fused2_unit_lean / FusedBfUnit::lean)
-            if (fused_lean && u.d.ma == 1 && i[0] == 1 && !u.d.bcast && t.a_nq[0] <= (bf ? 1 : dqmc::FusedGroup<real>::P) && !(t.flags & 8) && (i[24] & 3) <= 1) u.d.kind = bf ? 7 : 5;
+            if (fused_lean && u.d.ma == 1 && l.n_pieces() == 1 && !u.d.bcast && t.a_nq[0] <= (bf ? 1 : dqmc::FusedGroup<real>::P) && !(t.flags & 8) && (l.act() & 3) <= 1) u.d.kind = bf ? 7 : 5;
             u.cost = 12 + (long)u.d.ma * ((bf ? 3 : 4) * kq + 6);     // ~ fixed setup + MFMA quads / chunks + epilogue, in 100-cycle units
             level_units.push_back(u);
           }
@@ -402,7 +406,7 @@
     int orb = -1;
     for (int j = 0; j < fused_n_ops; ++j) if (ops[f_order[j]].kind == DQMC_OP_ORBITALS) orb = f_order[j];
     if (orb < 0 || fused2_WT == 0) return -1;
-    const dqmc::FusedBuf& bfb = fbufs2_h[ops[orb].i[0]];
+    const dqmc::FusedBuf& bfb = fbufs2_h[dqmc::OrbitalsOp(ops[orb]).src()];
     const size_t need = (size_t)fused2_WT * sys.n_det * N * N;
     const size_t bf_len = (size_t)fused2_WT * bfb.rows * bfb.stride;
     const size_t act_end = (fused2_lds - (size_t)dqmc::fused2_scratch_bytes(fused2_WT, N, sys.n_det, (int)sizeof(real), (int)n_itable)) / sizeof(real);
@@ -435,14 +439,7 @@
     a.ma1 = fused2_ma1 ? 1 : 0;
     a.stagger_div = fused_stagger_div; a.prio_mode = fused_prio;
     if (mc) a.mc = *mc;
-    double flops = 0;
-    for (int k = 0; k < fused_n_ops; ++k)
-      if (ops[k].kind == DQMC_OP_LINEAR) {
-        int ktot = 0;
-        for (int p = 0; p < ops[k].i[0]; ++p) ktot += ops[k].i[3 + 4 * p];
-        flops += 2.0 * B * ops[k].i[20] * (double)ktot * ops[k].i[21];
-      }
-    t_begin(mc ? "fused_substep" : "fused_psi", flops);
+    t_begin(mc ? "fused_substep" : "fused_psi", (double)B * fused_flops_per_walker());
     int occ = fused_occ_req;
     if (occ <= 0) { const size_t per_cu = (size_t)160 * 1024 / (fused2_lds ? fused2_lds : 1); occ = per_cu >= 4 ? 4 : (per_cu >= 3 ? 3 : 2); }
     dqmc::launch_fused2_value<real>(st, a, (B + fused2_WT - 1) / fused2_WT, fused2_lds, occ);
@@ -476,13 +473,13 @@
     for (int j = 0; j < fused_n_ops && fused_bf && sizeof(real) == 4; ++j) {
       // a layer goes to the bf16 matrix pipe when every piece is whole octets wide and the chunks of 32 k
       // (12 MFMAs of 16 cycles + the operand split) cost less than its k-steps of 4 (2 MFMAs of 32 cycles)
-      const dqmc_op& op = ops[f_order[j]];
-      if (op.kind != DQMC_OP_LINEAR) continue;
+      const dqmc::LinearOp l(ops[f_order[j]]);
+      if (l.op.kind != DQMC_OP_LINEAR) continue;
       bool ok = true;
       int chunks = 0, ksteps = 0;
-      for (int p = 0; p < op.i[0]; ++p) {
-        const int K = op.i[3 + 4 * p];
-        if (K % 8 != 0 || K == 0 || (bufs[op.i[1 + 4 * p]].width & 1)) ok = false;      // (even LDS row stride: 8-byte reads of the A octets)
+      for (int p = 0; p < l.n_pieces(); ++p) {
+        const int K = l.K(p);
+        if (K % 8 != 0 || K == 0 || (bufs[l.src(p)].width & 1)) ok = false;      // (even LDS row stride: 8-byte reads of the A octets)
         chunks += (K + 31) / 32; ksteps += (K + 3) / 4;
       }
       op_bf[j] = ok && (fused_bf >= 2 ? 9 * chunks < 2 * ksteps : 4 * chunks <= ksteps);     // (option value 2: the stricter rule; measured 110.8 vs 108.8 us)
@@ -491,18 +488,18 @@
       const dqmc_op& op = ops[f_order[j]];
       words[2 * j + 1] = (j + 1 == fused_n_ops || f_level[j + 1] > f_level[j]) ? 1 : 0;
       if (op.kind != DQMC_OP_LINEAR) continue;
-      const int32_t* i = op.i;
-      const int ldw = pad4(i[21]), NCB = (ldw + 15) / 16;
+      const dqmc::LinearOp l(op);
+      const int ldw = l.ldw(), NCB = (ldw + 15) / 16;
       // quad-interleaved: [piece][quad of 4 k-steps][column block][lane][k-step in quad]; every
       // piece is zero padded to whole quads, so one 16-byte load per lane feeds 4 MFMA k-steps
       words[2 * j] = (int32_t)count;
-      const long W = i[22];
+      const long W = l.w();
       int row0 = 0;
       if (op_bf[j]) {
         // bf16 plane layout: [piece][chunk of 32 k][column block][plane][lane][4 words]; word jj of lane l holds
         // k = 32 c + 8 (l >> 4) + 2 jj (low half) and + 1 (high half) of column cb 16 + (l & 15)
-        for (int p = 0; p < i[0]; ++p) {
-          const int K = i[3 + 4 * p], NC = (K + 31) / 32;
+        for (int p = 0; p < l.n_pieces(); ++p) {
+          const int K = l.K(p), NC = (K + 31) / 32;
           for (int c = 0; c < NC; ++c)
             for (int cb = 0; cb < NCB; ++cb)
               for (int pl = 0; pl < 3; ++pl)
@@ -520,8 +517,8 @@
         }
         continue;
       }
-      for (int p = 0; p < i[0]; ++p) {
-        const int KS = pad4(i[3 + 4 * p]) / 4, NQ = (KS + 3) / 4;
+      for (int p = 0; p < l.n_pieces(); ++p) {
+        const int KS = pad4(l.K(p)) / 4, NQ = (KS + 3) / 4;
         for (int q = 0; q < NQ; ++q)
           for (int cb = 0; cb < NCB; ++cb)
             for (int l = 0; l < 64; ++l)

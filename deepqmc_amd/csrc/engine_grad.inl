@@ -14,24 +14,19 @@
   size_t grad_zrow() const {     // largest nrows * ldw of a LINEAR op
     size_t z = 4;
     for (const auto& o : ops)
-      if (o.kind == DQMC_OP_LINEAR && (size_t)o.i[20] * pad4(o.i[21]) > z) z = (size_t)o.i[20] * pad4(o.i[21]);
+      if (o.kind == DQMC_OP_LINEAR) z = std::max(z, (size_t)dqmc::LinearOp(o).nrows() * dqmc::LinearOp(o).ldw());
     return z;
-  }
-  size_t grad_max_ldw() const {
-    size_t m = 4;
-    for (const auto& o : ops) if (o.kind == DQMC_OP_LINEAR && (size_t)pad4(o.i[21]) > m) m = (size_t)pad4(o.i[21]);
-    return m;
   }
   size_t grad_orb_partials() const {   // doubles per walker of the ORBITALS table partials
     for (const auto& o : ops)
-      if (o.kind == DQMC_OP_ORBITALS) return (size_t)4 * sys.n_det * N * sys.n_nuc * (o.i[6] > 0 ? o.i[6] : 1);
+      if (o.kind == DQMC_OP_ORBITALS) return (size_t)4 * sys.n_det * N * sys.n_nuc * dqmc::OrbitalsOp(o).n_env();
     return 0;
   }
   // adjoint workspace bytes per walker (beside the value pass's ws_bytes_per_walker(1))
   size_t grad_bytes_per_walker() const {
     size_t b = 0;
     for (const auto& bb : bufs) b += sizeof(real) * (size_t)bb.rows * bb.width;
-    b += sizeof(real) * (2 * grad_zrow() + grad_max_ldw());                      // Z, dZ, dZs
+    b += sizeof(real) * (2 * grad_zrow() + max_ldw());                      // Z, dZ, dZs
     b += sizeof(double) * (grad_orb_partials() + 2 * (size_t)sys.n_det + 2);   // table partials, dL, conf_coeff / alpha partials
     b += sizeof(real) + sizeof(int32_t);                                        // log|psi|, sign when the caller passes none
     return b;
@@ -40,9 +35,10 @@
     size_t m = 0;
     for (const auto& o : ops)
       if (o.kind == DQMC_OP_LINEAR) {
-        const int nt = (pad4(o.i[21]) + 15) / 16;
+        const dqmc::LinearOp l(o);
+        const int nt = (l.ldw() + 15) / 16;
         m = std::max(m, dqmc::grad_dw_part_doubles(1, nt));             // bias
-        for (int p = 0; p < o.i[0]; ++p) m = std::max(m, dqmc::grad_dw_part_doubles((o.i[3 + 4 * p] + 15) / 16, nt));
+        for (int p = 0; p < l.n_pieces(); ++p) m = std::max(m, dqmc::grad_dw_part_doubles((l.K(p) + 15) / 16, nt));
       }
     return sizeof(double) * m;
   }
@@ -57,13 +53,13 @@
     for (size_t k = 0; k < ops.size(); ++k) {
       const dqmc_op& o = ops[k];
       if (o.kind != DQMC_OP_CONV && o.kind != DQMC_OP_EDGE_SUM) continue;
-      const int32_t* i = o.i;
-      const int S = i[5], e_rows = bufs[i[0]].rows;
-      const int s_rows = o.kind == DQMC_OP_CONV ? bufs[i[1]].rows : 1;
+      const dqmc::ConvOp e(o);        // (EDGE_SUM: the slots it shares with CONV)
+      const int S = e.S(), e_rows = bufs[e.edge()].rows;
+      const int s_rows = o.kind == DQMC_OP_CONV ? bufs[e.node()].rows : 1;
       std::vector<std::vector<std::pair<int, int>>> rl(e_rows), sl(s_rows);
       for (int rc = 0; rc < N; ++rc)
         for (int s = 0; s < S; ++s) {
-          const int row = h_itable[i[4] + 2 * (rc * S + s)], snd = h_itable[i[4] + 2 * (rc * S + s) + 1];
+          const int row = h_itable[e.table() + 2 * (rc * S + s)], snd = h_itable[e.table() + 2 * (rc * S + s) + 1];
           if (row < 0) continue;
           rl[row].push_back({rc, snd});
           if (o.kind == DQMC_OP_CONV) sl[snd >= 0 ? snd : -1 - snd].push_back({rc, row});

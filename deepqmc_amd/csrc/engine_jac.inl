@@ -10,26 +10,21 @@
   bool jac_accum = false;        // some weight entry is written by more than one op
   bool jac_planned = false;
 
-  static long linear_w_rows(const dqmc_op& o) {     // rows of a LINEAR op's W block: its pieces, each padded to 4
-    long n = 0;
-    for (int p = 0; p < o.i[0]; ++p) n += pad4(o.i[3 + 4 * p]);
-    return n;
-  }
   // f(offset, count, is_linear) for every block of weight entries whose partials op o's reverse pass forms
   template <class F> void for_each_weight_block(const dqmc_op& o, F&& f) const {
-    const int32_t* i = o.i;
+    const dqmc::OpViews v(o);
     switch (o.kind) {
       case DQMC_OP_LINEAR:
-        f((long)i[22], linear_w_rows(o) * pad4(i[21]), true);
-        if (i[23] >= 0) f((long)i[23], (long)pad4(i[21]), true);
+        f((long)v.lin.w(), (long)v.lin.w_rows() * v.lin.ldw(), true);
+        if (v.lin.has_bias()) f((long)v.lin.bias(), (long)v.lin.ldw(), true);
         break;
-      case DQMC_OP_CONST: f((long)i[1], (long)bufs[i[0]].rows * bufs[i[0]].width, false); break;
+      case DQMC_OP_CONST: f((long)v.cst.table(), (long)bufs[v.cst.dst()].rows * bufs[v.cst.dst()].width, false); break;
       case DQMC_OP_ORBITALS:
-        for (int t = 0; t < 4; ++t) f((long)i[2 + t], (long)sys.n_det * N * sys.n_nuc * (i[6] > 0 ? i[6] : 1), false);
+        for (int t = 0; t < 4; ++t) f((long)v.orb.w(t), (long)sys.n_det * N * sys.n_nuc * v.orb.n_env(), false);
         break;
       case DQMC_OP_FINAL:
-        if (i[1] >= 0) f((long)i[1], (long)sys.n_det, false);
-        f((long)i[3], 2L, false);
+        if (v.fin.has_conf_coeff()) f((long)v.fin.conf_coeff(), (long)sys.n_det, false);
+        f((long)v.fin.alphas(), 2L, false);
         break;
       default: break;
     }

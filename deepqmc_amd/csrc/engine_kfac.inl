@@ -20,13 +20,11 @@
   int k_rest_nzero = 0;
   bool k_planned = false;
 
-  static long kfac_dim_a(const dqmc_op& o) { return linear_w_rows(o) + (o.i[23] >= 0 ? 1 : 0); }
-  static long kfac_dim_g(const dqmc_op& o) { return pad4(o.i[21]); }
   size_t kfac_part_bytes() const {
     size_t m = 0;
     for (const auto& o : ops)
       if (o.kind == DQMC_OP_LINEAR)
-        m = std::max(m, std::max(dqmc::gram_part_doubles((int)kfac_dim_a(o)), dqmc::gram_part_doubles((int)kfac_dim_g(o))));
+        m = std::max(m, std::max(dqmc::gram_part_doubles((int)dqmc::LinearOp(o).kfac_dim_a()), dqmc::gram_part_doubles((int)dqmc::LinearOp(o).kfac_dim_g())));
     return sizeof(double) * m;
   }
 
@@ -39,7 +37,7 @@
     k_n_linear = 0;
     for (size_t k = 0; k < ops.size(); ++k) {
       if (ops[k].kind == DQMC_OP_LINEAR) {
-        const long da = kfac_dim_a(ops[k]), dg = kfac_dim_g(ops[k]);
+        const long da = dqmc::LinearOp(ops[k]).kfac_dim_a(), dg = dqmc::LinearOp(ops[k]).kfac_dim_g();
         k_fac_off[k] = k_fac_total;
         k_fac_total += (size_t)(da * da + dg * dg);
         ++k_n_linear;

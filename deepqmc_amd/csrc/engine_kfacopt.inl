@@ -32,7 +32,7 @@
     // the LINEAR ops of the context by the offset of their A_l
     std::map<long, std::pair<long, long>> lin;      // a_off -> (d_a, d_g)
     for (size_t k = 0; k < ops.size(); ++k)
-      if (ops[k].kind == DQMC_OP_LINEAR) lin[(long)k_fac_off[k]] = {kfac_dim_a(ops[k]), kfac_dim_g(ops[k])};
+      if (ops[k].kind == DQMC_OP_LINEAR) lin[(long)k_fac_off[k]] = {dqmc::LinearOp(ops[k]).kfac_dim_a(), dqmc::LinearOp(ops[k]).kfac_dim_g()};
     const long np = (long)pm_n_params;
     std::vector<uint8_t> covered((size_t)np, 0);
     std::vector<dqmc::KfMod> mods((size_t)nm);

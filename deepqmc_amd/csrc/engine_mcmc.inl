@@ -1,15 +1,11 @@
 // engine_mcmc.inl -- member functions of Engine<real>, included INSIDE the struct body by engine.hip (one translation unit):
 // Metropolis / Langevin / exchange drivers, energy records, dqmc_debug_read.
 
-  // algorithmic flops of the linear layers of one value-only evaluation, per walker (the count run_fused2 reports)
-  double substep_flops() const {
+  // algorithmic flops of the linear layers of one value-only evaluation of the fused range, per walker (what run_fused2 and the
+  // plan-specialised sub-step kernel report)
+  double fused_flops_per_walker() const {
     double flops = 0;
-    for (int k = 0; k < fused_n_ops; ++k)
-      if (ops[k].kind == DQMC_OP_LINEAR) {
-        int ktot = 0;
-        for (int p = 0; p < ops[k].i[0]; ++p) ktot += ops[k].i[3 + 4 * p];
-        flops += 2.0 * ops[k].i[20] * (double)ktot * ops[k].i[21];
-      }
+    for (int k = 0; k < fused_n_ops; ++k) if (ops[k].kind == DQMC_OP_LINEAR) flops += dqmc::LinearOp(ops[k]).flops_per_walker();
     return flops;
   }
   int substep_kernel(char* name_out, size_t n) override {
@@ -58,7 +54,7 @@
         dqmc::LaneInfo li; li.N = N; li.T = 1; li.TP = 1;
         int rc = plan(B, 1);
         if (rc) return rc;
-        const dqmc_op& fin = ops[fused_n_ops + 1];
+        const dqmc::FinalOp fin(ops[fused_n_ops + 1]);
         dqmc::FusedMc mc{};
         mc.enabled = 1; mc.noise = noise_s; mc.unif = unif_s; mc.r = r; mc.logpsi = logpsi; mc.sign = sign; mc.age = age;
         mc.tau_in = tau; mc.tau_ring = d_tau_ring.p; mc.counters = d_nacc; mc.s = s; mc.target = target;
@@ -67,9 +63,9 @@
         mc.orb_op = -1;
         for (int j = 0; j < fused_n_ops; ++j) if (ops[f_order[j]].kind == DQMC_OP_ORBITALS) mc.orb_op = j;
         mc.mat_off = substep_mat_off();
-        mc.jas_width = fin.i[0] >= 0 ? bufs[fin.i[0]].width : 0;
-        mc.cc_off = fin.i[1]; mc.cusp_kind = fin.i[2]; mc.al_off = fin.i[3];
-        mc.same_scale = fin.f[0]; mc.anti_scale = fin.f[1];
+        mc.jas_width = fin.has_jastrow() ? bufs[fin.jastrow()].width : 0;
+        mc.cc_off = fin.conf_coeff(); mc.cusp_kind = fin.cusp_kind(); mc.al_off = fin.alphas();
+        mc.same_scale = fin.same_scale(); mc.anti_scale = fin.anti_scale();
         if (spec_k && fused_spec && d_tape) {
           // the plan-specialised kernel of this program (csrc/gen, spec_device.h): one wave per tile of 16 / N walkers
           if constexpr (sizeof(real) == 4) {
@@ -77,7 +73,7 @@
             sa.tape = d_tape; sa.w = reinterpret_cast<const float*>(d_w.p); sa.R = reinterpret_cast<const float*>(R);
             sa.B = B; sa.eps = sys.norm_eps; sa.mc = mc;
             sa.prof = fused_dbg ? d_prof.p : nullptr;
-            t_begin("fused_substep", (double)B * substep_flops());
+            t_begin("fused_substep", (double)B * fused_flops_per_walker());
             spec_k->launch(st, sa, (B + spec_k->walkers_per_block - 1) / spec_k->walkers_per_block);
             t_end();
           }

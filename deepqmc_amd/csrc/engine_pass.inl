@@ -12,11 +12,7 @@
     auto bump = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     for (size_t k = 0; k < bufs.size(); ++k)
       buf_off[k] = bump(sizeof(real) * (size_t)B * bufs[k].rows * lanes_of((int)k, TP) * bufs[k].width);
-    {
-      int max_ldw = 4;
-      for (const auto& o : ops) if (o.kind == DQMC_OP_LINEAR && pad4(o.i[21]) > max_ldw) max_ldw = pad4(o.i[21]);
-      off_z = bump(sizeof(real) * (size_t)B * TP * max_ldw);       // per-walker pre-activation rows of the split linear layers
-    }
+    off_z = bump(sizeof(real) * (size_t)B * TP * max_ldw());       // per-walker pre-activation rows of the split linear layers
     off_logdet = bump(sizeof(double) * (size_t)B * sys.n_det * TP);
     off_signk = bump(sizeof(int32_t) * (size_t)B * sys.n_det);
     off_cond = bump(sizeof(double) * (size_t)B * sys.n_det);      // conditioning record per determinant (Laplacian mode)
@@ -27,15 +23,18 @@
     return DQMC_OK;
   }
   real* bptr(int b) { return reinterpret_cast<real*>(d_ws + buf_off[b]); }
+  size_t max_ldw() const {       // widest padded output row of a LINEAR op
+    size_t m = 4;
+    for (const auto& o : ops) if (o.kind == DQMC_OP_LINEAR) m = std::max(m, (size_t)dqmc::LinearOp(o).ldw());
+    return m;
+  }
 
   // Workspace bytes per walker for an evaluation with TP lanes (what plan() allocates, without alignment slack).
   size_t ws_bytes_per_walker(int TP) const {
     size_t b = 0;
     for (size_t k = 0; k < bufs.size(); ++k)
       b += sizeof(real) * (size_t)bufs[k].rows * lanes_of((int)k, TP) * bufs[k].width;
-    size_t zrow = 4;
-    for (const auto& o : ops) if (o.kind == DQMC_OP_LINEAR && (size_t)pad4(o.i[21]) > zrow) zrow = (size_t)pad4(o.i[21]);
-    return b + sizeof(real) * zrow * TP + sizeof(double) * (size_t)sys.n_det * TP + sizeof(int32_t) * (size_t)sys.n_det +
+    return b + sizeof(real) * max_ldw() * TP + sizeof(double) * (size_t)sys.n_det * TP + sizeof(int32_t) * (size_t)sys.n_det +
            sizeof(double) * ((size_t)sys.n_det + 1) +           // off_cond, off_kappa
            (ph_n && TP > 1 ? sizeof(double) * (size_t)N * dqmc::PH_STRIDE : 0);
   }
@@ -132,6 +131,28 @@
     return plan(B, (3 * N + 2 + 15) / 16 * 16);
   }
 
+  // Piece table of a LINEAR launch (LinArgs forward, LinBwdArgs in reverse): geometry and the piece's first row in W;
+  // `ptrs(piece, buf)` sets the pointers.  K is padded to 4 for the forward kernel; the backward kernel takes it as the op has it.
+  template <class Piece, class Ptrs> void lin_pieces(const dqmc::LinearOp& l, Piece* piece, bool pad_k, Ptrs&& ptrs) const {
+    int w_row = 0;
+    for (int p = 0; p < l.n_pieces(); ++p) {
+      const dqmc_buf& sb = bufs[l.src(p)];
+      ptrs(piece[p], l.src(p));
+      piece[p].ld = sb.width; piece[p].rpw = sb.rows; piece[p].r0 = l.r0(p);
+      piece[p].K = pad_k ? pad4(l.K(p)) : l.K(p); piece[p].bcast = l.bcast(p); piece[p].w_row = w_row;
+      w_row += pad4(l.K(p));
+    }
+  }
+  // Destination and residual fields of a LINEAR launch (the same names in LinArgs and LinBwdArgs); `at(buf)` gives the base of
+  // a buffer -- the activations forward, the adjoints in reverse -- for `dst` and, where the op has a residual, `res`.
+  template <class Args, class Dst, class Res, class At> void lin_dst_res(const dqmc::LinearOp& l, Args& a, Dst& dst, Res& res, At&& at) const {
+    dst = at(l.dst());
+    a.ld_dst = bufs[l.dst()].width; a.rpw_dst = bufs[l.dst()].rows; a.r0_dst = l.dst_r0(); a.col0_dst = l.dst_col0();
+    res = l.has_residual() ? at(l.res()) : nullptr;
+    if (l.has_residual()) { a.ld_res = bufs[l.res()].width; a.rpw_res = bufs[l.res()].rows; a.r0_res = l.res_r0(); }
+    a.res_scale = l.res_scale<real>();
+  }
+
   int run_chunk(const real* r, const real* R, int B, bool laplacian, real* logpsi, int32_t* sign, real* e_loc, real* stats,
                 long stats_ld, real* grad, int b_offset) {
     dqmc::LaneInfo li;
@@ -217,73 +238,54 @@
     }
     for (size_t opi = first_op; opi < ops.size(); ++opi) {
       const dqmc_op& op = ops[opi];
-      const int32_t* i = op.i;
+      const dqmc::OpViews v(op);
       if (ran_with_parent[opi]) continue;               // second layer of a chained MLP: ran with its parent
       const int sid = sid_of(opi);
       const hipStream_t so = sl[sid];
       { const int rcb = before(op, sid); if (rcb) return rcb; }
+      auto buf_at = [&](int b) { return bptr(b); };
       switch (op.kind) {
         case DQMC_OP_FEAT_EN:
           t_begin("feat", 0, so);
-          dqmc::launch_feat_en<real>(so, r, R, bptr(i[0]), B, sys.n_nuc, sys.n_up, bufs[i[0]].width, li, sys.norm_eps, i[1], i[2], phq);
+          dqmc::launch_feat_en<real>(so, r, R, bptr(v.feat_en.dst()), B, sys.n_nuc, sys.n_up, bufs[v.feat_en.dst()].width, li, sys.norm_eps,
+                                     v.feat_en.log_rescale(), v.feat_en.use_spin(), phq);
           t_end();
           break;
         case DQMC_OP_FEAT_EE:
           t_begin("feat", 0, so);
-          dqmc::launch_feat_ee<real>(so, r, R, d_it + i[1], bptr(i[0]), B, i[2], li, sys.norm_eps, i[3],
-                                     li.TP > 1 && compact[i[0]], phq);
+          dqmc::launch_feat_ee<real>(so, r, R, d_it + v.feat_ee.table(), bptr(v.feat_ee.dst()), B, v.feat_ee.n_rows(), li, sys.norm_eps,
+                                     v.feat_ee.log_rescale(), li.TP > 1 && compact[v.feat_ee.dst()], phq);
           t_end();
           break;
         case DQMC_OP_LINEAR: {
+          const dqmc::LinearOp& l = v.lin;
           dqmc::LinArgs<real> a{};
           a.cfg_bf = linear_bf; a.cfg_bkx = linear_bkx; a.cfg_f64_split = linear_f64_split;
-          a.n_pieces = i[0];
-          int ktot = 0, w_row = 0, n_bc = 0;
-          for (int p = 0; p < i[0]; ++p) {
-            const int sb = i[1 + 4 * p];
-            a.piece[p].src = bptr(sb);
-            a.piece[p].ld = bufs[sb].width;
-            a.piece[p].rpw = bufs[sb].rows;
-            a.piece[p].r0 = i[2 + 4 * p];
-            a.piece[p].K = pad4(i[3 + 4 * p]);
-            a.piece[p].bcast = i[4 + 4 * p];
-            a.piece[p].w_row = w_row;
-            w_row += pad4(i[3 + 4 * p]);
-            n_bc += i[4 + 4 * p] ? 1 : 0;
-            ktot += i[3 + 4 * p];
-          }
-          a.W = d_w + i[22];
-          a.ldw = pad4(i[21]);
-          a.bias = i[23] >= 0 ? d_w + i[23] : nullptr;
-          a.dst = bptr(i[17]);
-          a.ld_dst = bufs[i[17]].width; a.rpw_dst = bufs[i[17]].rows; a.r0_dst = i[18]; a.col0_dst = i[19];
-          a.res = i[25] >= 0 ? bptr(i[25]) : nullptr;
-          if (i[25] >= 0) { a.ld_res = bufs[i[25]].width; a.rpw_res = bufs[i[25]].rows; a.r0_res = i[26]; }
-          a.res_scale = i[27] ? (real)0.70710678118654752440 : (real)1;
-          a.act = i[24]; a.nrows = i[20]; a.B = B; a.T = li.T; a.TP = li.TP;
-          if (li.TP > 1 && compact[i[17]]) { a.T = dqmc::PAIR_LANES; a.TP = dqmc::PAIR_LANES; }   // row-wise op on edge rows
-          if (mlp_child[opi] >= 0 && dqmc::linear_chain_supported(a.TP, a.ldw, pad4(ops[mlp_child[opi]].i[21])) &&
-              compact[ops[mlp_child[opi]].i[17]] == compact[i[17]]) {
+          a.n_pieces = l.n_pieces();
+          lin_pieces(l, a.piece, true, [&](dqmc::LinPiece<real>& pc, int b) { pc.src = bptr(b); });
+          const int ktot = l.k_total(), w_row = l.w_rows(), n_bc = l.n_bcast();
+          a.W = d_w + l.w();
+          a.ldw = l.ldw();
+          a.bias = l.has_bias() ? d_w + l.bias() : nullptr;
+          lin_dst_res(l, a, a.dst, a.res, buf_at);
+          a.act = l.act(); a.nrows = l.nrows(); a.B = B; a.T = li.T; a.TP = li.TP;
+          if (li.TP > 1 && compact[l.dst()]) { a.T = dqmc::PAIR_LANES; a.TP = dqmc::PAIR_LANES; }   // row-wise op on edge rows
+          const dqmc::LinearOp c(ops[mlp_child[opi] >= 0 ? mlp_child[opi] : opi]);      // second layer of a chained MLP (without one: the op itself, not used)
+          if (mlp_child[opi] >= 0 && dqmc::linear_chain_supported(a.TP, a.ldw, c.ldw()) && compact[c.dst()] == compact[l.dst()]) {
             // hidden layer + output layer of a row-wise MLP in one launch (the hidden activations stay in LDS)
-            const dqmc_op& ch = ops[mlp_child[opi]];
-            const int32_t* c = ch.i;
-            { const int rcb = before(ch, sid); if (rcb) return rcb; }
-            a.W2 = d_w + c[22]; a.ldw2 = pad4(c[21]); a.bias2 = c[23] >= 0 ? d_w + c[23] : nullptr; a.act2 = c[24];
-            a.dst = bptr(c[17]);
-            a.ld_dst = bufs[c[17]].width; a.rpw_dst = bufs[c[17]].rows; a.r0_dst = c[18]; a.col0_dst = c[19];
-            a.res = c[25] >= 0 ? bptr(c[25]) : nullptr;
-            if (c[25] >= 0) { a.ld_res = bufs[c[25]].width; a.rpw_res = bufs[c[25]].rows; a.r0_res = c[26]; }
-            a.res_scale = c[27] ? (real)0.70710678118654752440 : (real)1;
-            t_begin("linear", 2.0 * (double)B * i[20] * li.T * ((double)ktot * i[21] + (double)c[3] * c[21]), so,
-                    2.0 * (double)B * i[20] * a.TP * ((double)w_row * a.ldw + (double)a.ldw * a.ldw2));
+            { const int rcb = before(c.op, sid); if (rcb) return rcb; }
+            a.W2 = d_w + c.w(); a.ldw2 = c.ldw(); a.bias2 = c.has_bias() ? d_w + c.bias() : nullptr; a.act2 = c.act();
+            lin_dst_res(c, a, a.dst, a.res, buf_at);
+            t_begin("linear", 2.0 * (double)B * l.nrows() * li.T * ((double)ktot * l.nout() + (double)c.K(0) * c.nout()), so,
+                    2.0 * (double)B * l.nrows() * a.TP * ((double)w_row * a.ldw + (double)a.ldw * a.ldw2));
             dqmc::launch_linear_chain<real>(so, a);
             t_end();
             ran_with_parent[mlp_child[opi]] = 1;
             { const int rca = after(op, sid); if (rca) return rca; }
-            { const int rca = after(ch, sid); if (rca) return rca; }
+            { const int rca = after(c.op, sid); if (rca) return rca; }
             continue;
           }
-          if (split_bcast && n_bc > 0 && n_bc < i[0] && i[20] > 1 && !(li.TP > 1 && compact[i[17]])) {
+          if (split_bcast && n_bc > 0 && n_bc < l.n_pieces() && l.nrows() > 1 && !(li.TP > 1 && compact[l.dst()])) {
             // Per-walker (broadcast) pieces -- the spin means of the node update, reference gnn/update_features.py:64-106 --
             // contribute the same row to every electron of a walker: their product with W is computed ONCE per walker into
             // a scratch row and enters the main launch as an addend of the pre-activation (for LiH 57 %, for N2 62 % of the
@@ -291,7 +293,7 @@
             dqmc::LinArgs<real> z = a;
             dqmc::LinArgs<real> m = a;
             z.n_pieces = m.n_pieces = 0;
-            for (int p = 0; p < i[0]; ++p) {
+            for (int p = 0; p < l.n_pieces(); ++p) {
               if (a.piece[p].bcast) z.piece[z.n_pieces++] = a.piece[p];
               else m.piece[m.n_pieces++] = a.piece[p];
             }
@@ -304,10 +306,10 @@
             // (the last g layer) must be done before it is overwritten
             int zsid = sid;
             if (dual) {
-              for (int p = 0; p < i[0]; ++p)
-                if (i[4 + 4 * p] && !buf_w[i[1 + 4 * p]].empty()) zsid = buf_w[i[1 + 4 * p]].back().sid;
-              for (int p = 0; p < i[0]; ++p)
-                if (i[4 + 4 * p]) { const int rcw = wait_buf(i[1 + 4 * p], zsid); if (rcw) return rcw; }
+              for (int p = 0; p < l.n_pieces(); ++p)
+                if (l.bcast(p) && !buf_w[l.src(p)].empty()) zsid = buf_w[l.src(p)].back().sid;
+              for (int p = 0; p < l.n_pieces(); ++p)
+                if (l.bcast(p)) { const int rcw = wait_buf(l.src(p), zsid); if (rcw) return rcw; }
               if (zb_reader && zsid != sid) HIP_TRY(hipStreamWaitEvent(sl[zsid], zb_reader, 0));
             }
             t_begin("linear", 0, sl[zsid], 2.0 * (double)B * li.TP * (double)[&] { int k = 0; for (int q = 0; q < z.n_pieces; ++q) k += z.piece[q].K; return k; }() * a.ldw);
@@ -320,8 +322,8 @@
               last_ev[zsid] = ez;
               HIP_TRY(hipStreamWaitEvent(so, ez, 0));
             }
-            t_begin("linear", 2.0 * (double)B * i[20] * li.T * (double)ktot * i[21], so,
-                    2.0 * (double)B * i[20] * a.TP * (double)[&] { int k = 0; for (int q = 0; q < m.n_pieces; ++q) k += m.piece[q].K; return k; }() * a.ldw);
+            t_begin("linear", 2.0 * (double)B * l.nrows() * li.T * (double)ktot * l.nout(), so,
+                    2.0 * (double)B * l.nrows() * a.TP * (double)[&] { int k = 0; for (int q = 0; q < m.n_pieces; ++q) k += m.piece[q].K; return k; }() * a.ldw);
             dqmc::launch_linear<real>(so, m);
             t_end();
             if (dual) {
@@ -330,78 +332,82 @@
             }
             break;
           }
-          t_begin("linear", 2.0 * (double)B * i[20] * li.T * (double)ktot * i[21], so, 2.0 * (double)B * i[20] * a.TP * (double)w_row * a.ldw);
+          t_begin("linear", 2.0 * (double)B * l.nrows() * li.T * (double)ktot * l.nout(), so, 2.0 * (double)B * l.nrows() * a.TP * (double)w_row * a.ldw);
           dqmc::launch_linear<real>(so, a);
           t_end();
           break;
         }
         case DQMC_OP_SPIN_MEAN:
           t_begin("graph", 0, so);
-          dqmc::launch_spin_mean<real>(so, bptr(i[0]), bptr(i[1]), B, i[2], bufs[i[0]].width, li);
+          dqmc::launch_spin_mean<real>(so, bptr(v.spin_mean.src()), bptr(v.spin_mean.dst()), B, v.spin_mean.n_up(), bufs[v.spin_mean.src()].width, li);
           t_end();
           break;
-        case DQMC_OP_CONV:
+        case DQMC_OP_CONV: {
+          const dqmc_buf &eb = bufs[v.conv.edge()], &nb = bufs[v.conv.node()];
           t_begin("graph", 0, so);
-          dqmc::launch_conv<real>(so, bptr(i[0]), bufs[i[0]].rows, bufs[i[0]].width, bptr(i[1]), bufs[i[1]].rows, bufs[i[1]].width, bptr(i[2]),
-                                  bufs[i[2]].width, i[3], d_it + i[4], i[5], i[6], B, li, li.TP > 1 && compact[i[0]]);
+          dqmc::launch_conv<real>(so, bptr(v.conv.edge()), eb.rows, eb.width, bptr(v.conv.node()), nb.rows, nb.width, bptr(v.conv.dst()), bufs[v.conv.dst()].width,
+                                  v.conv.dst_col0(), d_it + v.conv.table(), v.conv.S(), v.conv.width(), B, li, li.TP > 1 && compact[v.conv.edge()]);
           t_end();
           break;
-        case DQMC_OP_EDGE_SUM:
+        }
+        case DQMC_OP_EDGE_SUM: {
+          const dqmc::EdgeSumOp& e = v.edge_sum;
           t_begin("graph", 0, so);
-          dqmc::launch_edge_sum<real>(so, bptr(i[0]), bufs[i[0]].rows, bufs[i[0]].width, bptr(i[2]), bufs[i[2]].width, i[3],
-                                      d_it + i[4], i[5], i[6], 1.0 / (double)(i[1] > 0 ? i[1] : 1), B, li,
-                                      li.TP > 1 && compact[i[0]]);
+          dqmc::launch_edge_sum<real>(so, bptr(e.edge()), bufs[e.edge()].rows, bufs[e.edge()].width, bptr(e.dst()), bufs[e.dst()].width, e.dst_col0(),
+                                      d_it + e.table(), e.S(), e.width(), e.scale(), B, li, li.TP > 1 && compact[e.edge()]);
           t_end();
           break;
+        }
         case DQMC_OP_ATTENTION: {
+          const dqmc::AttentionOp& at = v.att;
+          const int hd = at.head_dim(), nc = at.n_const(), ld = bufs[at.q()].width;
+          real *q = bptr(at.q()), *k = bptr(at.k()), *vv = bptr(at.v()), *out = bptr(at.dst());
+          const real *ck = d_w + at.const_k(), *cv = d_w + at.const_v();
           // algorithmic flops: S, dP v0 / P v_c, dP_c v_c contractions per lane
-          t_begin("attention", 2.0 * B * i[4] * (double)N * (N + i[6]) * i[5] * (li.T == 1 ? 2.0 : 5.0 * li.T));
+          t_begin("attention", 2.0 * B * at.heads() * (double)N * (N + nc) * hd * (li.T == 1 ? 2.0 : 5.0 * li.T));
           int rc2 = DQMC_OK;
-          const bool att_mfma = attention_mfma && dqmc::attention_mfma_supported<real>(N, i[5], i[6]) &&
+          const bool att_mfma = attention_mfma && dqmc::attention_mfma_supported<real>(N, hd, nc) &&
                                 (attention_mfma >= 2 || dqmc::attention_mfma_profitable(N));
           // (float64 only: the float32 instance of the split kernel agrees with float64 in the emulator but sent a whole benzene
           // batch to the float64 pass on the MI355X when it was tried -- not understood, not instantiated for the product)
           const int att_split = sizeof(real) == 8 ? (attention_split < 0 ? 1 : attention_split) : 0;
           bool done = false;
           if constexpr (sizeof(real) == 8) {
-            if (att_mfma && att_split && li.TP > 1 && dqmc::attention_mfma_split_lds_bytes<real>(N, i[5], i[6]) <= (size_t)160 * 1024 &&
-                i[5] >= 16) {
-              rc2 = dqmc::launch_attention_mfma_split<real>(st, bptr(i[0]), bptr(i[1]), bptr(i[2]), bptr(i[3]), bufs[i[0]].width, i[4], i[5],
-                                                            B, li, i[6], d_w + i[7], d_w + i[8]);
+            if (att_mfma && att_split && li.TP > 1 && dqmc::attention_mfma_split_lds_bytes<real>(N, hd, nc) <= (size_t)160 * 1024 && hd >= 16) {
+              rc2 = dqmc::launch_attention_mfma_split<real>(st, q, k, vv, out, ld, at.heads(), hd, B, li, nc, ck, cv);
               done = true;
             }
           }
           if (done) {}
           else if (att_mfma)
-            rc2 = dqmc::launch_attention_mfma<real>(st, bptr(i[0]), bptr(i[1]), bptr(i[2]), bptr(i[3]), bufs[i[0]].width, i[4], i[5], B, li,
-                                                    i[6], d_w + i[7], d_w + i[8], attention_ncb < 0 ? (sizeof(real) == 4 ? 1 : 0) : attention_ncb);
+            rc2 = dqmc::launch_attention_mfma<real>(st, q, k, vv, out, ld, at.heads(), hd, B, li, nc, ck, cv,
+                                                    attention_ncb < 0 ? (sizeof(real) == 4 ? 1 : 0) : attention_ncb);
           else
-            rc2 = dqmc::launch_attention<real>(st, bptr(i[0]), bptr(i[1]), bptr(i[2]), bptr(i[3]), bufs[i[0]].width,
-                                               i[4], i[5], B, li, i[6], d_w + i[7], d_w + i[8]);
+            rc2 = dqmc::launch_attention<real>(st, q, k, vv, out, ld, at.heads(), hd, B, li, nc, ck, cv);
           t_end();
           if (rc2) return fail(DQMC_E_HIP, "attention launch failed");
           break;
         }
         case DQMC_OP_CONST:
           t_begin("feat", 0, so);
-          dqmc::launch_const_rows<real>(so, d_w + i[1], bptr(i[0]), B, bufs[i[0]].rows, bufs[i[0]].width, li);
+          dqmc::launch_const_rows<real>(so, d_w + v.cst.table(), bptr(v.cst.dst()), B, bufs[v.cst.dst()].rows, bufs[v.cst.dst()].width, li);
           t_end();
           break;
         case DQMC_OP_ROW_SUM:
           t_begin("graph", 0, so);
-          dqmc::launch_row_sum<real>(so, bptr(i[0]), bptr(i[1]), B, bufs[i[0]].rows, bufs[i[0]].width, li);
+          dqmc::launch_row_sum<real>(so, bptr(v.row_sum.src()), bptr(v.row_sum.dst()), B, bufs[v.row_sum.src()].rows, bufs[v.row_sum.src()].width, li);
           t_end();
           break;
         case DQMC_OP_ORBITALS:
           t_begin("orbitals", 0, so);
-          dqmc::launch_orbitals<real>(so, r, R, bptr(i[0]), bufs[i[0]].width, bptr(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
-                                      d_w + i[4], d_w + i[5], B, sys.n_up, sys.n_nuc, i[6] > 0 ? i[6] : 1, sys.n_det, li,
-                                      sys.norm_eps, phq);
+          dqmc::launch_orbitals<real>(so, r, R, bptr(v.orb.src()), bufs[v.orb.src()].width, bptr(v.orb.dst()), bufs[v.orb.dst()].width,
+                                      d_w + v.orb.w(0), d_w + v.orb.w(1), d_w + v.orb.w(2), d_w + v.orb.w(3), B, sys.n_up, sys.n_nuc, v.orb.n_env(),
+                                      sys.n_det, li, sys.norm_eps, phq);
           t_end();
           break;
         case DQMC_OP_SLOGDET:
           t_begin("slogdet", 0);
-          dqmc::launch_slogdet<real>(st, bptr(i[0]), bufs[i[0]].width, reinterpret_cast<double*>(d_ws + off_logdet),
+          dqmc::launch_slogdet<real>(st, bptr(v.slogdet.src()), bufs[v.slogdet.src()].width, reinterpret_cast<double*>(d_ws + off_logdet),
                                      reinterpret_cast<int32_t*>(d_ws + off_signk), B, sys.n_det, li, slogdet_mfma,
                                      laplacian ? reinterpret_cast<double*>(d_ws + off_cond) : nullptr);
           t_end();
@@ -412,12 +418,12 @@
           a.ecp_loc = d_ecp_loc; a.ecp_nt = ecp_nt_loc;
           a.logdet = reinterpret_cast<double*>(d_ws + off_logdet);
           a.sign_k = reinterpret_cast<int32_t*>(d_ws + off_signk);
-          a.jastrow = i[0] >= 0 ? bptr(i[0]) : nullptr;
-          a.jas_width = i[0] >= 0 ? bufs[i[0]].width : 0;
-          a.conf_coeff = i[1] >= 0 ? d_w + i[1] : nullptr;
-          a.alphas = d_w + i[3];
-          a.cusp_kind = i[2];
-          a.same_scale = op.f[0]; a.anti_scale = op.f[1];
+          a.jastrow = v.fin.has_jastrow() ? bptr(v.fin.jastrow()) : nullptr;
+          a.jas_width = v.fin.has_jastrow() ? bufs[v.fin.jastrow()].width : 0;
+          a.conf_coeff = v.fin.has_conf_coeff() ? d_w + v.fin.conf_coeff() : nullptr;
+          a.alphas = d_w + v.fin.alphas();
+          a.cusp_kind = v.fin.cusp_kind();
+          a.same_scale = v.fin.same_scale(); a.anti_scale = v.fin.anti_scale();
           a.eps = sys.norm_eps;
           a.B = B; a.n_up = sys.n_up; a.n_nuc = sys.n_nuc; a.K = sys.n_det; a.li = li;
           a.logpsi = logpsi; a.sign = sign; a.e_loc = e_loc; a.stats = stats; a.stats_ld = stats_ld; a.grad = grad;

@@ -19,7 +19,7 @@
     orb_op = -1;
     for (size_t k = 0; k < ops.size(); ++k) if (ops[k].kind == DQMC_OP_ORBITALS) orb_op = (int)k;
     if (orb_op < 0) return fail(DQMC_E_UNSUPPORTED, "orbitals: the program has no ORBITALS op");
-    const dqmc_buf& ob = bufs[ops[orb_op].i[1]];
+    const dqmc_buf& ob = bufs[dqmc::OrbitalsOp(ops[orb_op]).dst()];
     if (ob.rows != sys.n_det || ob.width != pad4(N * N))
       return fail(DQMC_E_UNSUPPORTED, "orbitals: full-determinant programs only ([n_det][N x N] Slater matrices)");
     orb_live.assign(ops.size(), 0);
@@ -113,7 +113,7 @@
     const size_t o_sg = (sizeof(real) * (size_t)chunk + 255) / 256 * 256;
     { const int rc = grad_ws_reserve(o_sg + sizeof(int32_t) * (size_t)chunk); if (rc) return rc; }
     const UnfusedForward unfused(*this);
-    const int ob = ops[orb_op].i[1], NN = N * N;
+    const int ob = dqmc::OrbitalsOp(ops[orb_op]).dst(), NN = N * N;
     for (int b0 = 0; b0 < B; b0 += (int)chunk) {
       const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
       const int rc = run_chunk(r + (size_t)b0 * N * 3, (const real*)R, nb, false, reinterpret_cast<real*>(g_ws.p),

@@ -5,68 +5,80 @@
   int validate() {
     const int nb = (int)bufs.size();
     auto okb = [&](int b) { return b >= 0 && b < nb; };
+    auto fits_w = [&](int off, size_t n) { return (size_t)off + n <= n_weights; };       // n weight entries from offset off (off >= 0)
     for (size_t k = 0; k < ops.size(); ++k) {
       const dqmc_op& op = ops[k];
-      const int32_t* i = op.i;
+      const dqmc::OpViews v(op);
       bool ok = true;
       switch (op.kind) {
-        case DQMC_OP_FEAT_EN: ok = okb(i[0]) && bufs[i[0]].rows == N && bufs[i[0]].width >= 4 * sys.n_nuc + (i[2] ? 1 : 0); break;
-        case DQMC_OP_FEAT_EE: ok = okb(i[0]) && bufs[i[0]].rows == i[2] && bufs[i[0]].width == 4 && i[1] >= 0 && (size_t)(i[1] + 2 * i[2]) <= n_itable; break;
+        case DQMC_OP_FEAT_EN: ok = okb(v.feat_en.dst()) && bufs[v.feat_en.dst()].rows == N && bufs[v.feat_en.dst()].width >= 4 * sys.n_nuc + (v.feat_en.use_spin() ? 1 : 0); break;
+        case DQMC_OP_FEAT_EE: {
+          const dqmc::FeatEeOp& e = v.feat_ee;
+          ok = okb(e.dst()) && bufs[e.dst()].rows == e.n_rows() && bufs[e.dst()].width == 4 && e.table() >= 0 && (size_t)(e.table() + 2 * e.n_rows()) <= n_itable;
+          for (int r = 0; r < e.n_rows() && ok; ++r) {          // senders: electron s >= 0, or nucleus -1 - s
+            const int rc = h_itable[e.table() + 2 * r], sd = h_itable[e.table() + 2 * r + 1];
+            ok = rc >= 0 && rc < N && sd < N && -1 - sd < sys.n_nuc;
+          }
+          break;
+        }
         case DQMC_OP_LINEAR: {
-          ok = i[0] >= 1 && i[0] <= 4 && okb(i[17]);
-          size_t wrows = 0;
-          for (int p = 0; ok && p < i[0]; ++p) {
-            const int sb = i[1 + 4 * p], r0 = i[2 + 4 * p], K = i[3 + 4 * p], bc = i[4 + 4 * p];
-            ok = okb(sb) && K >= 1 && pad4(K) <= bufs[sb].width && r0 >= 0 && r0 + (bc ? 1 : i[20]) <= bufs[sb].rows;
-            wrows += pad4(K);
+          const dqmc::LinearOp& l = v.lin;
+          ok = l.n_pieces() >= 1 && l.n_pieces() <= dqmc::LIN_MAX_PIECES && okb(l.dst());
+          for (int p = 0; ok && p < l.n_pieces(); ++p) {
+            const int sb = l.src(p), r0 = l.r0(p), K = l.K(p);
+            ok = okb(sb) && K >= 1 && pad4(K) <= bufs[sb].width && r0 >= 0 && r0 + (l.bcast(p) ? 1 : l.nrows()) <= bufs[sb].rows;
           }
           if (ok) {
-            const dqmc_buf& d = bufs[i[17]];
-            const int ldw = pad4(i[21]);
-            ok = i[18] >= 0 && i[18] + i[20] <= d.rows && i[19] >= 0 && i[19] % 4 == 0 && i[19] + ldw <= d.width &&
-                 i[22] >= 0 && i[22] % 4 == 0 && (size_t)i[22] + wrows * ldw <= n_weights &&
-                 (i[23] < 0 || (i[23] % 4 == 0 && (size_t)(i[23] + ldw) <= n_weights)) && i[24] >= 0 && i[24] <= 4;
-            if (ok && i[25] >= 0)
-              ok = okb(i[25]) && bufs[i[25]].width >= i[19] + ldw && i[26] >= 0 && i[26] + i[20] <= bufs[i[25]].rows;
+            const dqmc_buf& d = bufs[l.dst()];
+            const int ldw = l.ldw(), c0 = l.dst_col0();
+            ok = l.dst_r0() >= 0 && l.dst_r0() + l.nrows() <= d.rows && c0 >= 0 && c0 % 4 == 0 && c0 + ldw <= d.width &&
+                 l.w() >= 0 && l.w() % 4 == 0 && fits_w(l.w(), (size_t)l.w_rows() * ldw) &&
+                 (!l.has_bias() || (l.bias() % 4 == 0 && (size_t)(l.bias() + ldw) <= n_weights)) && l.act() >= 0 && l.act() <= 4;
+            if (ok && l.has_residual())
+              ok = okb(l.res()) && bufs[l.res()].width >= c0 + ldw && l.res_r0() >= 0 && l.res_r0() + l.nrows() <= bufs[l.res()].rows;
           }
           break;
         }
-        case DQMC_OP_SPIN_MEAN: ok = okb(i[0]) && okb(i[1]) && bufs[i[0]].rows == N && bufs[i[1]].rows == 2 && bufs[i[0]].width == bufs[i[1]].width; break;
-        case DQMC_OP_CONST: ok = okb(i[0]) && i[1] >= 0 && (size_t)i[1] + (size_t)bufs[i[0]].rows * bufs[i[0]].width <= n_weights; break;
-        case DQMC_OP_CONV: ok = okb(i[0]) && okb(i[1]) && okb(i[2]) && bufs[i[2]].rows == N && i[6] <= bufs[i[0]].width && i[6] <= bufs[i[1]].width && i[3] + i[6] <= bufs[i[2]].width && (size_t)(i[4] + 2 * N * i[5]) <= n_itable; break;
-        case DQMC_OP_EDGE_SUM: ok = okb(i[0]) && okb(i[2]) && bufs[i[2]].rows == N && i[6] <= bufs[i[0]].width && i[3] + i[6] <= bufs[i[2]].width && (size_t)(i[4] + 2 * N * i[5]) <= n_itable; break;
-        case DQMC_OP_ROW_SUM: ok = okb(i[0]) && okb(i[1]) && bufs[i[1]].rows == 1 && bufs[i[0]].width == bufs[i[1]].width; break;
-        case DQMC_OP_ORBITALS: {
-          if (i[6] < 0) { ok = false; break; }
-          const size_t ne = (size_t)sys.n_det * N * sys.n_nuc * (i[6] > 0 ? i[6] : 1);
-          ok = okb(i[0]) && okb(i[1]) && bufs[i[0]].rows == N && bufs[i[0]].width >= sys.n_det * N && bufs[i[1]].rows == sys.n_det && bufs[i[1]].width >= N * N;
-          for (int q = 2; ok && q < 6; ++q) ok = i[q] >= 0 && (size_t)i[q] + ne <= n_weights;
+        case DQMC_OP_SPIN_MEAN: ok = okb(v.spin_mean.src()) && okb(v.spin_mean.dst()) && bufs[v.spin_mean.src()].rows == N && bufs[v.spin_mean.dst()].rows == 2 && bufs[v.spin_mean.src()].width == bufs[v.spin_mean.dst()].width; break;
+        case DQMC_OP_ROW_SUM: ok = okb(v.row_sum.src()) && okb(v.row_sum.dst()) && bufs[v.row_sum.dst()].rows == 1 && bufs[v.row_sum.src()].width == bufs[v.row_sum.dst()].width; break;
+        case DQMC_OP_CONST: ok = okb(v.cst.dst()) && v.cst.table() >= 0 && fits_w(v.cst.table(), (size_t)bufs[v.cst.dst()].rows * bufs[v.cst.dst()].width); break;
+        case DQMC_OP_CONV: case DQMC_OP_EDGE_SUM: {
+          const dqmc::EdgeOp& e = v.conv;
+          const bool conv = op.kind == DQMC_OP_CONV;
+          ok = okb(e.edge()) && (!conv || okb(v.conv.node())) && okb(e.dst()) && bufs[e.dst()].rows == N && e.width() <= bufs[e.edge()].width &&
+               (!conv || e.width() <= bufs[v.conv.node()].width) && e.dst_col0() + e.width() <= bufs[e.dst()].width && (size_t)(e.table() + 2 * N * e.S()) <= n_itable;
+          for (int q = 0; conv && q < N * e.S() && ok; ++q) {
+            const int row = h_itable[e.table() + 2 * q], sd = h_itable[e.table() + 2 * q + 1];
+            if (row < 0) continue;
+            ok = row < bufs[e.edge()].rows && (sd >= 0 ? sd : -1 - sd) < bufs[v.conv.node()].rows;
+          }
           break;
         }
-        case DQMC_OP_SLOGDET: ok = okb(i[0]) && bufs[i[0]].rows == sys.n_det && bufs[i[0]].width >= N * N && N <= 44; break;
-        case DQMC_OP_FINAL: ok = (i[0] < 0 || (okb(i[0]) && bufs[i[0]].rows == 1)) && (i[1] < 0 || (size_t)(i[1] + sys.n_det) <= n_weights) && i[3] >= 0 && (size_t)(i[3] + 2) <= n_weights && i[2] >= 0 && i[2] <= 2; break;
-        case DQMC_OP_ATTENTION:
-          ok = i[4] >= 1 && i[5] >= 1;
-          for (int q = 0; ok && q < 4; ++q) ok = okb(i[q]) && bufs[i[q]].rows == N && bufs[i[q]].width >= i[4] * i[5];
-          if (ok) ok = bufs[i[0]].width == bufs[i[1]].width && bufs[i[0]].width == bufs[i[2]].width && bufs[i[0]].width == bufs[i[3]].width;
-          if (ok) ok = i[6] >= 0 && (i[6] == 0 || (i[7] >= 0 && i[8] >= 0 && (size_t)i[7] + (size_t)i[6] * i[4] * i[5] <= n_weights &&
-                                                   (size_t)i[8] + (size_t)i[6] * i[4] * i[5] <= n_weights));
-          if (ok && dqmc::attention_lds_bytes<real>(N, i[5], i[6]) > (size_t)160 * 1024)
+        case DQMC_OP_ORBITALS: {
+          const dqmc::OrbitalsOp& o = v.orb;
+          if (o.n_env_slot() < 0) { ok = false; break; }
+          const size_t ne = (size_t)sys.n_det * N * sys.n_nuc * o.n_env();
+          ok = okb(o.src()) && okb(o.dst()) && bufs[o.src()].rows == N && bufs[o.src()].width >= sys.n_det * N && bufs[o.dst()].rows == sys.n_det && bufs[o.dst()].width >= N * N;
+          for (int t = 0; ok && t < 4; ++t) ok = o.w(t) >= 0 && fits_w(o.w(t), ne);
+          break;
+        }
+        case DQMC_OP_SLOGDET: ok = okb(v.slogdet.src()) && bufs[v.slogdet.src()].rows == sys.n_det && bufs[v.slogdet.src()].width >= N * N && N <= 44; break;
+        case DQMC_OP_FINAL:
+          ok = (!v.fin.has_jastrow() || (okb(v.fin.jastrow()) && bufs[v.fin.jastrow()].rows == 1)) && (!v.fin.has_conf_coeff() || (size_t)(v.fin.conf_coeff() + sys.n_det) <= n_weights) &&
+               v.fin.alphas() >= 0 && (size_t)(v.fin.alphas() + 2) <= n_weights && v.fin.cusp_kind() >= 0 && v.fin.cusp_kind() <= 2;
+          break;
+        case DQMC_OP_ATTENTION: {
+          const dqmc::AttentionOp& a = v.att;
+          const size_t n_kv = (size_t)a.n_const() * a.heads() * a.head_dim();
+          ok = a.heads() >= 1 && a.head_dim() >= 1;
+          for (int q = 0; ok && q < 4; ++q) ok = okb(a.buf(q)) && bufs[a.buf(q)].rows == N && bufs[a.buf(q)].width >= a.heads() * a.head_dim() && bufs[a.buf(q)].width == bufs[a.q()].width;
+          if (ok) ok = a.n_const() >= 0 && (a.n_const() == 0 || (a.const_k() >= 0 && a.const_v() >= 0 && fits_w(a.const_k(), n_kv) && fits_w(a.const_v(), n_kv)));
+          if (ok && dqmc::attention_lds_bytes<real>(N, a.head_dim(), a.n_const()) > (size_t)160 * 1024)
             return fail(DQMC_E_UNSUPPORTED, "attention tile set (N, head_dim) exceeds the 160 KiB LDS");
           break;
+        }
         default: ok = false;
       }
-      if (ok && op.kind == DQMC_OP_FEAT_EE)          // senders: electron s >= 0, or nucleus -1 - s
-        for (int r = 0; r < i[2] && ok; ++r) {
-          const int rc = h_itable[i[1] + 2 * r], sd = h_itable[i[1] + 2 * r + 1];
-          ok = rc >= 0 && rc < N && sd < N && -1 - sd < sys.n_nuc;
-        }
-      if (ok && op.kind == DQMC_OP_CONV)
-        for (int q = 0; q < N * i[5] && ok; ++q) {
-          const int row = h_itable[i[4] + 2 * q], sd = h_itable[i[4] + 2 * q + 1];
-          if (row < 0) continue;
-          ok = row < bufs[i[0]].rows && (sd >= 0 ? sd : -1 - sd) < bufs[i[1]].rows;
-        }
       if (!ok) return fail(DQMC_E_ARG, "malformed op #" + std::to_string(k) + " kind " + std::to_string(op.kind));
     }
     return DQMC_OK;
@@ -85,25 +97,23 @@
     std::vector<std::vector<int>> writers(nb), readers(nb);
     for (int k = 0; k < no; ++k) { op_io(ops[k], rd, wr); for (int b : wr) writers[b].push_back(k); for (int b : rd) readers[b].push_back(k); }
     for (int c = 0; c < no; ++c) {
-      const int32_t* ci = ops[c].i;
-      if (ops[c].kind != DQMC_OP_LINEAR || ci[0] != 1 || ci[4]) continue;                 // one non-broadcast piece
-      const int hb = ci[1];
+      const dqmc::LinearOp ch(ops[c]);
+      if (ops[c].kind != DQMC_OP_LINEAR || ch.n_pieces() != 1 || ch.bcast(0)) continue;   // one non-broadcast piece
+      const int hb = ch.src(0);
       if (writers[hb].size() != 1 || readers[hb].size() != 1) continue;                   // a private hidden buffer
       const int p = writers[hb][0];
       if (p >= c || ops[p].kind != DQMC_OP_LINEAR || mlp_child[p] >= 0 || mlp_skip[p]) continue;
-      const int32_t* pi = ops[p].i;
-      bool bc = false;
-      for (int q = 0; q < pi[0]; ++q) bc = bc || pi[4 + 4 * q];
-      if (bc || pi[25] >= 0) continue;                                                    // no broadcast pieces, no residual on the hidden layer
-      if (pi[18] != ci[2] || pi[20] != ci[20] || pi[19] != 0 || pad4(ci[3]) != pad4(pi[21])) continue;   // same rows, whole width
-      if (pad4(pi[21]) > 64 || pad4(ci[21]) > 32) continue;
-      if ((pi[24] & 7) > 2 || (ci[24] & 7) > 4) continue;
+      const dqmc::LinearOp pa(ops[p]);
+      if (pa.n_bcast() || pa.has_residual()) continue;                                    // no broadcast pieces, no residual on the hidden layer
+      if (pa.dst_r0() != ch.r0(0) || pa.nrows() != ch.nrows() || pa.dst_col0() != 0 || pad4(ch.K(0)) != pa.ldw()) continue;   // same rows, whole width
+      if (pa.ldw() > 64 || ch.ldw() > 32) continue;
+      if ((pa.act() & 7) > 2 || (ch.act() & 7) > 4) continue;
       bool ok = true;
-      if (ci[25] >= 0) for (int w : writers[ci[25]]) ok = ok && w < p;                    // residual input complete before the pair runs
+      if (ch.has_residual()) for (int w : writers[ch.res()]) ok = ok && w < p;            // residual input complete before the pair runs
       for (int m = p + 1; m < c && ok; ++m) {                                             // nobody in between reads or writes the output buffer
         op_io(ops[m], rd, wr);
-        for (int b : rd) ok = ok && b != ci[17];
-        for (int b : wr) ok = ok && b != ci[17];
+        for (int b : rd) ok = ok && b != ch.dst();
+        for (int b : wr) ok = ok && b != ch.dst();
       }
       if (!ok) continue;
       mlp_child[p] = c;
@@ -125,7 +135,7 @@
       op_io(ops[k], rd, wr);
       if (mlp_child.size() == (size_t)no && mlp_child[k] >= 0) {
         op_io(ops[mlp_child[k]], rd2, wr2);
-        for (int b : rd2) if (b != ops[k].i[17]) rd.push_back(b);
+        for (int b : rd2) if (b != dqmc::LinearOp(ops[k]).dst()) rd.push_back(b);
         for (int b : wr2) wr.push_back(b);
       }
     };
@@ -146,7 +156,7 @@
           if (w > producer) producer = w;
         }
       const dqmc_op& o = ops[k];
-      const bool edge = (o.kind == DQMC_OP_FEAT_EE && compact[o.i[0]]) || (o.kind == DQMC_OP_LINEAR && compact[o.i[17]]);
+      const bool edge = (o.kind == DQMC_OP_FEAT_EE && compact[dqmc::FeatEeOp(o).dst()]) || (o.kind == DQMC_OP_LINEAR && compact[dqmc::LinearOp(o).dst()]);
       int sid = 0;
       if (edge) sid = 1;
       else if (o.kind == DQMC_OP_SLOGDET || o.kind == DQMC_OP_FINAL || o.kind == DQMC_OP_ATTENTION) sid = 0;
@@ -182,67 +192,66 @@
       pr = rc; ps = sd;
     };
     for (size_t k = 0; k < ops.size() && ok; ++k) {
-      const int32_t* i = ops[k].i;
+      const dqmc::OpViews v(ops[k]);
+      // the table's (row, sender) of receiver el must be the row's own pair
+      auto own_pairs = [&](const dqmc::EdgeOp& e) {
+        for (int q = 0; q < N * e.S() && compact[e.edge()]; ++q) {
+          const int row = h_itable[e.table() + 2 * q], snd = h_itable[e.table() + 2 * q + 1];
+          if (row >= 0 && (pair_rs[e.edge()][2 * row] != q / e.S() || pair_rs[e.edge()][2 * row + 1] != snd)) ok = false;
+        }
+      };
       switch (ops[k].kind) {
-        case DQMC_OP_FEAT_EE:
-          if (full_written[i[0]]) { ok = false; break; }
-          compact[i[0]] = 1;
-          for (int r = 0; r < i[2]; ++r) set_pairs(i[0], r, h_itable[i[1] + 2 * r], h_itable[i[1] + 2 * r + 1]);
+        case DQMC_OP_FEAT_EE: {
+          const dqmc::FeatEeOp& e = v.feat_ee;
+          if (full_written[e.dst()]) { ok = false; break; }
+          compact[e.dst()] = 1;
+          for (int r = 0; r < e.n_rows(); ++r) set_pairs(e.dst(), r, h_itable[e.table() + 2 * r], h_itable[e.table() + 2 * r + 1]);
           break;
+        }
         case DQMC_OP_LINEAR: {
+          const dqmc::LinearOp& l = v.lin;
           int n_c = 0;
-          for (int p = 0; p < i[0]; ++p) n_c += compact[i[1 + 4 * p]] ? 1 : 0;
+          for (int p = 0; p < l.n_pieces(); ++p) n_c += compact[l.src(p)] ? 1 : 0;
           if (n_c == 0) {
-            if (compact[i[17]] || (i[25] >= 0 && compact[i[25]])) ok = false;
-            full_written[i[17]] = 1;
+            if (compact[l.dst()] || (l.has_residual() && compact[l.res()])) ok = false;
+            full_written[l.dst()] = 1;
             break;
           }
-          if (n_c != i[0] || full_written[i[17]]) { ok = false; break; }
-          compact[i[17]] = 1;
-          for (int rr = 0; rr < i[20] && ok; ++rr) {
-            const int sb0 = i[1], r00 = i[2];
-            if (i[4] || pair_rs[sb0].empty()) { ok = false; break; }
+          if (n_c != l.n_pieces() || full_written[l.dst()]) { ok = false; break; }
+          compact[l.dst()] = 1;
+          // every source row (pieces and residual) of a destination row carries the same pair
+          auto pair_is = [&](int b, int row, int rc, int sd) { return !pair_rs[b].empty() && pair_rs[b][2 * row] == rc && pair_rs[b][2 * row + 1] == sd; };
+          for (int rr = 0; rr < l.nrows() && ok; ++rr) {
+            const int sb0 = l.src(0), r00 = l.r0(0);
+            if (l.bcast(0) || pair_rs[sb0].empty()) { ok = false; break; }
             const int rc = pair_rs[sb0][2 * (r00 + rr)], sd = pair_rs[sb0][2 * (r00 + rr) + 1];
-            for (int p = 1; p < i[0]; ++p) {
-              const int sb = i[1 + 4 * p], r0 = i[2 + 4 * p];
-              if (i[4 + 4 * p] || pair_rs[sb].empty() || pair_rs[sb][2 * (r0 + rr)] != rc || pair_rs[sb][2 * (r0 + rr) + 1] != sd) ok = false;
-            }
-            if (i[25] >= 0) {
-              const int rb = i[25];
-              if (!compact[rb] || pair_rs[rb].empty() || pair_rs[rb][2 * (i[26] + rr)] != rc || pair_rs[rb][2 * (i[26] + rr) + 1] != sd) ok = false;
-            }
-            set_pairs(i[17], i[18] + rr, rc, sd);
+            for (int p = 1; p < l.n_pieces(); ++p)
+              if (l.bcast(p) || !pair_is(l.src(p), l.r0(p) + rr, rc, sd)) ok = false;
+            if (l.has_residual() && (!compact[l.res()] || !pair_is(l.res(), l.res_r0() + rr, rc, sd))) ok = false;
+            set_pairs(l.dst(), l.dst_r0() + rr, rc, sd);
           }
           break;
         }
         case DQMC_OP_CONV:
-          if (compact[i[1]] || compact[i[2]]) ok = false;
-          full_written[i[2]] = 1;
-          if (compact[i[0]])      // the table's (row, sender) of receiver el must be the row's own pair
-            for (int el = 0; el < N && ok; ++el)
-              for (int sdx = 0; sdx < i[5]; ++sdx) {
-                const int row = h_itable[i[4] + 2 * (el * i[5] + sdx)], snd = h_itable[i[4] + 2 * (el * i[5] + sdx) + 1];
-                if (row >= 0 && (pair_rs[i[0]][2 * row] != el || pair_rs[i[0]][2 * row + 1] != snd)) ok = false;
-              }
+          if (compact[v.conv.node()] || compact[v.conv.dst()]) ok = false;
+          full_written[v.conv.dst()] = 1;
+          own_pairs(v.conv);
           break;
         case DQMC_OP_EDGE_SUM:
-          if (compact[i[2]]) ok = false;
-          full_written[i[2]] = 1;
-          if (compact[i[0]])
-            for (int el = 0; el < N && ok; ++el)
-              for (int sdx = 0; sdx < i[5]; ++sdx) {
-                const int row = h_itable[i[4] + 2 * (el * i[5] + sdx)], snd = h_itable[i[4] + 2 * (el * i[5] + sdx) + 1];
-                if (row >= 0 && (pair_rs[i[0]][2 * row] != el || pair_rs[i[0]][2 * row + 1] != snd)) ok = false;
-              }
+          if (compact[v.edge_sum.dst()]) ok = false;
+          full_written[v.edge_sum.dst()] = 1;
+          own_pairs(v.edge_sum);
           break;
-        case DQMC_OP_FEAT_EN: case DQMC_OP_CONST: full_written[i[0]] = 1; break;
-        case DQMC_OP_SPIN_MEAN: case DQMC_OP_ROW_SUM: if (compact[i[0]]) ok = false; full_written[i[1]] = 1; break;
-        case DQMC_OP_ORBITALS: if (compact[i[0]]) ok = false; full_written[i[1]] = 1; break;
-        case DQMC_OP_SLOGDET: if (compact[i[0]]) ok = false; break;
-        case DQMC_OP_FINAL: if (i[0] >= 0 && compact[i[0]]) ok = false; break;
+        case DQMC_OP_FEAT_EN: full_written[v.feat_en.dst()] = 1; break;
+        case DQMC_OP_CONST: full_written[v.cst.dst()] = 1; break;
+        case DQMC_OP_SPIN_MEAN: if (compact[v.spin_mean.src()]) ok = false; full_written[v.spin_mean.dst()] = 1; break;
+        case DQMC_OP_ROW_SUM: if (compact[v.row_sum.src()]) ok = false; full_written[v.row_sum.dst()] = 1; break;
+        case DQMC_OP_ORBITALS: if (compact[v.orb.src()]) ok = false; full_written[v.orb.dst()] = 1; break;
+        case DQMC_OP_SLOGDET: if (compact[v.slogdet.src()]) ok = false; break;
+        case DQMC_OP_FINAL: if (v.fin.has_jastrow() && compact[v.fin.jastrow()]) ok = false; break;
         case DQMC_OP_ATTENTION:
-          for (int q = 0; q < 3; ++q) if (compact[i[q]]) ok = false;
-          full_written[i[3]] = 1;
+          for (int q = 0; q < 3; ++q) if (compact[v.att.buf(q)]) ok = false;
+          full_written[v.att.dst()] = 1;
           break;
         default: break;
       }
@@ -283,8 +292,8 @@
     for (const auto& b : bufs) { mix(b.rows); mix(b.width); }
     for (const auto& o : ops) {
       mix(o.kind);
-      for (int k = 0; k < 28; ++k) mix(o.i[k]);
-      for (int k = 0; k < 4; ++k) { int32_t bits; memcpy(&bits, &o.f[k], 4); mix(bits); }
+      for (int k = 0; k < dqmc::OP_N_SLOTS; ++k) mix(o.i[k]);
+      for (int k = 0; k < dqmc::OP_N_FSLOTS; ++k) { int32_t bits; memcpy(&bits, &o.f[k], 4); mix(bits); }
     }
     for (int32_t v : h_itable) mix(v);
     return h;

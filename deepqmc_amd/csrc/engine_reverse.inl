@@ -120,7 +120,7 @@
     for (size_t k = 0; k < bufs.size(); ++k) adj[k] = bump(sizeof(real) * (size_t)B * bufs[k].rows * bufs[k].width);
     const size_t adj_end = off;
     const size_t o_z = bump(sizeof(real) * (size_t)B * grad_zrow()), o_dz = bump(sizeof(real) * (size_t)B * grad_zrow());
-    const size_t o_dzs = bump(sizeof(real) * (size_t)B * grad_max_ldw());
+    const size_t o_dzs = bump(sizeof(real) * (size_t)B * max_ldw());
     const size_t o_orb = bump(sizeof(double) * (size_t)B * (!coords && grad_orb_partials() ? grad_orb_partials() : 1));
     const size_t o_dl = bump(sizeof(double) * (size_t)B * sys.n_det), o_pw = bump(sizeof(double) * (size_t)B * (sys.n_det + 2));
     const size_t o_lp = bump(sizeof(real) * (size_t)B), o_sg = bump(sizeof(int32_t) * (size_t)B);
@@ -136,7 +136,7 @@
     { const int rc = run_chunk(r, R, B, false, lp, sg, nullptr, nullptr, B, nullptr, 0); if (rc) return rc; }
     HIP_TRY(hipMemsetAsync(gw, 0, adj_end, st));
     if (orbs) {      // the cotangent enters at the ORBITALS destination buffer
-      const int ob = ops[orb_op].i[1], NN = N * N;
+      const int ob = dqmc::OrbitalsOp(ops[orb_op]).dst(), NN = N * N;
       const long rows = (long)B * sys.n_det;
       if (q.orb) dqmc::launch_orbitals_copy<real>(st, bptr(ob), bufs[ob].width, q.orb, NN, NN, rows);
       if (q.cot_orb) dqmc::launch_orbitals_copy<real>(st, q.cot_orb, NN, A(ob), bufs[ob].width, NN, rows);
@@ -180,125 +180,120 @@
     double* slot = coords ? reinterpret_cast<double*>(gw + o_slot) : nullptr;   // coordinate-difference adjoints (kernels_coords.inl)
     for (size_t opi = ops.size(); opi-- > 0;) {
       const dqmc_op& op = ops[opi];
-      const int32_t* i = op.i;
+      const dqmc::OpViews v(op);
       if (orbs && !orb_live[opi]) continue;
       switch (op.kind) {
         case DQMC_OP_FEAT_EN:      // leaves: no parameters; only the coordinate mode carries their adjoints on
           if (coords)
-            dqmc::launch_feat_en_coords<real>(st, r, R, A(i[0]), bufs[i[0]].width, B, N, sys.n_nuc, sys.norm_eps, i[1],
-                                              slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+            dqmc::launch_feat_en_coords<real>(st, r, R, A(v.feat_en.dst()), bufs[v.feat_en.dst()].width, B, N, sys.n_nuc, sys.norm_eps,
+                                              v.feat_en.log_rescale(), slot + 3 * (size_t)c_slot0[opi], c_n_slots);
           break;
         case DQMC_OP_FEAT_EE:
           if (coords)
-            dqmc::launch_feat_ee_coords<real>(st, r, R, d_it + i[1], A(i[0]), i[2], B, N, sys.norm_eps, i[3],
-                                              slot + 3 * (size_t)c_slot0[opi], c_n_slots);
+            dqmc::launch_feat_ee_coords<real>(st, r, R, d_it + v.feat_ee.table(), A(v.feat_ee.dst()), v.feat_ee.n_rows(), B, N, sys.norm_eps,
+                                              v.feat_ee.log_rescale(), slot + 3 * (size_t)c_slot0[opi], c_n_slots);
           break;
         case DQMC_OP_LINEAR: {
+          const dqmc::LinearOp& l = v.lin;
           // Z = X W + b with the forward kernel (no activation, no residual)
           dqmc::LinArgs<real> f{};
           f.cfg_bf = linear_bf; f.cfg_bkx = linear_bkx; f.cfg_f64_split = linear_f64_split;
-          f.n_pieces = i[0];
           dqmc::LinBwdArgs<real> a{};
-          a.n_pieces = i[0];
-          int w_row = 0;
-          for (int p = 0; p < i[0]; ++p) {
-            const int sb = i[1 + 4 * p];
-            f.piece[p].src = bptr(sb);
-            f.piece[p].ld = bufs[sb].width; f.piece[p].rpw = bufs[sb].rows; f.piece[p].r0 = i[2 + 4 * p];
-            f.piece[p].K = pad4(i[3 + 4 * p]); f.piece[p].bcast = i[4 + 4 * p]; f.piece[p].w_row = w_row;
-            a.piece[p].X = bptr(sb); a.piece[p].dX = A(sb);
-            a.piece[p].ld = bufs[sb].width; a.piece[p].rpw = bufs[sb].rows; a.piece[p].r0 = i[2 + 4 * p];
-            a.piece[p].K = i[3 + 4 * p]; a.piece[p].bcast = i[4 + 4 * p]; a.piece[p].w_row = w_row;
-            w_row += pad4(i[3 + 4 * p]);
-          }
+          f.n_pieces = a.n_pieces = l.n_pieces();
+          lin_pieces(l, f.piece, true, [&](dqmc::LinPiece<real>& pc, int b) { pc.src = bptr(b); });
+          lin_pieces(l, a.piece, false, [&](dqmc::LinBwdPiece<real>& pc, int b) { pc.X = bptr(b); pc.dX = A(b); });
           real* Z = reinterpret_cast<real*>(gw + o_z);
-          f.W = d_w + i[22]; f.ldw = pad4(i[21]); f.bias = i[23] >= 0 ? d_w + i[23] : nullptr;
-          f.dst = Z; f.ld_dst = f.ldw; f.rpw_dst = i[20]; f.r0_dst = 0; f.col0_dst = 0;
-          f.act = 0; f.nrows = i[20]; f.B = B; f.T = 1; f.TP = 1;
-          t_begin(coords ? "linear_dx" : jac ? "linear_jac" : "linear_bwd", (coords ? 4.0 : 6.0) * B * i[20] * (double)w_row * f.ldw);     // Z recompute, dX, dW
+          f.W = d_w + l.w(); f.ldw = l.ldw(); f.bias = l.has_bias() ? d_w + l.bias() : nullptr;
+          f.dst = Z; f.ld_dst = f.ldw; f.rpw_dst = l.nrows(); f.r0_dst = 0; f.col0_dst = 0;
+          f.act = 0; f.nrows = l.nrows(); f.B = B; f.T = 1; f.TP = 1;
+          t_begin(coords ? "linear_dx" : jac ? "linear_jac" : "linear_bwd", (coords ? 4.0 : 6.0) * B * l.nrows() * (double)l.w_rows() * f.ldw);     // Z recompute, dX, dW
           dqmc::launch_linear<real>(st, f);
-          a.W = f.W; a.ldw = f.ldw; a.nout = i[21]; a.nrows = i[20]; a.B = B; a.act = i[24];
+          a.W = f.W; a.ldw = f.ldw; a.nout = l.nout(); a.nrows = l.nrows(); a.B = B; a.act = l.act();
           a.Z = Z; a.dZ = reinterpret_cast<real*>(gw + o_dz); a.dZs = reinterpret_cast<real*>(gw + o_dzs);
-          a.dY = A(i[17]); a.ld_dst = bufs[i[17]].width; a.rpw_dst = bufs[i[17]].rows; a.r0_dst = i[18]; a.col0_dst = i[19];
-          if (i[25] >= 0) { a.dres = A(i[25]); a.ld_res = bufs[i[25]].width; a.rpw_res = bufs[i[25]].rows; a.r0_res = i[26]; }
-          a.res_scale = i[27] ? (real)0.70710678118654752440 : (real)1;
-          if (!coords && !jac) { a.dW = q.grad + i[22]; a.dbias = i[23] >= 0 ? q.grad + i[23] : nullptr; }   // else dX only
+          lin_dst_res(l, a, a.dY, a.dres, A);
+          if (!coords && !jac) { a.dW = q.grad + l.w(); a.dbias = l.has_bias() ? q.grad + l.bias() : nullptr; }   // else dX only
           a.part = reinterpret_cast<double*>(gw + o_part);
           a.wt = kw;
-          if (jac) dqmc::launch_linear_jac<real>(st, a, jo, i[22], i[23]);
+          if (jac) dqmc::launch_linear_jac<real>(st, a, jo, l.w(), l.bias());
           else dqmc::launch_linear_bwd<real>(st, a);
           if (kfac) {
             double* fA = q.factors + k_fac_off[opi];
-            dqmc::launch_kfac_factors<real>(st, a, i[23] >= 0, kw + B, fA, fA + kfac_dim_a(op) * kfac_dim_a(op),
-                                            reinterpret_cast<double*>(gw + o_kpart));
+            dqmc::launch_kfac_factors<real>(st, a, l.has_bias(), kw + B, fA, fA + l.kfac_dim_a() * l.kfac_dim_a(), reinterpret_cast<double*>(gw + o_kpart));
           }
           t_end();
           break;
         }
         case DQMC_OP_SPIN_MEAN:
-          dqmc::launch_spin_mean_bwd<real>(st, A(i[0]), A(i[1]), B, N, i[2], bufs[i[0]].width);
+          dqmc::launch_spin_mean_bwd<real>(st, A(v.spin_mean.src()), A(v.spin_mean.dst()), B, N, v.spin_mean.n_up(), bufs[v.spin_mean.src()].width);
           break;
         case DQMC_OP_ROW_SUM:
-          dqmc::launch_row_sum_bwd<real>(st, A(i[0]), A(i[1]), B, bufs[i[0]].rows, bufs[i[0]].width);
+          dqmc::launch_row_sum_bwd<real>(st, A(v.row_sum.src()), A(v.row_sum.dst()), B, bufs[v.row_sum.src()].rows, bufs[v.row_sum.src()].width);
           break;
         case DQMC_OP_CONV: {
           const int* t = &g_tab_of[4 * opi];
-          dqmc::launch_edge_rows_bwd<real>(st, A(i[0]), bufs[i[0]].rows, bufs[i[0]].width, bptr(i[1]), bufs[i[1]].rows, bufs[i[1]].width,
-                                           A(i[2]), bufs[i[2]].width, i[3], gt + t[0], t[1], i[6], B, N, 1.0);
-          dqmc::launch_conv_send_bwd<real>(st, A(i[1]), bufs[i[1]].rows, bufs[i[1]].width, bptr(i[0]), bufs[i[0]].rows, bufs[i[0]].width,
-                                           A(i[2]), bufs[i[2]].width, i[3], gt + t[2], t[3], i[6], B, N);
+          const dqmc::ConvOp& c = v.conv;
+          const dqmc_buf &eb = bufs[c.edge()], &nb = bufs[c.node()];
+          dqmc::launch_edge_rows_bwd<real>(st, A(c.edge()), eb.rows, eb.width, bptr(c.node()), nb.rows, nb.width, A(c.dst()), bufs[c.dst()].width,
+                                           c.dst_col0(), gt + t[0], t[1], c.width(), B, N, 1.0);
+          dqmc::launch_conv_send_bwd<real>(st, A(c.node()), nb.rows, nb.width, bptr(c.edge()), eb.rows, eb.width, A(c.dst()), bufs[c.dst()].width,
+                                           c.dst_col0(), gt + t[2], t[3], c.width(), B, N);
           break;
         }
         case DQMC_OP_EDGE_SUM: {
           const int* t = &g_tab_of[4 * opi];
-          dqmc::launch_edge_rows_bwd<real>(st, A(i[0]), bufs[i[0]].rows, bufs[i[0]].width, nullptr, 1, 4, A(i[2]), bufs[i[2]].width, i[3],
-                                           gt + t[0], t[1], i[6], B, N, 1.0 / (double)(i[1] > 0 ? i[1] : 1));
+          const dqmc::EdgeSumOp& e = v.edge_sum;
+          dqmc::launch_edge_rows_bwd<real>(st, A(e.edge()), bufs[e.edge()].rows, bufs[e.edge()].width, nullptr, 1, 4, A(e.dst()), bufs[e.dst()].width,
+                                           e.dst_col0(), gt + t[0], t[1], e.width(), B, N, e.scale());
           break;
         }
-        case DQMC_OP_CONST:
-          emit_partials((const real*)A(i[0]), (long)bufs[i[0]].rows * bufs[i[0]].width, bufs[i[0]].rows * bufs[i[0]].width, i[1]);
+        case DQMC_OP_CONST: {
+          const dqmc_buf& cb = bufs[v.cst.dst()];
+          emit_partials((const real*)A(v.cst.dst()), (long)cb.rows * cb.width, cb.rows * cb.width, v.cst.table());
           break;
+        }
         case DQMC_OP_ORBITALS: {
-          const int n_env = i[6] > 0 ? i[6] : 1, KN = sys.n_det * N, L = sys.n_nuc * n_env;
+          const dqmc::OrbitalsOp& o = v.orb;
+          const int n_env = o.n_env(), KN = sys.n_det * N, L = sys.n_nuc * n_env;
           double* pw = reinterpret_cast<double*>(gw + o_orb);
           t_begin("orbitals_bwd", 0);
-          dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[0]), A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
-                                          d_w + i[4], d_w + i[5], coords ? nullptr : pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det,
+          dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(o.src()), bufs[o.src()].width, A(o.src()), A(o.dst()), bufs[o.dst()].width, d_w + o.w(0),
+                                          d_w + o.w(1), d_w + o.w(2), d_w + o.w(3), coords ? nullptr : pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det,
                                           sys.norm_eps);
           if (coords)
-            dqmc::launch_orbitals_coords<real>(st, r, R, bptr(i[0]), bufs[i[0]].width, A(i[1]), bufs[i[1]].width, d_w + i[2], d_w + i[3],
-                                               d_w + i[4], d_w + i[5], B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps,
+            dqmc::launch_orbitals_coords<real>(st, r, R, bptr(o.src()), bufs[o.src()].width, A(o.dst()), bufs[o.dst()].width, d_w + o.w(0),
+                                               d_w + o.w(1), d_w + o.w(2), d_w + o.w(3), B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det, sys.norm_eps,
                                                slot + 3 * (size_t)c_slot0[opi], c_n_slots);
-          for (int t = 0; t < 4; ++t) emit_partials((const double*)pw + (size_t)t * KN * L, 4L * KN * L, KN * L, i[2 + t]);
+          for (int t = 0; t < 4; ++t) emit_partials((const double*)pw + (size_t)t * KN * L, 4L * KN * L, KN * L, o.w(t));
           t_end();
           break;
         }
         case DQMC_OP_SLOGDET:
           t_begin("slogdet_bwd", 0);
-          dqmc::launch_slogdet_bwd<real>(st, bptr(i[0]), bufs[i[0]].width, dL, A(i[0]), B, sys.n_det, N);
+          dqmc::launch_slogdet_bwd<real>(st, bptr(v.slogdet.src()), bufs[v.slogdet.src()].width, dL, A(v.slogdet.src()), B, sys.n_det, N);
           t_end();
           break;
         case DQMC_OP_FINAL: {
+          const dqmc::FinalOp& fin = v.fin;
           dqmc::FinalBwdArgs<real> a{};
           a.r = r;
           a.logdet = reinterpret_cast<double*>(d_ws + off_logdet);
           a.sign_k = reinterpret_cast<int32_t*>(d_ws + off_signk);
-          a.cc = i[1] >= 0 ? d_w + i[1] : nullptr;
-          a.alphas = d_w + i[3];
-          a.cusp_kind = i[2]; a.same_scale = op.f[0]; a.anti_scale = op.f[1]; a.eps = sys.norm_eps;
+          a.cc = fin.has_conf_coeff() ? d_w + fin.conf_coeff() : nullptr;
+          a.alphas = d_w + fin.alphas();
+          a.cusp_kind = fin.cusp_kind(); a.same_scale = fin.same_scale(); a.anti_scale = fin.anti_scale(); a.eps = sys.norm_eps;
           a.logpsi = lp; a.sign = sg;
           a.cot = q.mode == Rev::Vjp ? q.cot : nullptr;      // every other mode runs a unit cotangent
-          a.djas = i[0] >= 0 ? A(i[0]) : nullptr;
-          a.jas_ld = i[0] >= 0 ? bufs[i[0]].rows * bufs[i[0]].width : 0;
+          a.djas = fin.has_jastrow() ? A(fin.jastrow()) : nullptr;
+          a.jas_ld = fin.has_jastrow() ? bufs[fin.jastrow()].rows * bufs[fin.jastrow()].width : 0;
           a.dL = dL;
           a.pw = reinterpret_cast<double*>(gw + o_pw);
           a.B = B; a.N = N; a.n_up = sys.n_up; a.K = sys.n_det;
           dqmc::launch_final_bwd<real>(st, a);
-          if (coords && i[2])
-            dqmc::launch_cusp_coords<real>(st, r, d_w + i[3], i[2], op.f[0], op.f[1], sys.norm_eps, B, N, sys.n_up,
+          if (coords && fin.cusp_kind())
+            dqmc::launch_cusp_coords<real>(st, r, d_w + fin.alphas(), fin.cusp_kind(), fin.same_scale(), fin.anti_scale(), sys.norm_eps, B, N, sys.n_up,
                                            slot + 3 * (size_t)c_slot0[opi], c_n_slots);
-          if (i[1] >= 0) emit_partials((const double*)a.pw, sys.n_det + 2, sys.n_det, i[1]);
-          emit_partials((const double*)a.pw + sys.n_det, sys.n_det + 2, 2, i[3]);
+          if (fin.has_conf_coeff()) emit_partials((const double*)a.pw, sys.n_det + 2, sys.n_det, fin.conf_coeff());
+          emit_partials((const double*)a.pw + sys.n_det, sys.n_det + 2, 2, fin.alphas());
           break;
         }
         default:

@@ -25,6 +25,7 @@
 // DESIGN.md section 4) showed ~3.4 k cycles of such setup per unit against ~1.2 k cycles of MFMA work.
 #include "common.h"
 #include "kernels.h"
+#include "op_view.h"          // slot constants of dqmc_op::i
 #include "spec_device.h"      // fused2_det (shared with the plan-specialised sub-step kernels)
 
 #ifndef DQMC_UNIFORM
@@ -483,10 +484,10 @@ __device__ __forceinline__ void fused2_slater_entries(const Fused2Args<real>& a,
   HIP_DYNAMIC_SHARED(char, smem_raw)
   const real* smem = reinterpret_cast<const real*>(smem_raw);
   const int tid = threadIdx.x, nthr = blockDim.x, WT = a.WT, N = a.li.N, K = a.K, n_up = a.n_up, n_nuc = a.n_nuc, KN = K * N;
-  const BufPtr bf = (BufPtr)a.fbufs + op->i[0];
+  const BufPtr bf = (BufPtr)a.fbufs + op->i[ORB_SRC];
   const int bo = bf->off, bs = bf->stride;
-  const int n_env = op->i[6] > 0 ? op->i[6] : 1;
-  const int o_pu = op->i[2], o_pd = op->i[3], o_zu = op->i[4], o_zd = op->i[5];
+  const int n_env = op->i[ORB_N_ENV] > 0 ? op->i[ORB_N_ENV] : 1;
+  const int o_pu = op->i[ORB_PI_UP], o_pd = op->i[ORB_PI_DOWN], o_zu = op->i[ORB_ZETA_UP], o_zd = op->i[ORB_ZETA_DOWN];
   constexpr int WCH = 4;
   for (int q = tid; q < N * KN; q += nthr) {
     const int el = q / KN, kmu = q - el * KN;
@@ -559,8 +560,8 @@ __device__ __forceinline__ void fused2_generic(const Fused2Args<real>& a, OpPtr 
   // LDS rows of the same column; walkers beyond the batch (wl >= nw) are skipped.
   switch (kind) {
     case DQMC_OP_FEAT_EN: {
-      const BufPtr x = fbs + op->i[0];
-      const int xo = x->off, xs = x->stride, xw = x->width, lr = op->i[1], sp = op->i[2];
+      const BufPtr x = fbs + op->i[FEN_DST];
+      const int xo = x->off, xs = x->stride, xw = x->width, lr = op->i[FEN_LOG_RESCALE], sp = op->i[FEN_USE_SPIN];
       for (int e = tid; e < N * n_nuc * WT; e += nthr) {
         const int wl = e & wtm1, q = e >> sh;
         const int el = q / n_nuc, n = q - el * n_nuc;
@@ -581,9 +582,9 @@ __device__ __forceinline__ void fused2_generic(const Fused2Args<real>& a, OpPtr 
       break;
     }
     case DQMC_OP_FEAT_EE: {
-      const BufPtr eb = fbs + op->i[0];
-      const int eo = eb->off, es = eb->stride, n_rows = op->i[2], lr = op->i[3];
-      const int32_t* pairs = itab + op->i[1];
+      const BufPtr eb = fbs + op->i[FEE_DST];
+      const int eo = eb->off, es = eb->stride, n_rows = op->i[FEE_N_ROWS], lr = op->i[FEE_LOG_RESCALE];
+      const int32_t* pairs = itab + op->i[FEE_TABLE];
       for (int e = tid; e < n_rows * WT; e += nthr) {
         const int wl = e & wtm1, kr = e >> sh;
         if (wl >= nw) continue;
@@ -599,8 +600,8 @@ __device__ __forceinline__ void fused2_generic(const Fused2Args<real>& a, OpPtr 
       break;
     }
     case DQMC_OP_SPIN_MEAN: {
-      const BufPtr x = fbs + op->i[0];
-      const BufPtr m = fbs + op->i[1];
+      const BufPtr x = fbs + op->i[SPM_SRC];
+      const BufPtr m = fbs + op->i[SPM_DST];
       const int xo = x->off, xs = x->stride, W = x->width, mo = m->off, ms = m->stride;
       const real inv_up = n_up > 0 ? (real)1 / (real)n_up : (real)0, inv_dn = N > n_up ? (real)1 / (real)(N - n_up) : (real)0;
       for (int e = tid; e < W * 2 * WT; e += nthr) {
@@ -616,13 +617,13 @@ __device__ __forceinline__ void fused2_generic(const Fused2Args<real>& a, OpPtr 
     case DQMC_OP_CONV:
     case DQMC_OP_EDGE_SUM: {
       const bool conv = kind == DQMC_OP_CONV;
-      const BufPtr we = fbs + op->i[0];
-      const BufPtr out = fbs + op->i[2];
-      const BufPtr hx = conv ? fbs + op->i[1] : we;
+      const BufPtr we = fbs + op->i[CNV_EDGE];
+      const BufPtr out = fbs + op->i[CNV_DST];
+      const BufPtr hx = conv ? fbs + op->i[CNV_NODE] : we;
       const int wo = we->off, ws_ = we->stride, ho = hx->off, hs = hx->stride, oo = out->off, os = out->stride;
-      const real scale = conv ? (real)1 : (real)(1.0 / (double)(op->i[1] > 0 ? op->i[1] : 1));
-      const int32_t* tab = itab + op->i[4];
-      const int S = op->i[5], W = op->i[6], col0 = op->i[3];
+      const real scale = conv ? (real)1 : (real)(1.0 / (double)(op->i[ESUM_DIVISOR] > 0 ? op->i[ESUM_DIVISOR] : 1));
+      const int32_t* tab = itab + op->i[CNV_TABLE];
+      const int S = op->i[CNV_S], W = op->i[CNV_WIDTH], col0 = op->i[CNV_DST_COL0];
       const bool w_pow2 = (W & (W - 1)) == 0;
       const int w_sh = 31 - __builtin_clz((unsigned)(W > 0 ? W : 1));
       for (int e = tid; e < N * W * WT; e += nthr) {
@@ -640,8 +641,8 @@ __device__ __forceinline__ void fused2_generic(const Fused2Args<real>& a, OpPtr 
       break;
     }
     case DQMC_OP_ROW_SUM: {
-      const BufPtr x = fbs + op->i[0];
-      const BufPtr s = fbs + op->i[1];
+      const BufPtr x = fbs + op->i[RSUM_SRC];
+      const BufPtr s = fbs + op->i[RSUM_DST];
       const int xo = x->off, xs = x->stride, W = x->width, rows = x->rows, so = s->off, ss = s->stride;
       for (int e = tid; e < W * WT; e += nthr) {
         const int wl = e & wtm1, c = e >> sh;
@@ -653,7 +654,7 @@ __device__ __forceinline__ void fused2_generic(const Fused2Args<real>& a, OpPtr 
     }
     case DQMC_OP_ORBITALS: {
       if (a.mc.enabled) break;                     // sub-step mode: the tail builds the Slater matrices itself
-      const BufPtr orb = fbs + op->i[1];
+      const BufPtr orb = fbs + op->i[ORB_DST];
       const int ow = orb->width, orows = orb->rows;
       real* orb_g = reinterpret_cast<real*>(a.ws + orb->goff) + (long)blockIdx.x * WT * orows * ow;
       fused2_slater_entries<real>(a, op, nw, r, [&](int wl, int kd, int el, int mu, real v) {
