@@ -63,6 +63,7 @@ SIGNATURES = [
     ('dqmc_log_psi_kfac', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ('dqmc_log_psi_grad_coords', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ('dqmc_hf_force', c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
+    ('dqmc_ecp_force', c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p]),
     ('dqmc_set_pretrain_target', c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_double),
                                          POINTER(c_double), c_int, c_int, POINTER(c_double), c_int, POINTER(c_int32), POINTER(c_double)]),
     ('dqmc_pretrain_target', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

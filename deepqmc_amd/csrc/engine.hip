@@ -7,7 +7,7 @@
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
 // float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
-// engine_coords.inl, with the force estimators), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
+// engine_coords.inl, with the force estimators; engine_ecp_force.inl, the ECP force), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
 // step (engine_optim.inl), the KFAC preconditioner on its vectors (engine_kfacopt.inl) -- and
 // are included inside the struct body: one translation unit, as before.  The slot layout of dqmc_op lives in op_view.h: all of
 // the above read an op through its named views, never by slot number.
@@ -117,6 +117,8 @@ struct dqmc_ctx {
   virtual int log_psi_grad_coords(const void* r, const void* R, int B, void* grad_r, void* grad_R, void* logpsi, int32_t* sign) = 0;
   virtual int hf_force(int est, const void* r, const void* R, int B, const void* grad_r, const void* grad_R, const void* e_loc,
                        double energy, double* force) = 0;
+  virtual int ecp_force(int est, int all_rows, const void* r, const void* R, int B, const void* e_loc, double energy, double* force,
+                        double* parts) = 0;
   virtual int log_psi_kfac(const void* r, const void* R, int B, const void* cot, double* grad, double* factors, void* rest,
                            void* logpsi, int32_t* sign) = 0;
   virtual int set_pretrain_target(int n_shells, const int32_t* atom, const int32_t* l, const int32_t* n_prim, const double* coeffs,
@@ -491,6 +493,7 @@ struct Engine : dqmc_ctx {
 #include "engine_jac.inl"
 #include "engine_kfac.inl"
 #include "engine_coords.inl"
+#include "engine_ecp_force.inl"
 #include "engine_pretrain.inl"
 #include "engine_optim.inl"
 #include "engine_kfacopt.inl"
@@ -591,6 +594,12 @@ int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, in
   if (!ctx || !r || !R || !force) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->hf_force(estimator, r, R, B, grad_r, grad_R, e_loc, energy, force);
+}
+int dqmc_ecp_force(dqmc_ctx* ctx, int estimator, int all_rows, const void* r, const void* R, int B, const void* e_loc, double energy,
+                   double* force, double* parts) {
+  if (!ctx || !r || !R || !force) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->ecp_force(estimator, all_rows, r, R, B, e_loc, energy, force, parts);
 }
 int dqmc_set_pretrain_target(dqmc_ctx* ctx, int n_shells, const int32_t* shell_atom, const int32_t* shell_l, const int32_t* shell_n_prim,
                              const double* coeffs, const double* zetas, int n_ao, int n_mo, const double* mo_coeffs, int n_conf,

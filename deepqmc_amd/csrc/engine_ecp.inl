@@ -83,6 +83,7 @@
     HIP_TRY(hipStreamSynchronize(st));
     d_ecp_loc.reset(); d_ecp_nl.reset(); d_ecp_nuc.reset();
     ecp_nt_loc = ecp_n_nl = ecp_L = ecp_nt_nl = 0;
+    ecp_is_set = false;
     ecp_loc_h.clear(); ecp_loc_nt_h = 0;
     ecp_nl_h.clear(); ecp_nl_L_h = ecp_nl_nt_h = 0;
     if (loc && n_t_loc > 0 && sizeof(real) == 4) { ecp_loc_h.assign(loc, loc + (size_t)sys.n_nuc * 6 * n_t_loc); ecp_loc_nt_h = n_t_loc; }
@@ -112,6 +113,7 @@
         ecp_n_nl = (int)nuc.size(); ecp_L = n_l; ecp_nt_nl = n_t_nl;
       }
     }
+    ecp_is_set = true;
     return DQMC_OK;
   }
   int ecp_rotation(uint64_t seed, const void* phi) override { ecp_seed = seed; ecp_phi = phi; return DQMC_OK; }

@@ -291,6 +291,21 @@ template <typename real> void launch_ecp_points(hipStream_t st, const EcpArgs& a
 template <typename real>
 void launch_ecp_reduce(hipStream_t st, const EcpArgs& a, const real* logq, const int32_t* signq, const real* log0,
                        const int32_t* sign0, real* e_loc, real* stats, real* v_nl_out);
+// Hellmann-Feynman force of a Gaussian-type ECP Hamiltonian (dqmc_ecp_force).  Configurations of a walker chunk: [0, nb) the
+// walkers themselves, then 11 per (walker, non-local nucleus j, electron i) triple t = (bl n_nl + j) N + i (vertices 1 .. 11;
+// vertex 0 is the electron itself).  lq / sq / gr / gR: log|psi|, sign, d log|psi| / dr [n_cfg][N][3] and / dR [n_cfg][n_nuc][3]
+// of those configurations (the Coords reverse pass); gj: double[nb][n_nl][n_nuc][3], nucleus j's part of the non-local gradient.
+constexpr int ECPF_NQ = 11;      // configurations per (walker, nucleus, electron) triple: vertices 1 .. 11
+template <typename real> void launch_ecp_force_points(hipStream_t st, const EcpArgs& a, real* rq);
+template <typename real>
+void launch_ecp_force_reduce(hipStream_t st, const EcpArgs& a, int n_nuc, int all_rows, const real* lq, const int32_t* sq, const real* gr,
+                             const real* gR, double* gj);
+// force[b][K] = part0 + part1 (+ the zero-bias term when e_loc is given); part0 = F_nuc - dV_loc/dR, part1 = -sum_j gj (0 when
+// gj is nullptr); lq / sq / gR: the chunk's own walkers, or nullptr when no reverse pass has run; part0 / part1 may be nullptr.
+template <typename real>
+void launch_ecp_force_local(hipStream_t st, const EcpArgs& a, int n_nuc, const double* Z, const double* loc, int nt_loc, const double* gj,
+                            const real* lq, const int32_t* sq, const real* gR, const real* e_loc, double energy, double* force,
+                            double* part0, double* part1);
 template <typename real>
 void launch_ph_coeffs(hipStream_t st, const real* r, const real* R, const int32_t* ph_nuc, int n_ph, const double* rv_loc,
                       const double* rv_l2, int n_grid, double r_max, int B, int N, double* phq);

@@ -8,6 +8,8 @@
 // SURVEY.md section 8); they run through the ordinary value path on a batch of "quadrature walkers"
 // that k_ecp_points writes, and k_ecp_reduce folds the psi ratios back into E_loc.
 // The local part (gaussian_type_ecp.py:127-159) lives in k_final next to the Coulomb terms.
+// Further down: the mixed-precision quadrature of float32 contexts, the Hellmann-Feynman force of an ECP Hamiltonian
+// (gradient of the local and non-local terms with respect to the nuclei, dqmc_ecp_force) and the pseudo-Hamiltonian.
 #include "common.h"
 #include "kernels.h"
 
@@ -273,6 +275,265 @@ void launch_ecp_reduce(hipStream_t st, const EcpArgs& a, const real* logq, const
                      signq, log0, sign0, e_loc, stats, v_nl_out);
 }
 
+// ---- Hellmann-Feynman force of a Gaussian-type ECP Hamiltonian (dqmc_ecp_force; engine_ecp_force.inl) ------------------------
+// Reference: force.py:286-299 (evaluate_hf_force_bare with hamil.pot.grad_nonloc_potential), ecp/gaussian_type_ecp.py:257-330,
+// ecp/ecp_force_utils.py.  Per walker, F_I = F_nuc,I(Z) - dV_loc/dR_I - G_I with G the gradient of the non-local term.  For the
+// nucleus I = nl_nuc[j], electron i and vertex q (x_q = R_I + rho w_q, d = r_i - R_I, rho = |d|, ecp_vertex above):
+//   ratio_q        = s_q s_0 exp(log_q - log_0)
+//   dratio_q/dR_K  = ratio_q (gR_q[K] - gR_0[K] + [K == I] J_q^T gr_q[i]),     J_q = dx_q/dR_I (ecp_vertex_jt below)
+//   G_K           += sum_i sum_l (2l+1)/12 [ [K == I] dv_l/dR_I sum_q P_l(cos theta_q) ratio_q + v_l sum_q P_l(cos theta_q) dratio_q/dR_K ]
+// with gr_q / gR_q = d log|psi| / dr, / dR at the configuration with electron i at x_q (the Coords reverse pass) and gR_0 the
+// same at the walker itself.  Vertex 0 is the electron itself whatever R is (ratio 1, derivative 0): it is not part of the
+// batch (11 configurations per triple) and enters the dv_l term with ratio 1.  The sums over l are taken first:
+//   c_q = sum_l (2l+1)/12 v_l P_l(cos theta_q),   e_q = sum_l (2l+1)/12 (sum_t alpha_lt beta_lt e^{-alpha_lt rho^2}) P_l(cos theta_q)
+//   G_K = sum_i [ sum_q c_q ratio_q (gR_q[K] - gR_0[K]) ] + [K == I] sum_i [ sum_q ratio_q (2 d e_q + c_q J_q^T gr_q[i]) ].
+
+template <typename real>
+__device__ __forceinline__ double ecp_angle_of(const EcpArgs& a, int b, int j, int i) {       // the angle k_ecp_points uses
+  const long bg = a.walker_idx ? (long)a.walker_idx[b] : (long)b;
+  if (a.phi != nullptr) {
+    const long pidx = (bg * a.n_nl + j) * a.N + i;
+    return a.phi_f32 ? (double)reinterpret_cast<const float*>(a.phi)[pidx] : (double)reinterpret_cast<const real*>(a.phi)[pidx];
+  }
+  uint32_t o[4];
+  philox4x32(a.seed, 0x45435000ull + (uint64_t)j, (uint64_t)bg * (uint64_t)a.N + (uint64_t)i, o);
+  return u01(o[0], o[1]) * 0.62831853071795865;
+}
+
+// J_q^T g for vertex q of ecp_vertex: x_q = R + rho w(theta, phi), theta = arccos(d_z / rho), phi = atan2(d_y, d_x), so
+//   J_q = dx_q/dR = 1 - [ w dhat^T + rho (d_theta w)(grad_d theta)^T + rho (d_phi w)(grad_d phi)^T ],
+//   grad_d theta = (cos(theta) dhat - e_z) / (rho sin(theta)),   grad_d phi = (-d_y, d_x, 0) / (d_x^2 + d_y^2).
+// The same frame (ct, st, phi, u, v) as ecp_vertex; singular on the axis d || e_z, as the reference's autograd is.
+__device__ __forceinline__ void ecp_vertex_jt(const double d[3], double phr, int q, const double g[3], double out[3]) {
+  const double dx = d[0], dy = d[1], dz = d[2];
+  const double radius = sqrt(dx * dx + dy * dy + dz * dz);
+  double ct = dz / radius;
+  ct = ct < -1.0 ? -1.0 : (ct > 1.0 ? 1.0 : ct);
+  const double st = sqrt(1.0 - ct * ct);
+  const double phi = atan2(dy, dx);
+  const double cq = ico_cos(q), sq = sqrt(1.0 - cq * cq), pq = ico_phi(q) + phr;
+  const double ux = sq * cos(pq), uy = sq * sin(pq), uz = cq;
+  const double vx = ct * ux + st * uz, vy = uy, vz = -st * ux + ct * uz;
+  const double tx = -st * ux + ct * uz, tz = -ct * ux - st * uz;          // d_theta v (its y component is 0)
+  const double cp = cos(phi), sp = sin(phi);
+  const double wg = (cp * vx - sp * vy) * g[0] + (sp * vx + cp * vy) * g[1] + vz * g[2];        // w . g
+  const double tg = cp * tx * g[0] + sp * tx * g[1] + tz * g[2];                                // d_theta w . g
+  const double pg = (-sp * vx - cp * vy) * g[0] + (cp * vx - sp * vy) * g[1];                   // d_phi w . g
+  const double hx = dx / radius, hy = dy / radius, hz = dz / radius;
+  const double it = tg / st, ip = pg * radius / (dx * dx + dy * dy);
+  out[0] = g[0] - hx * wg - (ct * hx) * it + dy * ip;
+  out[1] = g[1] - hy * wg - (ct * hy) * it - dx * ip;
+  out[2] = g[2] - hz * wg - (ct * hz - 1.0) * it;
+}
+
+// Configurations of the chunk [b0, b0 + nb): [0, nb) the walkers themselves, then ECPF_NQ per triple t = (bl n_nl + j) N + i:
+// configuration nb + t ECPF_NQ + (q - 1) is walker b0 + bl with electron i at vertex q.  One thread per coordinate.
+template <typename real>
+__global__ void __launch_bounds__(256) k_ecp_force_points(const EcpArgs a, real* __restrict__ rq) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = a.N;
+  const long per_cfg = (long)N * 3;
+  const long n_cfg = (long)a.nb + (long)ECPF_NQ * a.nb * a.n_nl * N;
+  if (idx >= n_cfg * per_cfg) return;
+  const long cfg = idx / per_cfg;
+  const int ec = (int)(idx - cfg * per_cfg), e = ec / 3, c = ec - 3 * e;
+  const real* rall = reinterpret_cast<const real*>(a.r);
+  if (cfg < a.nb) { rq[idx] = rall[(long)(a.b0 + cfg) * per_cfg + ec]; return; }
+  const long k = cfg - a.nb;
+  const long t = k / ECPF_NQ;
+  const int q = 1 + (int)(k - t * ECPF_NQ);
+  const int i = (int)(t % N), j = (int)((t / N) % a.n_nl), bl = (int)(t / ((long)N * a.n_nl));
+  const int b = a.b0 + bl;
+  const real* r = rall + (long)b * per_cfg;
+  if (e != i) { rq[idx] = r[ec]; return; }
+  const real* R = reinterpret_cast<const real*>(a.R) + 3 * a.nl_nuc[j];
+  const double ri[3] = {(double)r[3 * i], (double)r[3 * i + 1], (double)r[3 * i + 2]};
+  const double Rn[3] = {(double)R[0], (double)R[1], (double)R[2]};
+  double x[3];
+  ecp_vertex(ri, Rn, ecp_angle_of<real>(a, b, j, i), q, x);
+  rq[idx] = (real)x[c];
+}
+
+__device__ __forceinline__ double ecpf_grp16_sum(double v) {      // fixed tree over the 16 lanes of a group
+  for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// One wave per (walker bl of the chunk, non-local nucleus j): gj[bl][j][K][3] = that nucleus's contribution to G_K, double.
+// Lane = (group g = lane / 16, vertex q = lane % 16; q >= 12 idle): group g takes the electrons g, g + 4, ...  Per electron
+// the vertices are summed by the xor tree of the group; the electrons are then summed in index order.  No atomics.
+// all_rows == 0: only the row K == I = nl_nuc[j] is formed, the others are zero.
+template <typename real>
+__global__ void __launch_bounds__(64) k_ecp_force_reduce(const EcpArgs a, int n_nuc, int all_rows, const real* __restrict__ lq,
+                                                         const int32_t* __restrict__ sq, const real* __restrict__ gr,
+                                                         const real* __restrict__ gR, double* __restrict__ gj) {
+  __shared__ double s_w[GRAD_GJ_NMAX][16];       // c_q ratio_q of (electron, vertex); 0 for q = 0 and the idle lanes
+  __shared__ double s_own[GRAD_GJ_NMAX][3];      // sum_q ratio_q (2 d e_q + c_q J_q^T gr_q[i]) per electron
+  __shared__ double s_part[GRAD_GJ_NMAX][3];     // sum_q c_q ratio_q (gR_q[K] - gR_0[K]) per electron, for the current K
+  const int lane = threadIdx.x, g = lane >> 4, q = lane & 15;
+  const int N = a.N, n_nl = a.n_nl;
+  const int bl = blockIdx.x / n_nl, j = blockIdx.x - bl * n_nl;
+  const int b = a.b0 + bl, I = a.nl_nuc[j];
+  const real* r = reinterpret_cast<const real*>(a.r) + (long)b * N * 3;
+  const real* R = reinterpret_cast<const real*>(a.R) + 3 * I;
+  const double* nl = a.nl + (long)j * a.L * 2 * a.n_t;
+  const double l0 = (double)lq[bl];
+  const int s0 = sq[bl];
+  const long cfg0 = (long)a.nb + ((long)bl * n_nl + j) * N * ECPF_NQ;      // first configuration of the pair's triples
+  for (int i0 = 0; i0 < N; i0 += 4) {
+    const int i = i0 + g;
+    double own0 = 0.0, own1 = 0.0, own2 = 0.0, w = 0.0;
+    if (i < N && q < 12) {
+      const double d[3] = {(double)r[3 * i] - (double)R[0], (double)r[3 * i + 1] - (double)R[1], (double)r[3 * i + 2] - (double)R[2]};
+      const double d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+      const double x = ico_cos(q);
+      double cq = 0.0, eq = 0.0, pm = 1.0, p = x;
+      for (int l = 0; l < a.L; ++l) {
+        double pl = l == 0 ? 1.0 : x;                 // Legendre recurrence, as k_ecp_reduce
+        if (l >= 2) { pl = ((2 * l - 1) * x * p - (l - 1) * pm) / l; pm = p; p = pl; }
+        double vl = 0.0, al = 0.0;
+        for (int t = 0; t < a.n_t; ++t) {
+          const double alpha = nl[(l * 2) * a.n_t + t], term = nl[(l * 2 + 1) * a.n_t + t] * exp(-d2 * alpha);
+          vl += term; al += alpha * term;
+        }
+        cq += (2 * l + 1) / 12.0 * vl * pl;
+        eq += (2 * l + 1) / 12.0 * al * pl;
+      }
+      double ratio = 1.0, jt[3] = {0.0, 0.0, 0.0};
+      if (q > 0) {
+        const long cfg = cfg0 + (long)i * ECPF_NQ + (q - 1);
+        const double lg = (double)lq[cfg];
+        const int s = sq[cfg];
+        ratio = (s != 0 && lg - lg == 0) ? exp(lg - l0) * (double)(s * s0) : 0.0;      // an invalid numerator: ratio 0
+        const real* gq = gr + (cfg * N + i) * 3;
+        const double gv[3] = {(double)gq[0], (double)gq[1], (double)gq[2]};
+        ecp_vertex_jt(d, ecp_angle_of<real>(a, b, j, i), q, gv, jt);
+        w = cq * ratio;
+      }
+      own0 = ratio * (2.0 * d[0] * eq) + w * jt[0];
+      own1 = ratio * (2.0 * d[1] * eq) + w * jt[1];
+      own2 = ratio * (2.0 * d[2] * eq) + w * jt[2];
+    }
+    own0 = ecpf_grp16_sum(own0); own1 = ecpf_grp16_sum(own1); own2 = ecpf_grp16_sum(own2);
+    if (i < N) {
+      s_w[i][q] = w;
+      if (q == 0) { s_own[i][0] = own0; s_own[i][1] = own1; s_own[i][2] = own2; }
+    }
+  }
+  __syncthreads();
+  double* out = gj + (long)blockIdx.x * n_nuc * 3;
+  for (int K = 0; K < n_nuc; ++K) {
+    if (!all_rows && K != I) {
+      if (lane < 3) out[K * 3 + lane] = 0.0;
+      continue;
+    }
+    const real* g0 = gR + ((long)bl * n_nuc + K) * 3;
+    for (int i0 = 0; i0 < N; i0 += 4) {
+      const int i = i0 + g;
+      double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+      if (i < N && q > 0 && q < 12) {
+        const double w = s_w[i][q];
+        const real* gq = gR + ((cfg0 + (long)i * ECPF_NQ + (q - 1)) * n_nuc + K) * 3;
+        v0 = w * ((double)gq[0] - (double)g0[0]);
+        v1 = w * ((double)gq[1] - (double)g0[1]);
+        v2 = w * ((double)gq[2] - (double)g0[2]);
+      }
+      v0 = ecpf_grp16_sum(v0); v1 = ecpf_grp16_sum(v1); v2 = ecpf_grp16_sum(v2);
+      if (i < N && q == 0) { s_part[i][0] = v0; s_part[i][1] = v1; s_part[i][2] = v2; }
+    }
+    __syncthreads();
+    if (lane < 3) {
+      double s = 0.0;
+      for (int i = 0; i < N; ++i) s += s_part[i][lane];
+      if (K == I) {
+        double o = 0.0;
+        for (int i = 0; i < N; ++i) o += s_own[i][lane];
+        s += o;
+      }
+      out[K * 3 + lane] = s;
+    }
+    __syncthreads();
+  }
+}
+
+// One thread per (walker bl of the chunk, nucleus K): F_nuc(Z) - dV_loc/dR_K (nuclear repulsion of the valence charges, the
+// -Z/rho attraction and the local ECP terms of gaussian_type_ecp.py:127-159: with f_K the radial function of nucleus K,
+// dV_loc/dR_K = -sum_i f_K'(rho) d / rho), minus G_K summed over the non-local nuclei in index order, and the optional
+// zero-bias term -2 (e_loc - energy) gR_0[K].  lq / sq / gR: the walkers' own log|psi|, sign and d log|psi| / dR where a
+// reverse pass has run (else nullptr); a walker with sign 0 or a non-finite log|psi| gets NaN rows in force and parts[1].
+template <typename real>
+__global__ void __launch_bounds__(256) k_ecp_force_local(const EcpArgs a, int n_nuc, const double* __restrict__ Z,
+                                                         const double* __restrict__ loc, int nt_loc, const double* __restrict__ gj,
+                                                         const real* __restrict__ lq, const int32_t* __restrict__ sq,
+                                                         const real* __restrict__ gR, const real* __restrict__ e_loc, double energy,
+                                                         double* __restrict__ force, double* __restrict__ part0,
+                                                         double* __restrict__ part1) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)a.nb * n_nuc) return;
+  const int K = (int)(idx % n_nuc), bl = (int)(idx / n_nuc), N = a.N;
+  const long b = a.b0 + bl;
+  const real* r = reinterpret_cast<const real*>(a.r) + b * N * 3;
+  const real* R = reinterpret_cast<const real*>(a.R);
+  double f[3] = {0, 0, 0};
+  for (int J = 0; J < n_nuc; ++J) {           // nuclear repulsion, as k_hf_force
+    if (J == K) continue;
+    double d[3], d2 = 0;
+    for (int c = 0; c < 3; ++c) { d[c] = (double)R[K * 3 + c] - (double)R[J * 3 + c]; d2 += d[c] * d[c]; }
+    const double w = Z[K] * Z[J] / (d2 * sqrt(d2));
+    for (int c = 0; c < 3; ++c) f[c] += w * d[c];
+  }
+  const double* p = loc ? loc + (long)K * 6 * nt_loc : nullptr;
+  double fe[3] = {0, 0, 0};
+  for (int i = 0; i < N; ++i) {
+    double d[3], d2 = 0;
+    for (int c = 0; c < 3; ++c) { d[c] = (double)r[i * 3 + c] - (double)R[K * 3 + c]; d2 += d[c] * d[c]; }
+    const double rho = sqrt(d2);
+    double fp = Z[K] / d2;                     // f'(rho) of -Z / rho
+    if (p)
+      for (int t = 0; t < nt_loc; ++t) {       // beta/rho e^{-alpha rho^2}, beta e^{-alpha rho^2}, beta rho e^{-alpha rho^2}
+        fp -= p[1 * nt_loc + t] * exp(-p[0 * nt_loc + t] * d2) * (1.0 / d2 + 2.0 * p[0 * nt_loc + t]);
+        fp -= p[3 * nt_loc + t] * exp(-p[2 * nt_loc + t] * d2) * (2.0 * p[2 * nt_loc + t] * rho);
+        fp += p[5 * nt_loc + t] * exp(-p[4 * nt_loc + t] * d2) * (1.0 - 2.0 * p[4 * nt_loc + t] * d2);
+      }
+    for (int c = 0; c < 3; ++c) fe[c] += fp * d[c] / rho;
+  }
+  const bool valid = !lq || (sq[bl] != 0 && (double)lq[bl] - (double)lq[bl] == 0);
+  const double de = e_loc ? -2.0 * ((double)e_loc[b] - energy) : 0.0;
+  for (int c = 0; c < 3; ++c) {
+    const double p0 = f[c] + fe[c];
+    double p1 = 0.0;
+    if (gj) {
+      double s = 0.0;
+      for (int j = 0; j < a.n_nl; ++j) s += gj[(((long)bl * a.n_nl + j) * n_nuc + K) * 3 + c];
+      p1 = valid ? 0.0 - s : NAN;
+    }
+    double tot = p0 + p1;
+    if (e_loc) tot += de * (double)gR[((long)bl * n_nuc + K) * 3 + c];
+    if (!valid) tot = NAN;
+    force[(b * n_nuc + K) * 3 + c] = tot;
+    if (part0) { part0[(b * n_nuc + K) * 3 + c] = p0; part1[(b * n_nuc + K) * 3 + c] = p1; }
+  }
+}
+
+template <typename real> void launch_ecp_force_points(hipStream_t st, const EcpArgs& a, real* rq) {
+  const long n = ((long)a.nb + (long)ECPF_NQ * a.nb * a.n_nl * a.N) * a.N * 3;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ecp_force_points<real>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, rq);
+}
+template <typename real>
+void launch_ecp_force_reduce(hipStream_t st, const EcpArgs& a, int n_nuc, int all_rows, const real* lq, const int32_t* sq, const real* gr,
+                             const real* gR, double* gj) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ecp_force_reduce<real>), dim3((unsigned)(a.nb * a.n_nl)), dim3(64), 0, st, a, n_nuc, all_rows, lq, sq,
+                     gr, gR, gj);
+}
+template <typename real>
+void launch_ecp_force_local(hipStream_t st, const EcpArgs& a, int n_nuc, const double* Z, const double* loc, int nt_loc, const double* gj,
+                            const real* lq, const int32_t* sq, const real* gR, const real* e_loc, double energy, double* force,
+                            double* part0, double* part1) {
+  const long n = (long)a.nb * n_nuc;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ecp_force_local<real>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, n_nuc, Z, loc, nt_loc,
+                     gj, lq, sq, gR, e_loc, energy, force, part0, part1);
+}
+
 // ---- pseudo-Hamiltonian coefficients ----------------------------------------------------------------------------
 // Reference: ecp/pseudo_hamiltonian.py:173-234.  For electron i of walker b, with d_I = r_i - R_I, rho_I = |d_I|
 // (plain norm, geom/general.py:19-21) and the tabulated radial functions rV_loc / rV_L2 of the PH nuclei (linear
@@ -342,7 +603,13 @@ void launch_ph_coeffs(hipStream_t st, const real* r, const real* R, const int32_
                                        const double*, int, double, int, int, double*);                             \
   template void launch_ecp_points<real>(hipStream_t, const EcpArgs&, real*);                                       \
   template void launch_ecp_reduce<real>(hipStream_t, const EcpArgs&, const real*, const int32_t*, const real*,     \
-                                        const int32_t*, real*, real*, real*);
+                                        const int32_t*, real*, real*, real*);                                      \
+  template void launch_ecp_force_points<real>(hipStream_t, const EcpArgs&, real*);                                 \
+  template void launch_ecp_force_reduce<real>(hipStream_t, const EcpArgs&, int, int, const real*, const int32_t*,  \
+                                              const real*, const real*, double*);                                  \
+  template void launch_ecp_force_local<real>(hipStream_t, const EcpArgs&, int, const double*, const double*, int,  \
+                                             const double*, const real*, const int32_t*, const real*, const real*, \
+                                             double, double*, double*, double*);
 DQMC_INST(float)
 DQMC_INST(double)
 #undef DQMC_INST

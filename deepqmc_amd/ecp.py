@@ -6,8 +6,8 @@ exponent, 1 = coefficient) and the non-local channels `nl[n_nuc, l_max+1, 2, n_t
 reference reads the bfd / ccECP coefficients from pyscf (`pyscf.gto.basis.load_ecp`); pyscf is neither
 vendored in the reference nor installed here, so tables are supplied by the caller in pyscf's own format
 (`ECP_TABLES`-style dict, see `GaussianTypeECP.from_tables`) or, if pyscf happens to be importable, looked up
-exactly as the reference does.  The arithmetic (local and non-local potential) runs in the HIP library
-(csrc/kernels_head.hip: k_final, csrc/kernels_ecp.hip).
+exactly as the reference does.  The arithmetic (local and non-local potential, and their gradients with respect to the
+nuclei) runs in the HIP library (csrc/kernels_head.hip: k_final, csrc/kernels_ecp.hip).
 """
 from __future__ import annotations
 
@@ -42,6 +42,13 @@ class GaussianTypeECP:
         assert self.loc_params.ndim == 4 and self.loc_params.shape[:3] == (n, 3, 2)
         assert self.nl_params.ndim == 4 and self.nl_params.shape[0] == n and self.nl_params.shape[2] == 2
         self.nuc_with_nl_pot = np.unique(np.nonzero(self.nl_params)[0])       # :121
+
+    def grad_nonloc_potential(self, wf, rng, phys_conf, params, rows='own'):
+        """gaussian_type_ecp.py:257-330 (the reference's name and argument order): the gradient of the non-local term with
+        respect to the nuclei, per walker, float64 [B, n_nuc, 3].  `wf` is the NeuralNetworkWaveFunction bound to the
+        Hamiltonian that holds this potential; `rng` the int seed of the quadrature rotation.  See deepqmc_amd.ecp_force."""
+        from .ecp_force import grad_nonloc_potential
+        return grad_nonloc_potential(wf.hamil, wf, rows)(rng, params, phys_conf)
 
     @classmethod
     def from_tables(cls, charges: Sequence[float], ecp_mask: Sequence[bool], tables: Dict[str, list]):

@@ -564,6 +564,39 @@ class Engine:
                                            ptr(grad_r), ptr(grad_R), ptr(e_loc), float(energy), force.data_ptr()))
         return force
 
+    def ecp_force(self, estimator: str, r, R=None, rng=None, ecp_phi=None, e_loc=None, energy: float = 0.0, rows='own',
+                  return_parts=False):
+        """Per-walker Hellmann-Feynman force of a Hamiltonian with a Gaussian-type ECP (dqmc_ecp_force; formulas in
+        include/dqmc.h), float64 [B, n_nuc, 3] on the device: F_I = F_nuc,I - dV_loc/dR_I - G_I with G the gradient of the
+        non-local term.  estimator: 'bare', or 'ac_zb' (bare - 2 (e_loc - energy) d log|psi| / dR_I; e_loc [B] in the engine's
+        dtype).  `rng` / `ecp_phi` key the quadrature rotation exactly as in `local_energy`: the same seed or angles give the
+        same vertices.  rows: 'own' keeps, for each non-local nucleus, only its own row of the ratio gradient (what the
+        reference computes); 'all' keeps every row, the full dV_nl/dR.  return_parts: (force, parts) with parts [2, B, n_nuc, 3]
+        = (F_nuc - dV_loc/dR, -G).  Walkers with sign 0 or a non-finite log|psi| get NaN rows.  Attention programs raise
+        DqmcError (-4)."""
+        if estimator not in ('bare', 'ac_zb'):
+            raise ValueError(f"unknown ECP force estimator {estimator!r}; one of ('bare', 'ac_zb')")
+        if rows not in ('own', 'all'):
+            raise ValueError(f"rows must be 'own' or 'all', not {rows!r}")
+        r = self._t(r)
+        B = r.shape[0]
+        assert r.shape[1:] == (self.N, 3)
+        if estimator == 'ac_zb':
+            if e_loc is None:
+                raise DqmcError("estimator 'ac_zb' needs e_loc")
+            if not isinstance(e_loc, torch.Tensor) or e_loc.dtype != self.dtype or not e_loc.is_contiguous() \
+                    or e_loc.device.type != self.device.type or tuple(e_loc.shape) != (B,):
+                raise DqmcError(f"'e_loc' must be a contiguous {self.dtype} tensor of shape {(B,)} on {self.device}")
+        else:
+            e_loc = None
+        self._set_ecp_rotation(B, rng, ecp_phi)
+        force = torch.empty(B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device)
+        parts = torch.empty(2, B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device) if return_parts else None
+        self._check(self.lib.dqmc_ecp_force(self._ctx, FORCE_ESTIMATORS.index(estimator), 1 if rows == 'all' else 0, r.data_ptr(),
+                                            self._R(R).data_ptr(), B, e_loc.data_ptr() if e_loc is not None else None, float(energy),
+                                            force.data_ptr(), parts.data_ptr() if parts is not None else None))
+        return (force, parts) if return_parts else force
+
     # ---- SCF-orbital pretraining: target, Slater matrices, their VJP, the fused loss step ----
     def set_pretrain_target(self, shells, mo_coeffs, confs, conf_coeffs):
         """Upload the (MC-)SCF target of this context (dqmc_set_pretrain_target).  shells: [(atom, (l, coeffs, zetas))] as
@@ -639,6 +672,21 @@ class Engine:
                                                      float(B if n_total is None else n_total), grad.data_ptr(), ps.data_ptr()))
         return ps, grad
 
+    def _set_ecp_rotation(self, B, rng, ecp_phi):
+        """The quadrature rotation of the following call (dqmc_ecp_rotation): an int seed, or explicit angles [B, n_ecp_nl, N].
+        Nothing to do without a non-local ECP channel."""
+        if getattr(getattr(self.hamil, 'pot', None), 'nl_params', np.zeros(0)).size:
+            if rng is None and ecp_phi is None:      # gaussian_type_ecp.py:183 `assert rng is not None`
+                raise DqmcError('a Hamiltonian with a non-local ECP needs `rng` (the seed of the quadrature rotation)')
+            if ecp_phi is None and not isinstance(rng, (int, np.integer)):
+                raise DqmcError('`rng` must be an integer seed')
+            self._ecp_phi = self._t(ecp_phi) if ecp_phi is not None else None      # keep alive during the call
+            if self._ecp_phi is not None and self._ecp_phi.shape[0] != B:
+                raise DqmcError('ecp_phi must have one row per walker')
+            seed = int(rng) & (2 ** 64 - 1) if isinstance(rng, (int, np.integer)) else 0
+            self._check(self.lib.dqmc_ecp_rotation(self._ctx, seed,
+                                                   self._ecp_phi.data_ptr() if self._ecp_phi is not None else None))
+
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None, static_io=False):
         """`rng` (an int seed or None) keys the random quadrature rotation of the non-local ECP term
@@ -653,17 +701,7 @@ class Engine:
         r = self._t(r)
         B = r.shape[0]
         assert r.shape[1:] == (self.N, 3)
-        if getattr(getattr(self.hamil, 'pot', None), 'nl_params', np.zeros(0)).size:
-            if rng is None and ecp_phi is None:      # gaussian_type_ecp.py:183 `assert rng is not None`
-                raise DqmcError('a Hamiltonian with a non-local ECP needs `rng` (the seed of the quadrature rotation)')
-            if ecp_phi is None and not isinstance(rng, (int, np.integer)):
-                raise DqmcError('`rng` must be an integer seed')
-            self._ecp_phi = self._t(ecp_phi) if ecp_phi is not None else None      # keep alive during the call
-            if self._ecp_phi is not None and self._ecp_phi.shape[0] != B:
-                raise DqmcError('ecp_phi must have one row per walker')
-            seed = int(rng) & (2 ** 64 - 1) if isinstance(rng, (int, np.integer)) else 0
-            self._check(self.lib.dqmc_ecp_rotation(self._ctx, seed,
-                                                   self._ecp_phi.data_ptr() if self._ecp_phi is not None else None))
+        self._set_ecp_rotation(B, rng, ecp_phi)
         static_io = static_io and not return_grad
         Rt = self._R(R)
         if static_io:

@@ -9,9 +9,10 @@ grad_R log|psi| from the coordinate reverse pass (dqmc_log_psi_grad_coords, the 
     F = f(params, phys_conf)                      # [B, n_nuc, 3]
 
 Cartesian nuclear coordinates only (no coordinate_transform).  Hamiltonians with an effective core potential or a
-pseudo-Hamiltonian are not supported by the estimators (NotImplementedError): the reference's ZVQ family rejects them, and
-the bare ECP force needs the gradient of the non-local term.  The AC-ZV and AC-ZVZB estimators (the local energy of
-d psi / d R, make_zv_term_via_jvp) are not provided.
+pseudo-Hamiltonian are not supported by the estimators of this module (NotImplementedError): the reference's ZVQ family
+rejects them, and the bare ECP force needs the gradient of the non-local term, which `deepqmc_amd.ecp_force` provides for
+Gaussian-type ECPs (evaluate_hf_force_bare, evaluate_hf_force_ac_zb; they work with `antithetic_wrapper` below).  The AC-ZV
+and AC-ZVZB estimators (the local energy of d psi / d R, make_zv_term_via_jvp) are not provided.
 """
 from __future__ import annotations
 

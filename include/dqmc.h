@@ -26,6 +26,8 @@
  *                          make_grad_nuc_log_wf), vmapped over walkers
  *   dqmc_hf_force       <- the Hellmann-Feynman force estimators of force.py (nuclear_force, evaluate_hf_force_bare,
  *                          evaluate_hf_force_ac_zvq / _zvzbq / _zb), per walker
+ *   dqmc_ecp_force      <- evaluate_hf_force_bare / _ac_zb for a Hamiltonian with a Gaussian-type ECP (force.py:286-299 with
+ *                          hamil.pot.grad_nonloc_potential, ecp/gaussian_type_ecp.py:257-330, ecp/ecp_force_utils.py)
  *
  * Conventions: plain pointers and sizes only.  Unless marked "host", every pointer is a
  * DEVICE pointer.  Walker-major contiguous layouts: r[B][N][3], R[n_nuc][3].  `real` is
@@ -400,6 +402,38 @@ enum dqmc_force_estimator {
 };
 int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, int B, const void* grad_r, const void* grad_R,
                   const void* e_loc, double energy, double* force);
+
+/* Hellmann-Feynman force of a Hamiltonian with a Gaussian-type ECP (dqmc_set_ecp), per walker b and nucleus I, Cartesian:
+ *     F_I = F_nuc,I(Z) - dV_loc/dR_I - G_I,      Z = the (valence) charges given to dqmc_create.
+ * V_loc = sum_i sum_I f_I(rho), f_I = -Z_I / rho + the local r^-1, r^0, r^1 Gaussians of nucleus I (d = r_i - R_I, rho = |d|):
+ *     dV_loc/dR_I = -sum_i f_I'(rho) d / rho.
+ * G is the gradient of the non-local term.  For a nucleus I = nl_nuc[j] with a non-local channel, electron i and quadrature
+ * vertex q (x_q = R_I + rho w_q, w_q = Rz(phi) Ry(theta) Rz(phi_rand) p_q: the vertices of dqmc_local_energy):
+ *     ratio_q       = s_q s_0 exp(log_q - log_0)
+ *     dratio_q/dR_K = ratio_q ( gR_q[K] - gR_0[K] + [K == I] J_q^T gr_q[i] )
+ *     J_q = dx_q/dR_I = 1 - [ w_q dhat^T + rho (d_theta w_q)(grad_d theta)^T + rho (d_phi w_q)(grad_d phi)^T ]
+ *     grad_d theta = (cos(theta) dhat - e_z) / (rho sin(theta)),   grad_d phi = (-d_y, d_x, 0) / (d_x^2 + d_y^2)
+ *     v_l(rho) = sum_t beta_lt e^{-alpha_lt rho^2},   dv_l/dR_I = -2 (R_I - r_i) sum_t alpha_lt beta_lt e^{-alpha_lt rho^2}
+ *     G_K += sum_i sum_l (2l+1)/12 [ [K == I] dv_l/dR_I sum_q P_l(cos theta_q) ratio_q + v_l sum_q P_l(cos theta_q) dratio_q/dR_K ]
+ * gr_q / gR_q: d log|psi| / dr, / dR at the configuration with electron i at x_q, gR_0 the same at the walker itself, all from
+ * one coordinate reverse pass (dqmc_log_psi_grad_coords) per walker chunk of "ecp_max_cfg" quadrature configurations, in the
+ * context's dtype; the assembly is double.  all_rows 0: only K == I is kept (the reference's wf_ratio_grad[:, nucleus_index]);
+ * all_rows 1: every K, the full dV_nl/dR.  The row of nucleus nl_nuc[j] is stored at row nl_nuc[j] (the reference stores it
+ * at row j, which is right only when every nucleus has a non-local channel).  On the axis d || e_z, J_q is singular, as the
+ * reference's autograd is.
+ *   estimator: DQMC_FORCE_BARE, or DQMC_FORCE_AC_ZB = BARE - 2 (e_loc[b] - energy) gR_0[b][I] (e_loc: real[B], else may be
+ *              NULL); anything else DQMC_E_ARG.
+ *   force: device double[B][n_nuc][3].  parts: NULL or device double[2][B][n_nuc][3]: parts[0] = F_nuc - dV_loc/dR,
+ *          parts[1] = -G (BARE: force = parts[0] + parts[1]).
+ *   The rotation is the one set by the preceding dqmc_ecp_rotation: the same seed or angles give the vertices of the
+ *   dqmc_local_energy call.
+ * DQMC_E_ARG when no Gaussian ECP is set or a pseudo-Hamiltonian is; DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as
+ * dqmc_log_psi_grad_coords.  An ECP with local terms only is valid: parts[1] is zero and no reverse pass runs unless AC_ZB
+ * needs gR_0.  A walker with sign 0 or a non-finite log|psi| gets NaN rows in parts[1] and force; a quadrature configuration
+ * with sign 0 or a non-finite log|psi| contributes ratio 0.  Fixed-order sums, no atomics: identical calls are bit-identical,
+ * and a chunked call equals an unchunked one bit for bit.  dqmc_last_chunks[0] afterwards: the walker chunks of the call. */
+int dqmc_ecp_force(dqmc_ctx* ctx, int estimator, int all_rows, const void* r, const void* R, int B, const void* e_loc,
+                   double energy, double* force, double* parts);
 
 /* ---- SCF-orbital pretraining (reference pretrain/pretraining.py, pretraining_target.py, gto.py) ----
  * Slater matrices are real[B][K][N][N], K = n_det: rows electrons (up first), columns orbitals.
