@@ -2,7 +2,8 @@
 
 Host glue only: compiles the layer program (program.py), hands it to the C ABI
 (include/dqmc.h) and moves raw device pointers of torch tensors across it.  torch is used
-for device memory and streams, nothing else.
+for device memory and streams, nothing else.  The library trusts those pointers: `Engine._arg` and
+`Engine._walkers` are where a wrong dtype, layout, device or shape is stopped.
 """
 from __future__ import annotations
 
@@ -40,6 +41,16 @@ def nuclear_energy(coords: np.ndarray, charges: np.ndarray) -> float:
     return e
 
 
+def _np_ptr(a: np.ndarray, ctype=ctypes.c_double, or_null=False):
+    """The data of a contiguous host array as a `ctype*`; or_null: an empty array crosses as NULL."""
+    return None if or_null and not a.size else a.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+def _ptr(t):
+    """The device pointer of an optional tensor (None -> NULL)."""
+    return t.data_ptr() if t is not None else None
+
+
 class Engine:
     def __init__(self, spec: AnsatzSpec, hamil: MolecularHamiltonian, params, *, dtype=torch.float32,
                  device='cuda', norm_eps: Optional[float] = None, lib=None, R=None, compiler=None):
@@ -63,6 +74,12 @@ class Engine:
         self.program: Program = self._compile(params)
         self._theta_ref = None         # the device vector of the last device update (params_flat)
         self.params_ahead = False      # set by a device update: the context's weights are newer than the tree it is cached under
+        self._param_map_set = self._kfac_map_set = False      # dqmc_set_param_map / dqmc_set_kfac_map done
+        self._kfac_layout = None       # the state layout of the installed KFAC tables (set_kfac_tables)
+        self._static_io = {}           # B -> the buffers of local_energy(static_io=True)
+        self._options = {}             # what set_option was given
+        self.pretrain_n_conf = None    # configurations of the uploaded pretraining target
+        self._ecp_phi = None
         self.N = hamil.n_up + hamil.n_down
         sysd = DqmcSystem(hamil.n_up, hamil.n_down, hamil.n_nuc, spec.n_determinants,
                           0 if dtype == torch.float32 else 1, 0, self.norm_eps, 0.0)
@@ -77,23 +94,19 @@ class Engine:
             dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
             stream = torch.cuda.current_stream(self.device).cuda_stream
         ctx = ctypes.c_void_p()
-        rc = self.lib.dqmc_create(ctypes.byref(ctx), dev_index, ctypes.c_void_p(stream), ctypes.byref(sysd),
-                                  ch.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), self._bufs, len(p.bufs),
-                                  self._ops, len(p.ops), w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), w.size,
-                                  it.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), p.itable.size)
+        rc = self.lib.dqmc_create(ctypes.byref(ctx), dev_index, ctypes.c_void_p(stream), ctypes.byref(sysd), _np_ptr(ch), self._bufs,
+                                  len(p.bufs), self._ops, len(p.ops), _np_ptr(w), w.size, _np_ptr(it, ctypes.c_int32), p.itable.size)
         self._ctx = ctx
         self._check(rc)
-        self._ecp_phi = None
         pot = getattr(hamil, 'pot', None)
-        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if a.size else None
         if pot is not None and hasattr(pot, 'rv_l2'):       # pseudo-Hamiltonian tables -> device
             mask = np.ascontiguousarray(pot.ecp_mask, np.int32)
-            self._check(self.lib.dqmc_set_pseudo_hamiltonian(self._ctx, pot.rv_loc.shape[1], pot.r_max, dp(pot.rv_loc), dp(pot.rv_l2),
-                                                             mask.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+            self._check(self.lib.dqmc_set_pseudo_hamiltonian(self._ctx, pot.rv_loc.shape[1], pot.r_max, _np_ptr(pot.rv_loc, or_null=True),
+                                                             _np_ptr(pot.rv_l2, or_null=True), _np_ptr(mask, ctypes.c_int32)))
         elif pot is not None:                               # Gaussian-type ECP tables -> device
-            self._check(self.lib.dqmc_set_ecp(self._ctx, pot.loc_params.shape[3], dp(pot.loc_params),
-                                              pot.nl_params.shape[1], pot.nl_params.shape[3], dp(pot.nl_params)))
-        self.R = torch.as_tensor(self.R0, dtype=dtype, device=self.device).contiguous()
+            self._check(self.lib.dqmc_set_ecp(self._ctx, pot.loc_params.shape[3], _np_ptr(pot.loc_params, or_null=True),
+                                              pot.nl_params.shape[1], pot.nl_params.shape[3], _np_ptr(pot.nl_params, or_null=True)))
+        self.R = torch.tensor(self.R0, dtype=dtype, device=self.device)      # (a copy: R0 may be the molecule's read-only array)
 
     # ------------------------------------------------------------------
     def _check(self, rc: int):
@@ -117,42 +130,80 @@ class Engine:
     def _t(self, x, dtype=None):
         return torch.as_tensor(x, dtype=dtype or self.dtype, device=self.device).contiguous()
 
+    # ---- what crosses the C ABI as a raw pointer: the layout must be exactly the documented one ----
+    def _arg(self, name, t, dtype, shape, optional=False):
+        """`t` if it is a contiguous `dtype` tensor of `shape` (None: any extent) on the engine's device type, else DqmcError.
+        A bool tensor for a uint8 slot is viewed as uint8; `optional`: None passes."""
+        if t is None and optional:
+            return None
+        if dtype == torch.uint8 and isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device.type != self.device.type \
+                or t.dim() != len(shape) or any(n is not None and n != m for n, m in zip(shape, t.shape)):
+            want = ', '.join('*' if n is None else str(n) for n in shape)
+            got = f'{t.dtype} {list(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t).__name__
+            raise DqmcError(f"'{name}' must be a contiguous {dtype} tensor of shape [{want}] on {self.device}, got {got}")
+        return t
+
+    def check_walker_vector(self, name, t, n=None):
+        """A [B] tensor about to cross the C ABI as a raw pointer: dtype, layout and device must be the context's."""
+        return self._arg(name, t, self.dtype, (n,))
+
+    def _walkers(self, r, R=None):
+        """The prologue of every entry point that takes walkers: (r [B, N, 3] as a contiguous tensor of the engine's dtype on
+        its device, the geometry tensor of the call, B)."""
+        r = self._arg('r', self._t(r), self.dtype, (None, self.N, 3))
+        return r, self._R(R), r.shape[0]
+
+    def _cot(self, cot, B):
+        return None if cot is None else self._arg('cot', self._t(cot).reshape(-1), self.dtype, (B,))
+
+    def _psi_out(self, B):
+        """New (logpsi [B], sign [B]) outputs."""
+        return torch.empty(B, dtype=self.dtype, device=self.device), torch.empty(B, dtype=torch.int32, device=self.device)
+
     def _R(self, R):
         if R is None:
             return self.R
         R = self._t(R)
         if R.dim() == 3:      # reference tiles R per walker (electron_samplers.py:165-173)
             R = R[0].contiguous()
+        self._arg('R', R, self.dtype, (self.hamil.n_nuc, 3))
         if self.spec.nuclei_tokens and not torch.equal(R, self.R):
             raise DqmcError('this ansatz folds the nuclear stream at the geometry of its Hamiltonian; '
                             'build a new engine for a different R')
         return R
 
+    def _read(self, fn, ctype, keys) -> dict:
+        """{key: value} of a getter `fn(ctx, ctype out[len(keys)])`."""
+        out = (ctype * len(keys))()
+        self._check(fn(self._ctx, out))
+        return dict(zip(keys, out))
+
     def set_params(self, params):
         """New parameter tree after an optimiser step (same structure)."""
         prog = self._compile(params)
         w = self._w_host = np.ascontiguousarray(prog.weights, np.float64)
-        self._check(self.lib.dqmc_set_weights(self._ctx, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), w.size))
+        self._check(self.lib.dqmc_set_weights(self._ctx, _np_ptr(w), w.size))
         self.params_ahead, self._theta_ref = False, None
 
     # ---- device-resident parameters and optimiser step (dqmc_set_param_map ... dqmc_apply_update) ----
     def _ensure_param_map(self):
         """Upload Program.grad_src on first use (dqmc_set_param_map)."""
-        if not self.__dict__.get('_param_map_set', False):
+        if not self._param_map_set:
             prog = self.program
             if prog.grad_unsupported:
                 raise NotImplementedError(f'device-resident parameters: unsupported for this program ({prog.grad_unsupported})')
             src = np.ascontiguousarray(prog.grad_src, np.int32)
-            self._check(self.lib.dqmc_set_param_map(self._ctx, src.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), src.size,
-                                                    prog.n_params()))
+            self._check(self.lib.dqmc_set_param_map(self._ctx, _np_ptr(src, ctypes.c_int32), src.size, prog.n_params()))
             self._param_map_set = True
 
-    def _theta_arg(self, name, t, n=None):
-        n = self.program.n_params() if n is None else n
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device.type != self.device.type \
-                or t.dim() != 1 or t.shape[0] != n:
-            raise DqmcError(f"'{name}' must be a contiguous 1-d float64 tensor of length {n} on {self.device}")
-        return t
+    def _thetas(self, norms=None, n_norms=3, **vectors):
+        """Check float64 [n_params] device vectors, given by name, and the optional `norms` [n_norms]."""
+        n = self.program.n_params()
+        for name, t in vectors.items():
+            self._arg(name, t, torch.float64, (n,))
+        self._arg('norms', norms, torch.float64, (n_norms,), optional=True)
 
     def params_flat(self, params=None):
         """The context's current parameters as a float64 device vector in Program.grad_leaves order: the theta of
@@ -174,15 +225,16 @@ class Engine:
     def set_params_flat(self, theta):
         """New parameter values from a float64 device vector (dqmc_weights_from_params): weights, twin, tape and fused planes
         are rewritten on the device, nothing goes through the host and captured graphs stay valid."""
+        self._thetas(theta=theta)
         self._ensure_param_map()
-        self._check(self.lib.dqmc_weights_from_params(self._ctx, self._theta_arg('theta', theta).data_ptr()))
+        self._check(self.lib.dqmc_weights_from_params(self._ctx, theta.data_ptr()))
         self.params_ahead, self._theta_ref = True, theta
 
     def grad_to_params(self, g):
         """Flat gradient over the weight buffer (log_psi_vjp) -> float64 [n_params] device vector: unflatten_grad flattened in
         leaf order, without leaving the device (dqmc_grad_to_params)."""
+        self._arg('g', g, torch.float64, (self.program.weights.size,))
         self._ensure_param_map()
-        g = self._theta_arg('g', g, self.program.weights.size)
         out = torch.empty(self.program.n_params(), dtype=torch.float64, device=self.device)
         self._check(self.lib.dqmc_grad_to_params(self._ctx, g.data_ptr(), out.data_ptr()))
         return out
@@ -190,26 +242,17 @@ class Engine:
     def adam_step(self, theta, mu, nu, grad_theta, *, lr, b1=0.9, b2=0.999, eps=1e-8, t=1, norms=None):
         """One optax.adam step in place on the device vectors theta, mu, nu, then the re-pack (dqmc_adam_step).  t: 1-based count.
         norms: optional float64 [3] device tensor receiving (param, grad, update) 2-norms."""
+        self._thetas(norms, theta=theta, mu=mu, nu=nu, grad_theta=grad_theta)
         self._ensure_param_map()
-        n = self.program.n_params()
-        for name, x in (('theta', theta), ('mu', mu), ('nu', nu), ('grad_theta', grad_theta)):
-            self._theta_arg(name, x)
-        if norms is not None:
-            self._theta_arg('norms', norms, 3)
-        self._check(self.lib.dqmc_adam_step(self._ctx, theta.data_ptr(), mu.data_ptr(), nu.data_ptr(), grad_theta.data_ptr(), n,
-                                            float(lr), float(b1), float(b2), float(eps), int(t),
-                                            norms.data_ptr() if norms is not None else None))
+        self._check(self.lib.dqmc_adam_step(self._ctx, theta.data_ptr(), mu.data_ptr(), nu.data_ptr(), grad_theta.data_ptr(),
+                                            self.program.n_params(), float(lr), float(b1), float(b2), float(eps), int(t), _ptr(norms)))
         self.params_ahead, self._theta_ref = True, theta
 
     def apply_update(self, theta, delta, scale=1.0, norms=None):
         """theta += scale * delta on the device, then the re-pack (dqmc_apply_update)."""
+        self._thetas(norms, theta=theta, delta=delta)
         self._ensure_param_map()
-        self._theta_arg('theta', theta)
-        self._theta_arg('delta', delta)
-        if norms is not None:
-            self._theta_arg('norms', norms, 3)
-        self._check(self.lib.dqmc_apply_update(self._ctx, theta.data_ptr(), delta.data_ptr(), float(scale),
-                                               norms.data_ptr() if norms is not None else None))
+        self._check(self.lib.dqmc_apply_update(self._ctx, theta.data_ptr(), delta.data_ptr(), float(scale), _ptr(norms)))
         self.params_ahead, self._theta_ref = True, theta
 
     # ---- KFAC preconditioner on the flat device vectors (dqmc_set_kfac_map, dqmc_kfac_direction, dqmc_kfac_apply) ----
@@ -256,7 +299,7 @@ class Engine:
     def _ensure_kfac_map(self):
         """Upload the KFAC tables on first use (dqmc_set_kfac_map), after the parameter map."""
         self._ensure_param_map()
-        if not self.__dict__.get('_kfac_map_set', False):
+        if not self._kfac_map_set:
             self.set_kfac_tables(*self._kfac_tables())
 
     def set_kfac_tables(self, tabs, layout):
@@ -264,10 +307,11 @@ class Engine:
         the program's own tables; tests use it with tables of their own."""
         self._ensure_param_map()
         m = _lib.DqmcKfacMap()
-        p64 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        m.n_modules, m.mod, m.n_ops, m.op = tabs['mod'].shape[0], p64(tabs['mod']), tabs['op'].shape[0], p64(tabs['op'])
-        m.n_maps, m.maps = tabs['maps'].size, tabs['maps'].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        m.n_diag, m.diag_pos, m.diag_row, m.diag_col = tabs['diag_pos'].size, p64(tabs['diag_pos']), p64(tabs['diag_row']), p64(tabs['diag_col'])
+        i64 = ctypes.c_int64
+        m.n_modules, m.mod, m.n_ops, m.op = tabs['mod'].shape[0], _np_ptr(tabs['mod'], i64), tabs['op'].shape[0], _np_ptr(tabs['op'], i64)
+        m.n_maps, m.maps = tabs['maps'].size, _np_ptr(tabs['maps'], ctypes.c_int32)
+        m.n_diag, m.diag_pos, m.diag_row, m.diag_col = tabs['diag_pos'].size, _np_ptr(tabs['diag_pos'], i64), \
+            _np_ptr(tabs['diag_row'], i64), _np_ptr(tabs['diag_col'], i64)
         self._check(self.lib.dqmc_set_kfac_map(self._ctx, ctypes.byref(m)))
         n = ctypes.c_size_t()
         self._check(self.lib.dqmc_kfac_state_size(self._ctx, ctypes.byref(n)))
@@ -294,36 +338,28 @@ class Engine:
         preallocated (delta, dot).  Nothing waits for the host."""
         self._ensure_kfac_map()
         lay = self.program.kfac_layout()
-        n = self.program.n_params()
-        self._theta_arg('grad_theta', grad_theta)
-        self._theta_arg('factors_buf', factors_buf, lay['n_factor_doubles'])
-        self._theta_arg('state', state, self._kfac_layout['size'])
-        B = logpsi.shape[0]
-        if logpsi.dtype != self.dtype or not logpsi.is_contiguous() or sign.dtype != torch.int32 or sign.shape[0] != B or not sign.is_contiguous():
-            raise DqmcError(f"'logpsi' must be a contiguous {self.dtype} vector and 'sign' an int32 vector of the same length")
-        if rest is not None and (rest.dtype != self.dtype or tuple(rest.shape) != (B, lay['n_rest']) or not rest.is_contiguous()):
-            raise DqmcError(f"'rest' must be a contiguous [{B}, {lay['n_rest']}] {self.dtype} tensor")
-        delta, dot = out if out is not None else (torch.empty(n, dtype=torch.float64, device=self.device),
+        B = self._arg('logpsi', logpsi, self.dtype, (None,)).shape[0]
+        self._arg('sign', sign, torch.int32, (B,))
+        self._arg('rest', rest, self.dtype, (B, lay['n_rest']), optional=True)
+        self._arg('factors_buf', factors_buf, torch.float64, (lay['n_factor_doubles'],))
+        self._arg('state', state, torch.float64, (self._kfac_layout['size'],))
+        delta, dot = out if out is not None else (torch.empty(self.program.n_params(), dtype=torch.float64, device=self.device),
                                                   torch.empty(1, dtype=torch.float64, device=self.device))
-        self._theta_arg('delta', delta)
-        self._theta_arg('dot', dot, 1)
-        self._check(self.lib.dqmc_kfac_direction(self._ctx, grad_theta.data_ptr(), factors_buf.data_ptr(),
-                                                 rest.data_ptr() if rest is not None else None, logpsi.data_ptr(), sign.data_ptr(), B,
-                                                 state.data_ptr(), int(bool(first)), float(ema), float(damping), delta.data_ptr(),
-                                                 dot.data_ptr()))
+        self._thetas(grad_theta=grad_theta, delta=delta)
+        self._arg('dot', dot, torch.float64, (1,))
+        self._check(self.lib.dqmc_kfac_direction(self._ctx, grad_theta.data_ptr(), factors_buf.data_ptr(), _ptr(rest), logpsi.data_ptr(),
+                                                 sign.data_ptr(), B, state.data_ptr(), int(bool(first)), float(ema), float(damping),
+                                                 delta.data_ptr(), dot.data_ptr()))
         return delta, dot
 
     def kfac_apply(self, theta, delta, dot, lr, norm_constraint, norms=None):
         """theta += -lr min(1, sqrt(norm_constraint / (lr^2 dot))) delta on the device, then the re-pack (dqmc_kfac_apply);
         norms: optional float64 [4] receiving (param, direction, update) 2-norms and lr^2 dot."""
+        self._thetas(norms, 4, theta=theta, delta=delta)
+        self._arg('dot', dot, torch.float64, (1,))
         self._ensure_param_map()
-        self._theta_arg('theta', theta)
-        self._theta_arg('delta', delta)
-        self._theta_arg('dot', dot, 1)
-        if norms is not None:
-            self._theta_arg('norms', norms, 4)
         self._check(self.lib.dqmc_kfac_apply(self._ctx, theta.data_ptr(), delta.data_ptr(), dot.data_ptr(), float(lr),
-                                             float(norm_constraint), norms.data_ptr() if norms is not None else None))
+                                             float(norm_constraint), _ptr(norms)))
         self.params_ahead, self._theta_ref = True, theta
 
     def debug_read_weights(self, which: int):
@@ -340,33 +376,15 @@ class Engine:
 
     def graph_counters(self) -> dict:
         """{captures, replays} of the context's forward-Laplacian graphs (dqmc_graph_counters)."""
-        out = (ctypes.c_int64 * 2)()
-        self._check(self.lib.dqmc_graph_counters(self._ctx, out))
-        return {'captures': int(out[0]), 'replays': int(out[1])}
+        return self._read(self.lib.dqmc_graph_counters, ctypes.c_int64, ('captures', 'replays'))
 
     # ---- loss assembly of multi-state training (dqmc_psi_ratio, dqmc_clip_rows, dqmc_loss_cotangents) ----
-    def _f64(self, name, t, shape):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device.type != self.device.type \
-                or tuple(t.shape) != tuple(shape):
-            raise DqmcError(f"'{name}' must be a contiguous float64 tensor of shape {tuple(shape)} on {self.device}")
-        return t
-
-    def _u8(self, name, t, shape):
-        if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
-            t = t.view(torch.uint8)
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or t.device.type != self.device.type \
-                or tuple(t.shape) != tuple(shape):
-            raise DqmcError(f"'{name}' must be a contiguous bool / uint8 tensor of shape {tuple(shape)} on {self.device}")
-        return t
-
     def psi_ratio(self, log, sign):
         """ratio[S, S, B] from log|psi| and sign [S, S, B] (float64; element [i, j] = psi_i on the samples of state j) by the
         log shift of loss.compute_psi_ratio (dqmc_psi_ratio).  Nothing waits for the host."""
-        if log.dim() != 3 or log.shape[0] != log.shape[1]:
-            raise DqmcError("'log' must have shape [S, S, B]")
-        S, _, B = log.shape
-        self._f64('log', log, (S, S, B))
-        self._f64('sign', sign, (S, S, B))
+        S, _, B = self._arg('log', log, torch.float64, (None, None, None)).shape
+        self._arg('log', log, torch.float64, (S, S, B))
+        self._arg('sign', sign, torch.float64, (S, S, B))
         out = torch.empty_like(log)
         self._check(self.lib.dqmc_psi_ratio(self._ctx, log.data_ptr(), sign.data_ptr(), S, B, out.data_ptr()))
         return out
@@ -375,18 +393,13 @@ class Engine:
         """Row-wise clip of x[n_rows, B] (float64) with each row's own centre (median or mean) and scale (mean or median absolute
         deviation) (dqmc_clip_rows).  Returns (x_clip [n_rows, B], mask bool [n_rows, B], row_stats [n_rows, 4] = centre,
         scale, mean_b(w x_clip), mask count).  A row with a non-finite element comes back non-finite."""
-        if x.dim() != 2:
-            raise DqmcError("'x' must have shape [n_rows, B]")
-        n, B = x.shape
-        self._f64('x', x, (n, B))
-        if w is not None:
-            self._f64('w', w, (n, B))
+        n, B = self._arg('x', x, torch.float64, (None, None)).shape
+        self._arg('w', w, torch.float64, (n, B), optional=True)
         out = torch.empty_like(x)
         mask = torch.empty(n, B, dtype=torch.uint8, device=self.device)
         stats = torch.empty(n, 4, dtype=torch.float64, device=self.device)
-        self._check(self.lib.dqmc_clip_rows(self._ctx, x.data_ptr(), w.data_ptr() if w is not None else None, n, B,
-                                            int(bool(median_center)), int(bool(median_scale)), float(clip_width), float(exclude_width),
-                                            out.data_ptr(), mask.data_ptr(), stats.data_ptr()))
+        self._check(self.lib.dqmc_clip_rows(self._ctx, x.data_ptr(), _ptr(w), n, B, int(bool(median_center)), int(bool(median_scale)),
+                                            float(clip_width), float(exclude_width), out.data_ptr(), mask.data_ptr(), stats.data_ptr()))
         return out, mask.view(torch.bool), stats
 
     def loss_cotangents(self, e_clip, e_mask, e_stats, w=None, *, alpha=0.0, r_clip=None, r_mask=None, r_stats=None, scale=None,
@@ -394,24 +407,20 @@ class Engine:
         """The cotangents c[S, B] of log|psi_s| on the states' own samples from the clipped energies, optionally the clipped
         ratios and the spin rows (dqmc_loss_cotangents; formulas in include/dqmc.h).  spin_kind: None, 'squared' or 'raising'.
         Returns (c, k): k [n_states, B] the direct weights of the raising kind (else None).  Everything stays on the device."""
-        S, B = e_clip.shape
+        S, B = self._arg('e_clip', e_clip, torch.float64, (None, None)).shape
         t = _lib.DqmcLossTerms()
         keep = []
 
-        def ptr(x):
-            keep.append(x)
-            return x.data_ptr()
+        def ptr(name, x, shape, dtype=torch.float64):     # (the struct holds integers: `keep` holds the uint8 views)
+            keep.append(self._arg(name, x, dtype, shape))
+            return keep[-1].data_ptr()
         t.S, t.B = S, B
-        t.w = ptr(self._f64('w', w, (S, B))) if w is not None else None
-        t.e_clip, t.e_mask, t.e_stats = ptr(self._f64('e_clip', e_clip, (S, B))), ptr(self._u8('e_mask', e_mask, (S, B))), \
-            ptr(self._f64('e_stats', e_stats, (S, 4)))
+        t.w = ptr('w', w, (S, B)) if w is not None else None
+        t.e_clip, t.e_mask, t.e_stats = e_clip.data_ptr(), ptr('e_mask', e_mask, (S, B), torch.uint8), ptr('e_stats', e_stats, (S, 4))
         t.alpha = float(alpha)
         if r_clip is not None:
-            if rank is None or rank.dtype != torch.int32 or tuple(rank.shape) != (S,) or rank.device.type != self.device.type:
-                raise DqmcError(f"'rank' must be an int32 tensor of shape ({S},) on {self.device}")
-            t.r_clip, t.r_mask = ptr(self._f64('r_clip', r_clip, (S, S, B))), ptr(self._u8('r_mask', r_mask, (S, S, B)))
-            t.r_stats, t.scale, t.rank = ptr(self._f64('r_stats', r_stats, (S * S, 4))), ptr(self._f64('scale', scale, (S, S))), \
-                ptr(rank.contiguous())
+            t.r_clip, t.r_mask = ptr('r_clip', r_clip, (S, S, B)), ptr('r_mask', r_mask, (S, S, B), torch.uint8)
+            t.r_stats, t.scale, t.rank = ptr('r_stats', r_stats, (S * S, 4)), ptr('scale', scale, (S, S)), ptr('rank', rank, (S,), torch.int32)
         kinds = {None: 0, 'squared': 1, 'raising': 2}
         if spin_kind not in kinds:
             raise ValueError("spin_kind must be None, 'squared' or 'raising'")
@@ -421,24 +430,20 @@ class Engine:
             states = list(range(S)) if states is None else [int(q) for q in states]
             n = len(states)
             arr = (ctypes.c_int32 * max(n, 1))(*states)
-            keep.append(arr)
             t.states_host, t.n_states = arr, n
-            t.spin = ptr(self._f64('spin', spin, (n, B)))
+            t.spin = ptr('spin', spin, (n, B))
             if spin_kind == 'raising':
-                t.spin_mask, t.spin_stats = ptr(self._u8('spin_mask', spin_mask, (n, B))), ptr(self._f64('spin_stats', spin_stats, (n, 4)))
+                t.spin_mask, t.spin_stats = ptr('spin_mask', spin_mask, (n, B), torch.uint8), ptr('spin_stats', spin_stats, (n, 4))
                 k = torch.empty(n, B, dtype=torch.float64, device=self.device)
         c = torch.empty(S, B, dtype=torch.float64, device=self.device)
-        self._check(self.lib.dqmc_loss_cotangents(self._ctx, ctypes.byref(t), c.data_ptr(), k.data_ptr() if k is not None else None))
+        self._check(self.lib.dqmc_loss_cotangents(self._ctx, ctypes.byref(t), c.data_ptr(), _ptr(k)))
         return c, k
 
     # ---- ansatz.apply ---------------------------------------------------
     def wf_eval(self, r, R=None):
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._check(self.lib.dqmc_wf_eval(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, logpsi.data_ptr(),
+        r, R, B = self._walkers(r, R)
+        logpsi, sign = self._psi_out(B)
+        self._check(self.lib.dqmc_wf_eval(self._ctx, r.data_ptr(), R.data_ptr(), B, logpsi.data_ptr(),
                                           sign.data_ptr()))
         return sign, logpsi
 
@@ -447,18 +452,11 @@ class Engine:
         """sum_b cot[b] d log|psi(r_b)| / d w over the flat weight buffer (loss/loss_function.py:59-75).
         Returns (sign, logpsi, grad_flat): grad_flat is float64 [n_weights] on the engine's device; map it onto the
         parameter tree with `self.program.unflatten_grad`.  cot None = all ones."""
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
-        c = None
-        if cot is not None:
-            c = self._t(cot).reshape(-1)
-            self.check_walker_vector('cot', c, B)
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+        r, R, B = self._walkers(r, R)
+        c = self._cot(cot, B)
+        logpsi, sign = self._psi_out(B)
         grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
-        self._check(self.lib.dqmc_log_psi_vjp(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B,
-                                              c.data_ptr() if c is not None else None, grad.data_ptr(),
+        self._check(self.lib.dqmc_log_psi_vjp(self._ctx, r.data_ptr(), R.data_ptr(), B, _ptr(c), grad.data_ptr(),
                                               logpsi.data_ptr(), sign.data_ptr()))
         return sign, logpsi, grad
 
@@ -467,18 +465,15 @@ class Engine:
         log_psi_vjp contracts with its cotangent.  Returns (sign, logpsi, J): J is [B, n_weights] on the engine's device, in the
         engine's dtype; map it onto the parameters with `self.program.unflatten_jacobian`.  `out`: a preallocated [B, ld]
         tensor (ld >= n_weights, unit column stride) that J is a view of; its columns >= n_weights are not touched."""
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
+        r, R, B = self._walkers(r, R)
         nw = self.program.weights.size
         if out is None:
             out = torch.empty(B, nw, dtype=self.dtype, device=self.device)
-        elif (out.dim() != 2 or out.shape[0] != B or out.shape[1] < nw or out.dtype != self.dtype or out.device.type != self.device.type
-              or out.stride(1) != 1 or out.stride(0) < nw):
-            raise DqmcError(f'out must be a [{B}, >= {nw}] {self.dtype} tensor on {self.device} with unit column stride')
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._check(self.lib.dqmc_log_psi_jacobian(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, out.data_ptr(),
+        elif (not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != B or out.shape[1] < nw or out.dtype != self.dtype
+              or out.device.type != self.device.type or out.stride(1) != 1 or out.stride(0) < nw):      # (strided rows: not _arg's case)
+            raise DqmcError(f"'out' must be a [{B}, >= {nw}] {self.dtype} tensor on {self.device} with unit column stride")
+        logpsi, sign = self._psi_out(B)
+        self._check(self.lib.dqmc_log_psi_jacobian(self._ctx, r.data_ptr(), R.data_ptr(), B, out.data_ptr(),
                                                    out.stride(0), logpsi.data_ptr(), sign.data_ptr()))
         return sign, logpsi, out[:, :nw]
 
@@ -495,26 +490,19 @@ class Engine:
         (Program.kfac_layout); rest [B, n_rest] in the engine's dtype, the per-walker partials of the weight entries no LINEAR
         op owns (columns Program.kfac_layout()['rest_index']), or None with rest=False.  `out`: optional preallocated
         (factor buffer, rest) tensors."""
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
-        c = None
-        if cot is not None:
-            c = self._t(cot).reshape(-1)
-            self.check_walker_vector('cot', c, B)
+        r, R, B = self._walkers(r, R)
+        c = self._cot(cot, B)
         lay = self.program.kfac_layout()
         fac = out[0] if out is not None else torch.empty(lay['n_factor_doubles'], dtype=torch.float64, device=self.device)
+        self._arg('out[0]', fac, torch.float64, (lay['n_factor_doubles'],))
         rst = None
         if rest:
             rst = out[1] if out is not None and out[1] is not None else torch.empty(B, lay['n_rest'], dtype=self.dtype, device=self.device)
-            assert rst.shape == (B, lay['n_rest']) and rst.dtype == self.dtype and rst.is_contiguous()
-        assert fac.numel() == lay['n_factor_doubles'] and fac.dtype == torch.float64 and fac.is_contiguous()
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+            self._arg('out[1]', rst, self.dtype, (B, lay['n_rest']))
+        logpsi, sign = self._psi_out(B)
         grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
-        self._check(self.lib.dqmc_log_psi_kfac(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, c.data_ptr() if c is not None else None,
-                                               grad.data_ptr(), fac.data_ptr(), rst.data_ptr() if rst is not None else None,
-                                               logpsi.data_ptr(), sign.data_ptr()))
+        self._check(self.lib.dqmc_log_psi_kfac(self._ctx, r.data_ptr(), R.data_ptr(), B, _ptr(c), grad.data_ptr(), fac.data_ptr(),
+                                               _ptr(rst), logpsi.data_ptr(), sign.data_ptr()))
         factors = [(fac[o['a_off']:o['a_off'] + o['d_a'] ** 2].view(o['d_a'], o['d_a']),
                     fac[o['g_off']:o['g_off'] + o['d_g'] ** 2].view(o['d_g'], o['d_g'])) for o in lay['ops']]
         return sign, logpsi, grad, factors, rst
@@ -526,16 +514,12 @@ class Engine:
         Walkers with sign 0 or a non-finite log|psi| get zero rows.  Programs with attention ops raise DqmcError (-4)."""
         if not (want_r or want_R):
             raise ValueError('log_psi_grad_coords: want_r and want_R are both False')
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
+        r, R, B = self._walkers(r, R)
         gr = torch.empty(B, self.N, 3, dtype=self.dtype, device=self.device) if want_r else None
         gR = torch.empty(B, self.hamil.n_nuc, 3, dtype=self.dtype, device=self.device) if want_R else None
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._check(self.lib.dqmc_log_psi_grad_coords(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B,
-                                                      gr.data_ptr() if gr is not None else None,
-                                                      gR.data_ptr() if gR is not None else None, logpsi.data_ptr(), sign.data_ptr()))
+        logpsi, sign = self._psi_out(B)
+        self._check(self.lib.dqmc_log_psi_grad_coords(self._ctx, r.data_ptr(), R.data_ptr(), B, _ptr(gr), _ptr(gR),
+                                                      logpsi.data_ptr(), sign.data_ptr()))
         return sign, logpsi, gr, gR
 
     def hf_force(self, estimator: str, r, R=None, grad_r=None, grad_R=None, e_loc=None, energy: float = 0.0):
@@ -544,24 +528,13 @@ class Engine:
         ('ac_zb', 'ac_zvqzb') and e_loc [B] (the estimators with a ZB term) are device tensors in the engine's dtype."""
         if estimator not in FORCE_ESTIMATORS:
             raise ValueError(f'unknown force estimator {estimator!r}; one of {FORCE_ESTIMATORS}')
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
-
-        def arg(name, t, shape):
-            if t is None:
-                return None
-            if not isinstance(t, torch.Tensor) or t.dtype != self.dtype or not t.is_contiguous() or t.device.type != self.device.type \
-                    or tuple(t.shape) != shape:
-                raise DqmcError(f"'{name}' must be a contiguous {self.dtype} tensor of shape {shape} on {self.device}")
-            return t
-        grad_r = arg('grad_r', grad_r, (B, self.N, 3))
-        grad_R = arg('grad_R', grad_R, (B, self.hamil.n_nuc, 3))
-        e_loc = arg('e_loc', e_loc, (B,))
+        r, R, B = self._walkers(r, R)
+        self._arg('grad_r', grad_r, self.dtype, (B, self.N, 3), optional=True)
+        self._arg('grad_R', grad_R, self.dtype, (B, self.hamil.n_nuc, 3), optional=True)
+        self._arg('e_loc', e_loc, self.dtype, (B,), optional=True)
         force = torch.empty(B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.dqmc_hf_force(self._ctx, FORCE_ESTIMATORS.index(estimator), r.data_ptr(), self._R(R).data_ptr(), B,
-                                           ptr(grad_r), ptr(grad_R), ptr(e_loc), float(energy), force.data_ptr()))
+        self._check(self.lib.dqmc_hf_force(self._ctx, FORCE_ESTIMATORS.index(estimator), r.data_ptr(), R.data_ptr(), B,
+                                           _ptr(grad_r), _ptr(grad_R), _ptr(e_loc), float(energy), force.data_ptr()))
         return force
 
     def ecp_force(self, estimator: str, r, R=None, rng=None, ecp_phi=None, e_loc=None, energy: float = 0.0, rows='own',
@@ -578,23 +551,15 @@ class Engine:
             raise ValueError(f"unknown ECP force estimator {estimator!r}; one of ('bare', 'ac_zb')")
         if rows not in ('own', 'all'):
             raise ValueError(f"rows must be 'own' or 'all', not {rows!r}")
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
-        if estimator == 'ac_zb':
-            if e_loc is None:
-                raise DqmcError("estimator 'ac_zb' needs e_loc")
-            if not isinstance(e_loc, torch.Tensor) or e_loc.dtype != self.dtype or not e_loc.is_contiguous() \
-                    or e_loc.device.type != self.device.type or tuple(e_loc.shape) != (B,):
-                raise DqmcError(f"'e_loc' must be a contiguous {self.dtype} tensor of shape {(B,)} on {self.device}")
-        else:
-            e_loc = None
+        r, R, B = self._walkers(r, R)
+        if estimator == 'ac_zb' and e_loc is None:
+            raise DqmcError("estimator 'ac_zb' needs e_loc")
+        e_loc = self._arg('e_loc', e_loc, self.dtype, (B,)) if estimator == 'ac_zb' else None
         self._set_ecp_rotation(B, rng, ecp_phi)
         force = torch.empty(B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device)
         parts = torch.empty(2, B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device) if return_parts else None
         self._check(self.lib.dqmc_ecp_force(self._ctx, FORCE_ESTIMATORS.index(estimator), 1 if rows == 'all' else 0, r.data_ptr(),
-                                            self._R(R).data_ptr(), B, e_loc.data_ptr() if e_loc is not None else None, float(energy),
-                                            force.data_ptr(), parts.data_ptr() if parts is not None else None))
+                                            R.data_ptr(), B, _ptr(e_loc), float(energy), force.data_ptr(), _ptr(parts)))
         return (force, parts) if return_parts else force
 
     # ---- SCF-orbital pretraining: target, Slater matrices, their VJP, the fused loss step ----
@@ -615,60 +580,54 @@ class Engine:
         cc = np.ascontiguousarray(conf_coeffs, np.float64).reshape(-1)
         if mo.ndim != 2 or confs.ndim != 2 or confs.shape[1] != self.N or cc.size != confs.shape[0]:
             raise ValueError(f'expected mo_coeffs [n_ao, n_mo], confs [n_conf, {self.N}], conf_coeffs [n_conf]')
-        pi = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        pd = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        self._check(self.lib.dqmc_set_pretrain_target(self._ctx, len(shells), pi(atom), pi(ls), pi(npr), pd(coeffs), pd(zetas),
-                                                      mo.shape[0], mo.shape[1], pd(mo), confs.shape[0], pi(confs), pd(cc)))
+        i32 = ctypes.c_int32
+        self._check(self.lib.dqmc_set_pretrain_target(self._ctx, len(shells), _np_ptr(atom, i32), _np_ptr(ls, i32), _np_ptr(npr, i32),
+                                                      _np_ptr(coeffs), _np_ptr(zetas), mo.shape[0], mo.shape[1], _np_ptr(mo),
+                                                      confs.shape[0], _np_ptr(confs, i32), _np_ptr(cc)))
         self.pretrain_n_conf = confs.shape[0]
 
-    def _orb_check(self, r):
+    def _orb_check(self, r, R):
         if not getattr(self.spec, 'full_determinant', True):
             raise DqmcError('only full-determinant programs expose their orbital matrices')
-        r = self._t(r)
-        assert r.shape[1:] == (self.N, 3)
-        return r, r.shape[0]
+        return self._walkers(r, R)
 
     def pretrain_target(self, r, R=None):
         """The target Slater matrices [B, n_conf, N, N] (rows electrons, columns orbitals) of the uploaded table
         (dqmc_pretrain_target), on the device in the engine's dtype."""
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
-        if getattr(self, 'pretrain_n_conf', None) is None:
+        r, R, B = self._walkers(r, R)
+        if self.pretrain_n_conf is None:
             raise DqmcError('pretrain_target: no target set (Engine.set_pretrain_target)')
         out = torch.empty(B, self.pretrain_n_conf, self.N, self.N, dtype=self.dtype, device=self.device)
-        self._check(self.lib.dqmc_pretrain_target(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, out.data_ptr()))
+        self._check(self.lib.dqmc_pretrain_target(self._ctx, r.data_ptr(), R.data_ptr(), B, out.data_ptr()))
         return out
 
     def orbitals(self, r, R=None):
         """The Slater matrices [B, K, N, N] of the value pass (dqmc_orbitals), on the device in the engine's dtype."""
-        r, B = self._orb_check(r)
+        r, R, B = self._orb_check(r, R)
         out = torch.empty(B, self.spec.n_determinants, self.N, self.N, dtype=self.dtype, device=self.device)
-        self._check(self.lib.dqmc_orbitals(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, out.data_ptr()))
+        self._check(self.lib.dqmc_orbitals(self._ctx, r.data_ptr(), R.data_ptr(), B, out.data_ptr()))
         return out
 
     def orbitals_vjp(self, r, cot, R=None, want_orbitals=True):
         """sum_{b,k,i,mu} cot[b,k,i,mu] d A[b,k,i,mu] / d w over the flat weight buffer (dqmc_orbitals_vjp).  cot: [B, K, N, N].
         Returns (orbitals [B, K, N, N] or None, grad_flat float64 [n_weights]); map grad_flat onto the parameter tree with
         `self.program.unflatten_grad`.  Programs with attention ops raise DqmcError (-4)."""
-        r, B = self._orb_check(r)
+        r, R, B = self._orb_check(r, R)
         shape = (B, self.spec.n_determinants, self.N, self.N)
-        c = self._t(cot)
-        if tuple(c.shape) != shape:
-            raise DqmcError(f"'cot' must have shape {shape}, got {tuple(c.shape)}")
+        c = self._arg('cot', self._t(cot), self.dtype, shape)
         orb = torch.empty(shape, dtype=self.dtype, device=self.device) if want_orbitals else None
         grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
-        self._check(self.lib.dqmc_orbitals_vjp(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, c.data_ptr(), grad.data_ptr(),
-                                               orb.data_ptr() if orb is not None else None))
+        self._check(self.lib.dqmc_orbitals_vjp(self._ctx, r.data_ptr(), R.data_ptr(), B, c.data_ptr(), grad.data_ptr(),
+                                               _ptr(orb)))
         return orb, grad
 
     def pretrain_loss_grad(self, r, R=None, n_total=None):
         """The fused pretraining step (dqmc_pretrain_loss_grad): returns (per_sample_loss float64 [B], grad_flat float64
         [n_weights]) with grad_flat = d (sum_b per_sample_loss[b] / n_total) / d w; n_total defaults to B."""
-        r, B = self._orb_check(r)
+        r, R, B = self._orb_check(r, R)
         ps = torch.empty(B, dtype=torch.float64, device=self.device)
         grad = torch.empty(self.program.weights.size, dtype=torch.float64, device=self.device)
-        self._check(self.lib.dqmc_pretrain_loss_grad(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B,
+        self._check(self.lib.dqmc_pretrain_loss_grad(self._ctx, r.data_ptr(), R.data_ptr(), B,
                                                      float(B if n_total is None else n_total), grad.data_ptr(), ps.data_ptr()))
         return ps, grad
 
@@ -684,8 +643,7 @@ class Engine:
             if self._ecp_phi is not None and self._ecp_phi.shape[0] != B:
                 raise DqmcError('ecp_phi must have one row per walker')
             seed = int(rng) & (2 ** 64 - 1) if isinstance(rng, (int, np.integer)) else 0
-            self._check(self.lib.dqmc_ecp_rotation(self._ctx, seed,
-                                                   self._ecp_phi.data_ptr() if self._ecp_phi is not None else None))
+            self._check(self.lib.dqmc_ecp_rotation(self._ctx, seed, _ptr(self._ecp_phi)))
 
     # ---- hamil.local_energy ---------------------------------------------
     def local_energy(self, phys_conf, rng=None, return_grad=False, ecp_phi=None, static_io=False):
@@ -698,29 +656,26 @@ class Engine:
             r, R = phys_conf.r, phys_conf.R
         else:
             r, R = phys_conf, None
-        r = self._t(r)
-        B = r.shape[0]
-        assert r.shape[1:] == (self.N, 3)
+        r, R, B = self._walkers(r, R)
         self._set_ecp_rotation(B, rng, ecp_phi)
         static_io = static_io and not return_grad
-        Rt = self._R(R)
         if static_io:
-            bufs = self.__dict__.setdefault('_static_io', {})
-            if B not in bufs:
-                bufs[B] = (torch.empty(B, self.N, 3, dtype=self.dtype, device=self.device), torch.empty_like(Rt),
-                           torch.empty(B, dtype=self.dtype, device=self.device), torch.empty(6, B, dtype=self.dtype, device=self.device))
-            r_in, R_in, e, st = bufs[B]
+            if B not in self._static_io:
+                self._static_io[B] = (torch.empty(B, self.N, 3, dtype=self.dtype, device=self.device), torch.empty_like(R),
+                                      torch.empty(B, dtype=self.dtype, device=self.device),
+                                      torch.empty(6, B, dtype=self.dtype, device=self.device))
+            r_in, R_in, e, st = self._static_io[B]
             r_in.copy_(r)
-            if Rt is not self.R:          # (a sampler stacks a new R tensor per step: same values, another pointer)
-                R_in.copy_(Rt)
-                Rt = R_in
+            if R is not self.R:          # (a sampler stacks a new R tensor per step: same values, another pointer)
+                R_in.copy_(R)
+                R = R_in
             r = r_in
         else:
             e = torch.empty(B, dtype=self.dtype, device=self.device)
             st = torch.empty(6, B, dtype=self.dtype, device=self.device)
         grad = torch.empty(B, 3 * self.N, dtype=self.dtype, device=self.device) if return_grad else None
-        self._check(self.lib.dqmc_local_energy(self._ctx, r.data_ptr(), Rt.data_ptr(), B, e.data_ptr(),
-                                               st.data_ptr(), grad.data_ptr() if return_grad else None, None, None))
+        self._check(self.lib.dqmc_local_energy(self._ctx, r.data_ptr(), R.data_ptr(), B, e.data_ptr(),
+                                               st.data_ptr(), _ptr(grad), None, None))
         if static_io:
             e, st = e.clone(), st.clone()
         stats = {k: st[i] for i, k in enumerate(STAT_KEYS)}
@@ -730,132 +685,100 @@ class Engine:
         """(sign, log|psi|, grad log|psi| [B,N,3]) in one forward-Laplacian pass -- what the reference's
         LangevinSampler obtains with value_and_grad (electron_samplers.py:193-201).  No potential terms and
         no ECP quadrature run (dqmc_psi_grad)."""
-        r = self._t(r)
-        B = r.shape[0]
+        r, R, B = self._walkers(r, R)
         grad = torch.empty(B, 3 * self.N, dtype=self.dtype, device=self.device)
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
-        self._check(self.lib.dqmc_psi_grad(self._ctx, r.data_ptr(), self._R(R).data_ptr(), B, logpsi.data_ptr(),
+        logpsi, sign = self._psi_out(B)
+        self._check(self.lib.dqmc_psi_grad(self._ctx, r.data_ptr(), R.data_ptr(), B, logpsi.data_ptr(),
                                            sign.data_ptr(), grad.data_ptr()))
         return sign, logpsi, grad.reshape(B, self.N, 3)
 
     # ---- sampler ----------------------------------------------------------
-    def mcmc_steps(self, state: Dict[str, torch.Tensor], n_sub: int, *, max_age=None, target_acceptance=0.57,
-                   seed: int = 0, noise=None, unif=None, R=None, want_stats=True, return_accept=False):
-        """In-place Metropolis sub-steps on state {'r','log','sign','age','tau'} (device tensors)."""
-        r, B = state['r'], state['r'].shape[0]
-        want = {'r': self.dtype, 'log': self.dtype, 'tau': self.dtype, 'sign': torch.int32, 'age': torch.int32}
-        for k, dt in want.items():     # raw device pointers cross the C ABI: the layout must be exactly the documented one
-            t = state[k]
-            if t.dtype != dt or not t.is_contiguous() or t.device.type != self.device.type:
-                raise DqmcError(f"sampler state '{k}' must be a contiguous {dt} tensor on {self.device}")
-        if r.shape != (B, self.N, 3) or any(state[k].shape[0] != B for k in ('log', 'sign', 'age')):
-            raise DqmcError('sampler state shapes do not match [B, N, 3] / [B]')
-        acc = torch.empty(n_sub, B, dtype=torch.uint8, device=self.device) if return_accept else None
-        stats = (ctypes.c_double * 7)()
-        if noise is not None:
-            noise, unif = self._t(noise), self._t(unif)
-            assert noise.shape == (n_sub, B, self.N, 3) and unif.shape == (n_sub, B)
-        rc = self.lib.dqmc_mcmc_steps(
-            self._ctx, r.data_ptr(), state['log'].data_ptr(), state['sign'].data_ptr(), state['age'].data_ptr(),
-            state['tau'].data_ptr(), self._R(R).data_ptr(), B, n_sub, -1 if max_age is None else int(max_age),
-            -1.0 if target_acceptance is None else float(target_acceptance), int(seed),
-            noise.data_ptr() if noise is not None else None, unif.data_ptr() if unif is not None else None,
-            acc.data_ptr() if return_accept else None, stats if want_stats else None)
-        self._check(rc)
-        out = dict(zip(SAMPLER_STAT_KEYS, list(stats))) if want_stats else {}
-        return (out, acc) if return_accept else out
+    def _check_state(self, state, keys, R):
+        """The prologue of the sampler entry points: (B, the geometry tensor of the call, the device pointers of the tensors `keys`
+        of the state, which the library updates in place)."""
+        B = self._arg("state['r']", state['r'], self.dtype, (None, self.N, 3)).shape[0]
+        want = {'r': (self.dtype, (B, self.N, 3)), 'force': (self.dtype, (B, self.N, 3)), 'log': (self.dtype, (B,)),
+                'tau': (self.dtype, (1,)), 'sign': (torch.int32, (B,)), 'age': (torch.int32, (B,))}
+        return B, self._R(R), [self._arg(f"state['{k}']", state[k], *want[k]).data_ptr() for k in keys]
 
-    def _check_state(self, state, keys):
-        B = state['r'].shape[0]
-        want = {'r': self.dtype, 'log': self.dtype, 'tau': self.dtype, 'force': self.dtype, 'sign': torch.int32, 'age': torch.int32}
-        for k in keys:     # raw device pointers cross the C ABI: the layout must be exactly the documented one
-            t = state[k]
-            if t.dtype != want[k] or not t.is_contiguous() or t.device.type != self.device.type:
-                raise DqmcError(f"sampler state '{k}' must be a contiguous {want[k]} tensor on {self.device}")
-        if state['r'].shape != (B, self.N, 3) or any(state[k].shape[0] != B for k in keys if k not in ('r', 'tau')):
-            raise DqmcError('sampler state shapes do not match [B, N, 3] / [B]')
-        return B
+    def _sampler_io(self, lead, noise, unif, return_accept):
+        """What the sampler entry points share: (acc uint8 [*lead] or None, the host stats array, noise [*lead, N, 3] or None,
+        unif [*lead] or None)."""
+        acc = torch.empty(*lead, dtype=torch.uint8, device=self.device) if return_accept else None
+        noise = self._arg('noise', self._t(noise), self.dtype, (*lead, self.N, 3)) if noise is not None else None
+        unif = self._arg('unif', self._t(unif), self.dtype, lead) if unif is not None else None
+        return acc, (ctypes.c_double * len(SAMPLER_STAT_KEYS))(), noise, unif
+
+    @staticmethod
+    def _sampler_result(stats, acc, want_stats=True):
+        out = dict(zip(SAMPLER_STAT_KEYS, stats)) if want_stats else {}
+        return out if acc is None else (out, acc)
 
     def _molz(self, charges):
         z = np.ascontiguousarray(charges, np.float64)
-        assert z.shape == (self.hamil.n_nuc,)
-        return z, z.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        if z.shape != (self.hamil.n_nuc,):
+            raise DqmcError(f"'mol_charges' must have shape ({self.hamil.n_nuc},), got {z.shape}")
+        return z, _np_ptr(z)
+
+    def mcmc_steps(self, state: Dict[str, torch.Tensor], n_sub: int, *, max_age=None, target_acceptance=0.57,
+                   seed: int = 0, noise=None, unif=None, R=None, want_stats=True, return_accept=False):
+        """In-place Metropolis sub-steps on state {'r','log','sign','age','tau'} (device tensors)."""
+        B, R, (r, log, sign, age, tau) = self._check_state(state, ('r', 'log', 'sign', 'age', 'tau'), R)
+        acc, stats, noise, unif = self._sampler_io((n_sub, B), noise, unif, return_accept)
+        self._check(self.lib.dqmc_mcmc_steps(
+            self._ctx, r, log, sign, age, tau, R.data_ptr(), B, n_sub, -1 if max_age is None else int(max_age),
+            -1.0 if target_acceptance is None else float(target_acceptance), int(seed), _ptr(noise), _ptr(unif), _ptr(acc),
+            stats if want_stats else None))
+        return self._sampler_result(stats, acc, want_stats)
 
     def langevin_update(self, r, tau, mol_charges, R=None):
         """LangevinSampler._update (electron_samplers.py:193-208): (sign, log|psi|, cleaned drift [B,N,3])."""
-        r = self._t(r)
-        B = r.shape[0]
-        tau = self._t(tau).reshape(1)
+        r, R, B = self._walkers(r, R)
+        tau = self._arg('tau', self._t(tau).reshape(-1), self.dtype, (1,))
         z, zp = self._molz(mol_charges)
-        logpsi = torch.empty(B, dtype=self.dtype, device=self.device)
-        sign = torch.empty(B, dtype=torch.int32, device=self.device)
+        logpsi, sign = self._psi_out(B)
         force = torch.empty(B, self.N, 3, dtype=self.dtype, device=self.device)
-        self._check(self.lib.dqmc_langevin_update(self._ctx, r.data_ptr(), self._R(R).data_ptr(), zp, B, tau.data_ptr(),
+        self._check(self.lib.dqmc_langevin_update(self._ctx, r.data_ptr(), R.data_ptr(), zp, B, tau.data_ptr(),
                                                   logpsi.data_ptr(), sign.data_ptr(), force.data_ptr()))
         return sign, logpsi, force
 
     def langevin_steps(self, state, n_sub, mol_charges, *, max_age=None, target_acceptance=0.57, seed=0, noise=None, unif=None,
                        R=None, want_stats=True, return_accept=False):
         """In-place Langevin sub-steps on state {'r','log','sign','age','tau','force'} (dqmc_langevin_steps)."""
-        B = self._check_state(state, ('r', 'log', 'sign', 'age', 'tau', 'force'))
-        acc = torch.empty(n_sub, B, dtype=torch.uint8, device=self.device) if return_accept else None
-        stats = (ctypes.c_double * 7)()
-        if noise is not None:
-            noise, unif = self._t(noise), self._t(unif)
-            assert noise.shape == (n_sub, B, self.N, 3) and unif.shape == (n_sub, B)
+        B, R, (r, log, sign, age, force, tau) = self._check_state(state, ('r', 'log', 'sign', 'age', 'force', 'tau'), R)
+        acc, stats, noise, unif = self._sampler_io((n_sub, B), noise, unif, return_accept)
         z, zp = self._molz(mol_charges)
         self._check(self.lib.dqmc_langevin_steps(
-            self._ctx, state['r'].data_ptr(), state['log'].data_ptr(), state['sign'].data_ptr(), state['age'].data_ptr(),
-            state['force'].data_ptr(), state['tau'].data_ptr(), self._R(R).data_ptr(), zp, B, n_sub,
+            self._ctx, r, log, sign, age, force, tau, R.data_ptr(), zp, B, n_sub,
             -1 if max_age is None else int(max_age), -1.0 if target_acceptance is None else float(target_acceptance), int(seed),
-            noise.data_ptr() if noise is not None else None, unif.data_ptr() if unif is not None else None,
-            acc.data_ptr() if return_accept else None, stats if want_stats else None))
-        out = dict(zip(SAMPLER_STAT_KEYS, list(stats))) if want_stats else {}
-        return (out, acc) if return_accept else out
+            _ptr(noise), _ptr(unif), _ptr(acc), stats if want_stats else None))
+        return self._sampler_result(stats, acc, want_stats)
 
     def exchange_step(self, state, up_idx, down_idx, unif, R=None, return_accept=False):
         """One opposite-spin exchange step, in place on state {'r','log','sign','age','tau'} (dqmc_exchange_step)."""
-        B = self._check_state(state, ('r', 'log', 'sign', 'age', 'tau'))
+        B, R, (r, log, sign, age, tau) = self._check_state(state, ('r', 'log', 'sign', 'age', 'tau'), R)
         for name, idx, n in (('up_idx', up_idx, self.hamil.n_up), ('down_idx', down_idx, self.hamil.n_down)):
             host = idx if isinstance(idx, np.ndarray) else (idx if isinstance(idx, torch.Tensor) and idx.device.type == 'cpu' else None)
             if host is not None and len(host) and (int(host.min()) < 0 or int(host.max()) >= n):     # device tensors: clamped in the kernel
                 raise DqmcError(f'{name} must lie in [0, {n})')
-        up = torch.as_tensor(up_idx, device=self.device).to(torch.int32).contiguous()
-        dn = torch.as_tensor(down_idx, device=self.device).to(torch.int32).contiguous()
-        u = self._t(unif)
-        assert up.shape == dn.shape == u.shape == (B,)
-        acc = torch.empty(B, dtype=torch.uint8, device=self.device) if return_accept else None
-        stats = (ctypes.c_double * 7)()
-        self._check(self.lib.dqmc_exchange_step(self._ctx, state['r'].data_ptr(), state['log'].data_ptr(), state['sign'].data_ptr(),
-                                                state['age'].data_ptr(), state['tau'].data_ptr(), self._R(R).data_ptr(), B,
-                                                up.data_ptr(), dn.data_ptr(), u.data_ptr(), acc.data_ptr() if return_accept else None,
-                                                stats))
-        out = dict(zip(SAMPLER_STAT_KEYS, list(stats)))
-        return (out, acc) if return_accept else out
-
-    def check_walker_vector(self, name, t, n=None):
-        """A [B] tensor about to cross the C ABI as a raw pointer: dtype, layout and device must be the context's."""
-        if not isinstance(t, torch.Tensor) or t.dtype != self.dtype or not t.is_contiguous() or t.device.type != self.device.type \
-                or t.dim() != 1 or (n is not None and t.shape[0] != n):
-            raise DqmcError(f"'{name}' must be a contiguous 1-d {self.dtype} tensor on {self.device}"
-                            + (f' of length {n}' if n is not None else ''))
-        return t
+        up, dn = (self._arg(name, torch.as_tensor(idx, device=self.device).to(torch.int32).contiguous(), torch.int32, (B,))
+                  for name, idx in (('up_idx', up_idx), ('down_idx', down_idx)))
+        acc, stats, _, u = self._sampler_io((B,), None, unif, return_accept)
+        self._check(self.lib.dqmc_exchange_step(self._ctx, r, log, sign, age, tau, R.data_ptr(), B,
+                                                up.data_ptr(), dn.data_ptr(), u.data_ptr(), _ptr(acc), stats))
+        return self._sampler_result(stats, acc)
 
     def energy_record(self, e_loc, w=None):
-        self.check_walker_vector('e_loc', e_loc)
-        if w is not None:
-            self.check_walker_vector('w', w, e_loc.shape[0])
+        B = self.check_walker_vector('e_loc', e_loc).shape[0]
+        self._arg('w', w, self.dtype, (B,), optional=True)
         rec = (ctypes.c_double * 7)()
-        self._check(self.lib.dqmc_energy_stats(self._ctx, e_loc.data_ptr(), w.data_ptr() if w is not None else None,
-                                               e_loc.shape[0], rec))
+        self._check(self.lib.dqmc_energy_stats(self._ctx, e_loc.data_ptr(), _ptr(w), B, rec))
         return np.array(list(rec))
 
     def merge_energy_records(self, records: np.ndarray):
         records = np.ascontiguousarray(records, np.float64).reshape(-1, 7)
         out = (ctypes.c_double * 5)()
-        self._check(self.lib.dqmc_merge_energy_stats(records.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                     records.shape[0], out))
+        self._check(self.lib.dqmc_merge_energy_stats(_np_ptr(records), records.shape[0], out))
         return dict(zip(('local_energy/mean', 'local_energy/std', 'local_energy/min', 'local_energy/max',
                          'local_energy/weighted_mean'), list(out)))
 
@@ -873,7 +796,7 @@ class Engine:
             rows, width = self.program.bufs[idx]
             shape = (B, rows, TP, width)
         out = np.empty(shape, np.float64)
-        self._check(self.lib.dqmc_debug_read(self._ctx, idx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size))
+        self._check(self.lib.dqmc_debug_read(self._ctx, idx, _np_ptr(out), out.size))
         return out
 
     def last_refined(self) -> int:
@@ -882,17 +805,15 @@ class Engine:
 
     def refine_info(self) -> dict:
         """State of the float64 refinement after the last local-energy call (dqmc_refine_info)."""
-        out = (ctypes.c_double * 4)()
-        self._check(self.lib.dqmc_refine_info(self._ctx, out))
         # ('error_per_score': the scale m of the exponential error model, float32 error = m x score x xi)
-        return {'mode': int(out[0]), 'score_threshold': out[1], 'error_per_score': out[2], 'direct_f64_calls_left': int(out[3])}
+        out = self._read(self.lib.dqmc_refine_info, ctypes.c_double, ('mode', 'score_threshold', 'error_per_score', 'direct_f64_calls_left'))
+        out['mode'], out['direct_f64_calls_left'] = int(out['mode']), int(out['direct_f64_calls_left'])
+        return out
 
     def refine_counters(self) -> dict:
         """Running counts of the context (dqmc_refine_counters): local-energy calls, calls evaluated in float64 whole,
         calibration probes, walkers re-evaluated in float64."""
-        out = (ctypes.c_int64 * 4)()
-        self._check(self.lib.dqmc_refine_counters(self._ctx, out))
-        return {'calls': int(out[0]), 'direct_f64_calls': int(out[1]), 'probe_calls': int(out[2]), 'walkers_refined': int(out[3])}
+        return self._read(self.lib.dqmc_refine_counters, ctypes.c_int64, ('calls', 'direct_f64_calls', 'probe_calls', 'walkers_refined'))
 
     def substep_kernel(self) -> str:
         """Name of the plan-specialised sub-step kernel bound to this context's program (dqmc_substep_kernel), '' if none."""
@@ -905,29 +826,25 @@ class Engine:
     def refine_scores(self, n: int) -> np.ndarray:
         """Error-predictor scores of the first n walkers of the last float32 forward-Laplacian pass (dqmc_refine_scores)."""
         out = np.empty(int(n), np.float64)
-        self._check(self.lib.dqmc_refine_scores(self._ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(n)))
+        self._check(self.lib.dqmc_refine_scores(self._ctx, _np_ptr(out), int(n)))
         return out
 
     def last_chunks(self) -> dict:
         """Walker chunks the last local-energy call was split into (dqmc_last_chunks): the context's own pass and its
         float64 twin's."""
-        out = (ctypes.c_int * 2)()
-        self._check(self.lib.dqmc_last_chunks(self._ctx, out))
-        return {'own': int(out[0]), 'twin': int(out[1])}
+        return self._read(self.lib.dqmc_last_chunks, ctypes.c_int, ('own', 'twin'))
 
     def ecp_counts(self) -> dict:
         """(nucleus, electron) pairs of the last mixed-precision ECP quadrature by class (dqmc_ecp_counts)."""
-        out = (ctypes.c_int64 * 3)()
-        self._check(self.lib.dqmc_ecp_counts(self._ctx, out))
-        return {'f32': int(out[0]), 'f64': int(out[1]), 'dropped': int(out[2])}
+        return self._read(self.lib.dqmc_ecp_counts, ctypes.c_int64, ('f32', 'f64', 'dropped'))
 
     def set_option(self, name: str, value: int):
         self._check(self.lib.dqmc_set_option(self._ctx, name.encode(), int(value)))
-        self.__dict__.setdefault('_options', {})[name] = int(value)      # (what the caller chose: apply(return_mos=True) restores it)
+        self._options[name] = int(value)      # (what the caller chose: apply(return_mos=True) restores it)
 
     def get_option(self, name: str, default: int) -> int:
         """The value last set through set_option (the library has no getter), else `default`."""
-        return self.__dict__.get('_options', {}).get(name, default)
+        return self._options.get(name, default)
 
     def timing(self, enable=True):
         self._check(self.lib.dqmc_timing_enable(self._ctx, int(enable)))
