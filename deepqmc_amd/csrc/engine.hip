@@ -2,10 +2,12 @@
 // per-kernel timing.  Host code only; every arithmetic step is one of the kernels in
 // kernel_linear.hip / kernels_graph.hip / kernels_head.hip / kernels_mcmc.hip.
 // This file: DevBuf, the one type that owns device memory here (every allocation of a context is a DevBuf member and is
-// released by it), the context base, the state of Engine<real> (members, options' storage, captured-graph bookkeeping),
+// released by it), Slab, the one way a scratch DevBuf<char> is carved into aligned typed slices, PassOpts, what a pass is asked
+// to do beyond its outputs, the context base, the state of Engine<real> (members, options' storage, captured-graph bookkeeping),
 // and the extern "C" entry points.  The member functions live in engine_*.inl by concern -- program analyses
 // (engine_program.inl), planner of the LDS-resident kernel (engine_fused_plan.inl), pass runner (engine_pass.inl),
-// float64 refinement (engine_refine.inl), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
+// float64 refinement (engine_refine.inl; its host-only policy -- threshold calibration, direct-mode hysteresis -- in
+// refine_policy.h), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
 // engine_coords.inl, with the force estimators; engine_ecp_force.inl, the ECP force), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
 // step (engine_optim.inl), the KFAC preconditioner on its vectors (engine_kfacopt.inl) -- and
@@ -18,7 +20,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <string>
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include "../../include/dqmc.h"
 #include "kernels.h"
 #include "op_view.h"
+#include "refine_policy.h"
 #include "spec_device.h"
 
 namespace {
@@ -102,6 +104,28 @@ struct DevBuf {
   }
 };
 
+// The layout of one scratch slab (a DevBuf<char>): take<T>(n) the slices in order -- each starts 256-byte aligned --, reserve
+// `bytes` once, then slice.in(slab) is the slice's typed pointer.
+struct Slab {
+  template <typename T> struct Slice {
+    size_t off;
+    T* in(char* slab) const { return reinterpret_cast<T*>(slab + off); }
+  };
+  size_t bytes = 0;
+  size_t take_bytes(size_t n) { const size_t o = bytes; bytes += (n + 255) / 256 * 256; return o; }
+  template <typename T> Slice<T> take(size_t n) { return {take_bytes(sizeof(T) * n)}; }
+};
+
+// What a forward-Laplacian pass is asked to do beyond its outputs (lap_refined -> pass_own -> run -> run_graphed / run_chunk,
+// local_energy_ecp).  The default is the plain pass of a caller that knows nothing of the refinement.
+struct PassOpts {
+  bool flag = false;         // k_final scores every walker and lists those above refine_thresh in d_flag (part of a captured graph's key)
+  bool skip_ph = false;      // a float64 twin serving a plain-gradient call (psi_grad / Langevin): no pseudo-Hamiltonian seeding
+  bool skip_nl = false;      // ... and no non-local ECP quadrature; also a call whose quadrature follows in ecp_mixed
+  const int32_t* walker_idx = nullptr;   // twin serving a float32 context: global walker index per walker (EcpArgs::walker_idx)
+  bool phi_f32 = false;      // ... whose rotation angles (ecp_phi) are float32
+};
+
 }  // namespace
 
 struct dqmc_ctx {
@@ -169,8 +193,6 @@ struct dqmc_ctx {
   virtual dqmc_ctx* twin_ctx() { return nullptr; }
                                                          // (the float64 refinement twin of a float32 context, once it exists)
   int last_TP = 0;
-  bool ph_skip = false;     // set on a float64 twin while it serves a plain-gradient call (no pseudo-Hamiltonian seeding)
-  bool ecp_skip_nl = false; // ... and no non-local ECP quadrature
   int last_refined = 0;     // walkers re-evaluated in float64 by the last local-energy / psi_grad call
   double refine_info[4] = {0, 0, 0, 0};   // {mode, score threshold, measured error per unit of score, direct float64 calls left}
   int64_t ecp_last_counts[3] = {0, 0, 0};   // (nucleus, electron) pairs of the last mixed-precision quadrature: float32, float64, dropped
@@ -311,8 +333,6 @@ struct Engine : dqmc_ctx {
   int ecp_nt_loc = 0, ecp_n_nl = 0, ecp_L = 0, ecp_nt_nl = 0;
   uint64_t ecp_seed = 0;
   const void* ecp_phi = nullptr;
-  const int32_t* ecp_idx = nullptr;   // twin serving a float32 context: global walker index per walker (EcpArgs::walker_idx)
-  bool ecp_phi_f32 = false;
   std::vector<double> ecp_nl_h;       // host copy of the non-local tables for the float64 twin
   int ecp_nl_L_h = 0, ecp_nl_nt_h = 0;
   DevBuf<char> d_ecp;           // quadrature walkers + their psi + psi of the walkers themselves
@@ -320,7 +340,6 @@ struct Engine : dqmc_ctx {
   // weight w = max_l (2l+1)|V_l| exceeds ecp_w_heavy ("ecp_heavy_e6", in 1e-6 Ha) gets float64 psi ratios, one below
   // ecp_w_skip ("ecp_skip_e12", in 1e-12 Ha) is dropped
   int ecp_mixed_on = 1;
-  bool ecp_defer = false;       // set while lap_refined_core runs for a call whose quadrature follows in ecp_mixed
   double ecp_w_heavy = 1e-2, ecp_w_skip = 1e-10;
   // float32 error of log|psi(r)| up to which a walker counts as ordinary ("ecp_dlog_floor_e6", in 1e-6; 0: weights alone
   // decide, the round-4 rule): beyond it the walker's float64 bound tightens in proportion (kernels.h: EcpMixArgs::l32).
@@ -359,18 +378,7 @@ struct Engine : dqmc_ctx {
   int refine_probe = 32;
   int refine_sample = 256;       // walkers of the calibration sample (option "refine_sample"; 64 until round 4 -- six seeds on benzene
                                  // then drew thresholds that flagged 36-50 % of the batch)
-  // Whole-batch float64 ("direct") mode, with hysteresis: a context ENTERS it when more than refine_direct_enter of a batch
-  // lies above the threshold (the float32 pass would mostly be wasted: f32(B) + f64(p B) costs more than f64(B) from
-  // p ~ 0.6 on, the float64 pass being ~2.5-3 x the float32 one per walker), runs 15 calls there, then looks again with a
-  // float32 pass and LEAVES only if the flagged fraction has fallen below refine_direct_exit.  One draw near a single
-  // 50 % line used to flip the mode -- and the cost of a benzene step between 166 and 207 ms -- from run to run.
-  double refine_direct_enter = 0.60, refine_direct_exit = 0.45;
-  int refine_direct_calls = 15;  // calls a context stays in the direct mode before it looks again (option "refine_direct_calls")
-  int refine_direct_backoff = 4; // every look that CONFIRMS the direct mode doubles the stay, at most this many times (15, 30, ... 240 calls:
-                                 // the float32 pass of such a look is thrown away -- 1/16 of ~0.4 of a benzene / C4H4 E_loc call at a fixed stay);
-                                 // option "refine_direct_backoff"
-  int direct_streak = 0;         // consecutive confirmations
-  bool was_direct = false;       // the last mode decision was "direct"
+  dqmc::DirectMode direct;       // whole-batch float64 ("direct") mode: lines, stay, back-off and their state (refine_policy.h)
 
   int twin_full_budget = 1;      // the twin's activation workspace may be as large as this context's (option "twin_full_budget")
   // option "pass_graph" (1): a forward-Laplacian pass that fits one workspace chunk is captured ONCE per (buffers, batch
@@ -411,8 +419,6 @@ struct Engine : dqmc_ctx {
   }
   int calls_since_probe = -1;    // -1: never probed
   double probe_c = 0.0;          // last measured scale m of the float32 error per unit of score (0: none yet)
-  bool flag_on = false;
-  int refine_all_calls = 0;      // > 0: most walkers were flagged last time -> the next calls go to float64 directly
   std::vector<std::pair<std::string, int>> twin_opts;
   std::vector<double> w64_h, ecp_loc_h;
   int ecp_loc_nt_h = 0;
@@ -424,7 +430,7 @@ struct Engine : dqmc_ctx {
   size_t off_phq = 0;
   std::vector<double> ph_loc_h, ph_l2_h;      // host copies for the float64 twin
   std::vector<int32_t> ph_mask_h;
-  dqmc_ctx* twin = nullptr;
+  Engine<double>* twin = nullptr;
   dqmc_ctx* twin_ctx() override { return twin; }
   int no_twin = 0;        // option "no_twin" 1: this float32 context never creates its float64 twin -- ensure_twin answers like a program
                           // without a float64 kernel set (DQMC_E_UNSUPPORTED): plain float32 everywhere (refinement off by itself,
@@ -432,9 +438,6 @@ struct Engine : dqmc_ctx {
   DevBuf<int32_t> d_flag;        // [0] = count, [1..] = walker indices
   DevBuf<double> d_score;        // [B] error predictor of the last flagged pass
   DevBuf<char> d_ref;
-  const double* ref_e64 = nullptr;   // float64 local energies of the last refine_listed pass (device)
-  std::vector<double> probe_sample_e;          // ... of the calibration sample of a probe call (host)
-  std::function<void()> probe_rethreshold;     // set by the probe call: derives refine_thresh from probe_sample_e
 
   ~Engine() override {      // what is not memory, before the members release theirs
     delete twin;

@@ -2,8 +2,10 @@
 // effective core potentials and pseudo-Hamiltonian: tables -> device, the 12-point quadrature through the value path,
 // the mixed-precision quadrature of float32 contexts.
 
+  // Non-local ECP term of a float32 context with per-pair precision (kernels_ecp.hip: "mixed-precision quadrature"):
+  // added to e_loc, stored in stats[3].
   int ecp_mixed(const float* r, const float* R, int B, float* e_loc, float* stats) {
-    // No float64 twin for this program (its float64 kernel set does not exist: DQMC_E_UNSUPPORTED -- lap_refined_core has
+    // No float64 twin for this program (its float64 kernel set does not exist: DQMC_E_UNSUPPORTED -- lap_f32 has
     // switched the refinement off for the same reason): the quadrature runs entirely in float32, as local_energy_ecp would
     // (every kept pair in the float32 class; the pair cut-off stays).  Any other failure is an error of the call.
     int rc = ensure_twin();
@@ -13,18 +15,20 @@
     int nbw = (int)(ecp_max_cfg / per_walker);
     nbw = nbw < 1 ? 1 : (nbw > B ? B : nbw);
     const size_t n_cfg = (size_t)nbw * (per_walker + 1), n_tr = (size_t)nbw * triples_pw;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_cls = 0, o_ll = o_cls + al(4 * n_tr), o_lh = o_ll + al(4 * n_tr), o_cnt = o_lh + al(4 * n_tr),
-                 o_r32 = o_cnt + 256, o_l32 = o_r32 + al(4 * n_cfg * N * 3), o_s32 = o_l32 + al(4 * n_cfg),
-                 o_r64 = o_s32 + al(4 * n_cfg), o_l64 = o_r64 + al(8 * n_cfg * N * 3), o_s64 = o_l64 + al(8 * n_cfg),
-                 o_R64 = o_s64 + al(4 * n_cfg), tot = o_R64 + al(8 * 3 * (size_t)sys.n_nuc);
-    rc = d_ecpm.reserve(tot, st, "ECP scratch");
+    Slab slab;
+    const auto o_cls = slab.take<int32_t>(n_tr), o_ll = slab.take<int32_t>(n_tr), o_lh = slab.take<int32_t>(n_tr), o_cnt = slab.take<int32_t>(64);
+    const auto o_r32 = slab.take<float>(n_cfg * N * 3), o_l32 = slab.take<float>(n_cfg);
+    const auto o_s32 = slab.take<int32_t>(n_cfg);
+    const auto o_r64 = slab.take<double>(n_cfg * N * 3), o_l64 = slab.take<double>(n_cfg);
+    const auto o_s64 = slab.take<int32_t>(n_cfg);
+    const auto o_R64 = slab.take<double>(3 * (size_t)sys.n_nuc);
+    rc = d_ecpm.reserve(slab.bytes, st, "ECP scratch");
     if (rc) return rc;
-    int32_t* cls = (int32_t*)(d_ecpm + o_cls); int32_t* list_l = (int32_t*)(d_ecpm + o_ll); int32_t* list_h = (int32_t*)(d_ecpm + o_lh);
-    int32_t* cnt = (int32_t*)(d_ecpm + o_cnt);
-    float* rq32 = (float*)(d_ecpm + o_r32); float* lq32 = (float*)(d_ecpm + o_l32); int32_t* sq32 = (int32_t*)(d_ecpm + o_s32);
-    double* rq64 = (double*)(d_ecpm + o_r64); double* lq64 = (double*)(d_ecpm + o_l64); int32_t* sq64 = (int32_t*)(d_ecpm + o_s64);
-    double* R64 = (double*)(d_ecpm + o_R64);
+    int32_t *cls = o_cls.in(d_ecpm), *list_l = o_ll.in(d_ecpm), *list_h = o_lh.in(d_ecpm), *cnt = o_cnt.in(d_ecpm);
+    float *rq32 = o_r32.in(d_ecpm), *lq32 = o_l32.in(d_ecpm);
+    int32_t* sq32 = o_s32.in(d_ecpm);
+    double *rq64 = o_r64.in(d_ecpm), *lq64 = o_l64.in(d_ecpm), *R64 = o_R64.in(d_ecpm);
+    int32_t* sq64 = o_s64.in(d_ecpm);
     if (have_twin) dqmc::launch_refine_gather(st, r, R, nullptr, nullptr, 0, 3 * N, 3 * sys.n_nuc, nullptr, R64);      // (widens R only)
     dqmc::EcpMixArgs a{};
     a.r = r; a.R = R; a.nl_nuc = d_ecp_nuc; a.nl = d_ecp_nl; a.phi = (const float*)ecp_phi; a.seed = ecp_seed;
@@ -116,7 +120,10 @@
     ecp_is_set = true;
     return DQMC_OK;
   }
-  int ecp_rotation(uint64_t seed, const void* phi) override { ecp_seed = seed; ecp_phi = phi; return DQMC_OK; }
+  int ecp_rotation(uint64_t seed, const void* phi) override {      // (the twin rotates as the walkers it stands for: PassOpts::phi_f32)
+    ecp_seed = seed; ecp_phi = phi;
+    return twin ? twin->ecp_rotation(seed, phi) : DQMC_OK;
+  }
 
   // Pseudo-Hamiltonian tables (ecp/pseudo_hamiltonian.py:73-112): rV_loc and rV_L2 on the regular grid
   // linspace(0, r_max, n_grid), one row per nucleus; rows of nuclei with mask 0 are ignored.  An all-zero mask
@@ -154,25 +161,27 @@
   // E_loc with the non-local ECP term: the Laplacian pass, then 12 N n_nl value-only psi evaluations per
   // walker in batches of <= ecp_max_cfg quadrature walkers (gaussian_type_ecp.py:161-255).
   int local_energy_ecp(const real* r, const real* R, int B, real* e_loc, real* stats, real* grad, real* logpsi,
-                       int32_t* sign) {
+                       int32_t* sign, const PassOpts& opts) {
     const size_t per_walker = (size_t)ecp_n_nl * N * 12;
     int nbw = (int)(ecp_max_cfg / per_walker);
     nbw = nbw < 1 ? 1 : (nbw > B ? B : nbw);
     const size_t n_cfg = (size_t)nbw * per_walker;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_rq = 0, o_lq = o_rq + al(sizeof(real) * n_cfg * N * 3), o_sq = o_lq + al(sizeof(real) * n_cfg),
-                 o_l0 = o_sq + al(sizeof(int32_t) * n_cfg), o_s0 = o_l0 + al(sizeof(real) * B),
-                 tot = o_s0 + al(sizeof(int32_t) * B);
-    int rc = d_ecp.reserve(tot, st, "ECP scratch");
+    Slab slab;
+    const auto o_rq = slab.take<real>(n_cfg * N * 3), o_lq = slab.take<real>(n_cfg);
+    const auto o_sq = slab.take<int32_t>(n_cfg);
+    const auto o_l0 = slab.take<real>(B);
+    const auto o_s0 = slab.take<int32_t>(B);
+    int rc = d_ecp.reserve(slab.bytes, st, "ECP scratch");
     if (rc) return rc;
-    real* rq = (real*)(d_ecp + o_rq); real* lq = (real*)(d_ecp + o_lq); int32_t* sq = (int32_t*)(d_ecp + o_sq);
-    real* l0 = logpsi ? logpsi : (real*)(d_ecp + o_l0);
-    int32_t* s0 = sign ? sign : (int32_t*)(d_ecp + o_s0);
-    rc = run(r, R, B, true, l0, s0, e_loc, stats, grad);
+    real *rq = o_rq.in(d_ecp), *lq = o_lq.in(d_ecp);
+    int32_t* sq = o_sq.in(d_ecp);
+    real* l0 = logpsi ? logpsi : o_l0.in(d_ecp);
+    int32_t* s0 = sign ? sign : o_s0.in(d_ecp);
+    rc = run(r, R, B, true, l0, s0, e_loc, stats, grad, opts);
     if (rc) return rc;
     dqmc::EcpArgs a{};
     a.r = r; a.R = R; a.nl_nuc = d_ecp_nuc; a.nl = d_ecp_nl; a.phi = ecp_phi; a.seed = ecp_seed;
-    a.walker_idx = ecp_idx; a.phi_f32 = ecp_phi_f32 ? 1 : 0;
+    a.walker_idx = opts.walker_idx; a.phi_f32 = opts.phi_f32 ? 1 : 0;
     a.B = B; a.N = N; a.n_nl = ecp_n_nl; a.L = ecp_L; a.n_t = ecp_nt_nl;
     for (int b0 = 0; b0 < B; b0 += nbw) {
       a.b0 = b0; a.nb = (B - b0) < nbw ? (B - b0) : nbw;

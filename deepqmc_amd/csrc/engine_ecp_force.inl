@@ -47,15 +47,16 @@
     int nbw = per_walker ? (int)(ecp_max_cfg / per_walker) : (int)std::min<size_t>(ecp_max_cfg, (size_t)B);
     nbw = nbw < 1 ? 1 : (nbw > B ? B : nbw);
     const size_t cfg_pw = 1 + (size_t)n_nl * N * dqmc::ECPF_NQ, n_cfg = (size_t)nbw * cfg_pw;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_rq = 0, o_lq = o_rq + al(sizeof(real) * n_cfg * N * 3), o_sq = o_lq + al(sizeof(real) * n_cfg),
-                 o_gr = o_sq + al(sizeof(int32_t) * n_cfg), o_gR = o_gr + al(n_nl ? sizeof(real) * n_cfg * N * 3 : 0),
-                 o_gj = o_gR + al(sizeof(real) * n_cfg * n_nuc * 3), tot = o_gj + al(sizeof(double) * (size_t)nbw * n_nl * n_nuc * 3);
-    int rc = d_ecpf.reserve(tot, st, "ECP force scratch");
+    Slab slab;
+    const auto o_rq = slab.take<real>(n_cfg * N * 3), o_lq = slab.take<real>(n_cfg);
+    const auto o_sq = slab.take<int32_t>(n_cfg);
+    const auto o_gr = slab.take<real>(n_nl ? n_cfg * N * 3 : 0), o_gR = slab.take<real>(n_cfg * n_nuc * 3);
+    const auto o_gj = slab.take<double>((size_t)nbw * n_nl * n_nuc * 3);
+    int rc = d_ecpf.reserve(slab.bytes, st, "ECP force scratch");
     if (rc) return rc;
-    real* rq = (real*)(d_ecpf + o_rq); real* lq = (real*)(d_ecpf + o_lq); int32_t* sq = (int32_t*)(d_ecpf + o_sq);
-    real* gr = n_nl ? (real*)(d_ecpf + o_gr) : nullptr; real* gR = (real*)(d_ecpf + o_gR);
-    double* gj = n_nl ? (double*)(d_ecpf + o_gj) : nullptr;
+    real *rq = o_rq.in(d_ecpf), *lq = o_lq.in(d_ecpf), *gr = n_nl ? o_gr.in(d_ecpf) : nullptr, *gR = o_gR.in(d_ecpf);
+    int32_t* sq = o_sq.in(d_ecpf);
+    double* gj = n_nl ? o_gj.in(d_ecpf) : nullptr;
     int n_chunks = 0;
     for (int b0 = 0; b0 < B; b0 += nbw, ++n_chunks) {
       a.b0 = b0; a.nb = (B - b0) < nbw ? (B - b0) : nbw;

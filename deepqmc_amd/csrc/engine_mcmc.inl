@@ -21,16 +21,15 @@
     if ((noise_ == nullptr) != (unif_ == nullptr)) return fail(DQMC_E_ARG, "noise and unif must both be given or both NULL");
     real* r = (real*)r_; real* logpsi = (real*)logpsi_; real* tau = (real*)tau_;
     const real* R = (const real*)R_;
-    const size_t n_r = (size_t)B * N * 3;
+    const size_t n_r = (size_t)B * N * 3, ns = (size_t)(n_sub > 0 ? n_sub : 1);
     // scratch: r_prop, logpsi_prop, sign_prop, noise, unif
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_rp = 0, o_lp = o_rp + al(sizeof(real) * n_r), o_sp = o_lp + al(sizeof(real) * B),
-                 o_nz = o_sp + al(sizeof(int32_t) * B), o_un = o_nz + al(sizeof(real) * n_r * (size_t)(n_sub > 0 ? n_sub : 1)),
-                 tot = o_un + al(sizeof(real) * B * (size_t)(n_sub > 0 ? n_sub : 1));
-    { const int rc = d_mc.reserve(tot, st); if (rc) return rc; }
-    real* r_prop = (real*)(d_mc + o_rp); real* lp_prop = (real*)(d_mc + o_lp);
-    int32_t* s_prop = (int32_t*)(d_mc + o_sp);
-    real* nz = (real*)(d_mc + o_nz); real* un = (real*)(d_mc + o_un);
+    Slab slab;
+    const auto o_rp = slab.take<real>(n_r), o_lp = slab.take<real>(B);
+    const auto o_sp = slab.take<int32_t>(B);
+    const auto o_nz = slab.take<real>(n_r * ns), o_un = slab.take<real>(B * ns);
+    { const int rc = d_mc.reserve(slab.bytes, st); if (rc) return rc; }
+    real *r_prop = o_rp.in(d_mc), *lp_prop = o_lp.in(d_mc), *nz = o_nz.in(d_mc), *un = o_un.in(d_mc);
+    int32_t* s_prop = o_sp.in(d_mc);
     if (!noise_ && n_sub > 0) {      // all sub-steps' normals and uniforms in ONE launch (Philox is counter based)
       t_begin("mcmc", 0);
       dqmc::launch_rng<real>(st, nz, (long)(n_r * n_sub), un, (long)B * n_sub, seed, (uint64_t)0);
@@ -149,15 +148,15 @@
     real* r = (real*)r_; real* logpsi = (real*)logpsi_; real* tau = (real*)tau_; real* force = (real*)force_;
     const real* R = (const real*)R_;
     const size_t n_r = (size_t)B * N * 3, ns = (size_t)(n_sub > 0 ? n_sub : 1);
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_rp = 0, o_g = o_rp + al(sizeof(real) * n_r), o_fp = o_g + al(sizeof(real) * n_r), o_lp = o_fp + al(sizeof(real) * n_r),
-                 o_sp = o_lp + al(sizeof(real) * B), o_nz = o_sp + al(sizeof(int32_t) * B), o_un = o_nz + al(sizeof(real) * n_r * ns),
-                 tot = o_un + al(sizeof(real) * B * ns);
-    rc = d_mc.reserve(tot, st);
+    Slab slab;
+    const auto o_rp = slab.take<real>(n_r), o_g = slab.take<real>(n_r), o_fp = slab.take<real>(n_r), o_lp = slab.take<real>(B);
+    const auto o_sp = slab.take<int32_t>(B);
+    const auto o_nz = slab.take<real>(n_r * ns), o_un = slab.take<real>(B * ns);
+    rc = d_mc.reserve(slab.bytes, st);
     if (rc) return rc;
-    real* r_prop = (real*)(d_mc + o_rp); real* g_prop = (real*)(d_mc + o_g); real* f_prop = (real*)(d_mc + o_fp);
-    real* lp_prop = (real*)(d_mc + o_lp); int32_t* s_prop = (int32_t*)(d_mc + o_sp);
-    real* nz = (real*)(d_mc + o_nz); real* un = (real*)(d_mc + o_un);
+    real *r_prop = o_rp.in(d_mc), *g_prop = o_g.in(d_mc), *f_prop = o_fp.in(d_mc), *lp_prop = o_lp.in(d_mc);
+    int32_t* s_prop = o_sp.in(d_mc);
+    real *nz = o_nz.in(d_mc), *un = o_un.in(d_mc);
     if (!noise_ && n_sub > 0) {
       t_begin("mcmc", 0);
       dqmc::launch_rng<real>(st, nz, (long)(n_r * n_sub), un, (long)B * n_sub, seed, (uint64_t)1);
@@ -192,11 +191,13 @@
     if (sys.n_up < 1 || sys.n_down < 1) return fail(DQMC_E_ARG, "an exchange step needs electrons of both spins");
     real* r = (real*)r_; real* logpsi = (real*)logpsi_;
     const size_t n_r = (size_t)B * N * 3;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_rp = 0, o_lp = o_rp + al(sizeof(real) * n_r), o_sp = o_lp + al(sizeof(real) * B), tot = o_sp + al(sizeof(int32_t) * B);
-    int rc = d_mc.reserve(tot, st);
+    Slab slab;
+    const auto o_rp = slab.take<real>(n_r), o_lp = slab.take<real>(B);
+    const auto o_sp = slab.take<int32_t>(B);
+    int rc = d_mc.reserve(slab.bytes, st);
     if (rc) return rc;
-    real* r_prop = (real*)(d_mc + o_rp); real* lp_prop = (real*)(d_mc + o_lp); int32_t* s_prop = (int32_t*)(d_mc + o_sp);
+    real *r_prop = o_rp.in(d_mc), *lp_prop = o_lp.in(d_mc);
+    int32_t* s_prop = o_sp.in(d_mc);
     t_begin("mcmc", 0);
     dqmc::launch_exchange_propose<real>(st, r, up_idx, down_idx, sys.n_up, B, N, r_prop);
     t_end();

@@ -8,17 +8,16 @@
 
   int plan(int B, int TP) {
     buf_off.resize(bufs.size());
-    size_t off = 0;
-    auto bump = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    Slab slab;
     for (size_t k = 0; k < bufs.size(); ++k)
-      buf_off[k] = bump(sizeof(real) * (size_t)B * bufs[k].rows * lanes_of((int)k, TP) * bufs[k].width);
-    off_z = bump(sizeof(real) * (size_t)B * TP * max_ldw());       // per-walker pre-activation rows of the split linear layers
-    off_logdet = bump(sizeof(double) * (size_t)B * sys.n_det * TP);
-    off_signk = bump(sizeof(int32_t) * (size_t)B * sys.n_det);
-    off_cond = bump(sizeof(double) * (size_t)B * sys.n_det);      // conditioning record per determinant (Laplacian mode)
-    off_kappa = bump(sizeof(double) * (size_t)B);                 // ... and its psi-weighted sum per walker
-    if (ph_n && TP > 1) off_phq = bump(sizeof(double) * (size_t)B * N * dqmc::PH_STRIDE);
-    { const int rc = d_ws.reserve(off, st, "workspace"); if (rc) return rc; }
+      buf_off[k] = slab.take<real>((size_t)B * bufs[k].rows * lanes_of((int)k, TP) * bufs[k].width).off;
+    off_z = slab.take<real>((size_t)B * TP * max_ldw()).off;         // per-walker pre-activation rows of the split linear layers
+    off_logdet = slab.take<double>((size_t)B * sys.n_det * TP).off;
+    off_signk = slab.take<int32_t>((size_t)B * sys.n_det).off;
+    off_cond = slab.take<double>((size_t)B * sys.n_det).off;         // conditioning record per determinant (Laplacian mode)
+    off_kappa = slab.take<double>((size_t)B).off;                    // ... and its psi-weighted sum per walker
+    if (ph_n && TP > 1) off_phq = slab.take<double>((size_t)B * N * dqmc::PH_STRIDE).off;
+    { const int rc = d_ws.reserve(slab.bytes, st, "workspace"); if (rc) return rc; }
     last_B = B; last_TP = TP;
     return DQMC_OK;
   }
@@ -43,7 +42,7 @@
   // ws_budget (benzene/Psiformer in Laplacian mode needs ~0.2 GB per walker: 2048 walkers per GPU do not fit 288 GB
   // at once).  Chunks are still thousands of MFMA row blocks each.
   int run(const real* r, const real* R, int B, bool laplacian, real* logpsi, int32_t* sign, real* e_loc, real* stats,
-          real* grad) {
+          real* grad, const PassOpts& opts = {}) {
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
     const int T = laplacian ? 3 * N + 2 : 1, TP = laplacian ? (T + 15) / 16 * 16 : 1;
     const size_t per = ws_bytes_per_walker(TP);
@@ -51,35 +50,36 @@
     if (chunk < 1) chunk = 1;
     if (laplacian) last_chunks[0] = chunk >= B ? 1 : (int)((B + chunk - 1) / chunk);
     if (chunk >= B) {
-      if (laplacian && graph_fits(B)) return run_graphed(r, R, B, logpsi, sign, e_loc, stats, grad);
-      return run_chunk(r, R, B, laplacian, logpsi, sign, e_loc, stats, B, grad, 0);
+      if (laplacian && graph_fits(B)) return run_graphed(r, R, B, logpsi, sign, e_loc, stats, grad, opts);
+      return run_chunk(r, R, B, laplacian, logpsi, sign, e_loc, stats, B, grad, 0, opts);
     }
     for (int b0 = 0; b0 < B; b0 += (int)chunk) {
       const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
       const int rc = run_chunk(r + (size_t)b0 * N * 3, R, nb, laplacian, logpsi ? logpsi + b0 : nullptr, sign ? sign + b0 : nullptr,
-                               e_loc ? e_loc + b0 : nullptr, stats ? stats + b0 : nullptr, B, grad ? grad + (size_t)b0 * 3 * N : nullptr, b0);
+                               e_loc ? e_loc + b0 : nullptr, stats ? stats + b0 : nullptr, B, grad ? grad + (size_t)b0 * 3 * N : nullptr, b0, opts);
       if (rc) return rc;
     }
     return DQMC_OK;
   }
 
   // one forward-Laplacian pass through its captured graph (see pass_graph above)
-  int run_graphed(const real* r, const real* R, int B, real* logpsi, int32_t* sign, real* e_loc, real* stats, real* grad) {
+  int run_graphed(const real* r, const real* R, int B, real* logpsi, int32_t* sign, real* e_loc, real* stats, real* grad,
+                  const PassOpts& opts) {
     if (std::find(graph_warm.begin(), graph_warm.end(), B) == graph_warm.end()) {
       graph_warm.push_back(B);
-      return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0);
+      return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0, opts);
     }
     const void* key[7] = {r, R, logpsi, sign, e_loc, stats, grad};
     PassGraph* hit = nullptr;
     for (auto& g : pgraphs)
-      if (g.B == B && g.flag == flag_on && g.ws == d_ws && g.flagp == d_flag && g.epoch == graph_epoch && !memcmp(g.p, key, sizeof(key))) hit = &g;
+      if (g.B == B && g.flag == opts.flag && g.ws == d_ws && g.flagp == d_flag && g.epoch == graph_epoch && !memcmp(g.p, key, sizeof(key))) hit = &g;
     if (!hit) {
       // a caller that hands over different buffers on every call would pay a capture (milliseconds) per pass: once captures
       // clearly outnumber replays, the context goes back to eager launches for good
       if (graph_captures >= 8 && graph_hits < graph_captures) {
         graph_broken = true;
         drop_graphs();
-        return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0);
+        return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0, opts);
       }
       ++graph_captures;
       if (!st_g) {
@@ -92,10 +92,10 @@
       if (hipStreamBeginCapture(st_g, hipStreamCaptureModeRelaxed) != hipSuccess) {
         (void)hipGetLastError();
         graph_broken = true;
-        return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0);
+        return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0, opts);
       }
       st = st_g;                                   // (run_chunk launches on `st` and forks its side streams from it)
-      const int rc = run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0);
+      const int rc = run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0, opts);
       st = caller;
       const hipError_t ee = hipStreamEndCapture(st_g, &graph);
       hipGraphExec_t exec = nullptr;
@@ -104,7 +104,7 @@
         if (graph) (void)hipGraphDestroy(graph);
         graph_broken = true;                       // this program / runtime does not capture: eager from now on
         if (rc) return rc;
-        return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0);
+        return run_chunk(r, R, B, true, logpsi, sign, e_loc, stats, B, grad, 0, opts);
       }
       (void)hipGraphDestroy(graph);
       if (pgraphs.size() >= 12) {                  // (a handful of batch sizes x output buffers; evict the least recently used)
@@ -115,7 +115,7 @@
       }
       PassGraph g{};
       memcpy(g.p, key, sizeof(key));
-      g.B = B; g.flag = flag_on; g.ws = d_ws; g.flagp = d_flag; g.epoch = graph_epoch; g.exec = exec;
+      g.B = B; g.flag = opts.flag; g.ws = d_ws; g.flagp = d_flag; g.epoch = graph_epoch; g.exec = exec;
       pgraphs.push_back(g);
       hit = &pgraphs.back();
     }
@@ -154,7 +154,7 @@
   }
 
   int run_chunk(const real* r, const real* R, int B, bool laplacian, real* logpsi, int32_t* sign, real* e_loc, real* stats,
-                long stats_ld, real* grad, int b_offset) {
+                long stats_ld, real* grad, int b_offset, const PassOpts& opts = {}) {
     dqmc::LaneInfo li;
     li.N = N;
     li.T = laplacian ? 3 * N + 2 : 1;
@@ -165,7 +165,7 @@
     // pseudo-Hamiltonian: the local-energy pass (not the plain gradient of psi_grad / the Langevin sampler) seeds its
     // derivative lanes with the per-electron Cholesky factors of A(r_i) (ecp/pseudo_hamiltonian.py:115-146)
     const double* phq = nullptr;
-    if (laplacian && ph_n && e_loc && !ph_skip) {
+    if (laplacian && ph_n && e_loc && !opts.skip_ph) {
       double* q = reinterpret_cast<double*>(d_ws + off_phq);
       dqmc::launch_ph_coeffs<real>(st, r, R, d_ph_nuc, ph_n, d_ph_loc, d_ph_l2, ph_grid, ph_rmax, B, N, q);
       phq = q;
@@ -173,7 +173,7 @@
     // edge-stream ops (destination carries pair-compact lanes) go to the companion stream in Laplacian mode, independent
     // node branches to two more (analyse_streams); every op records an event, readers on other streams wait for the
     // events of the buffers they read
-    const bool dual = laplacian && dual_stream && !timing_serial() && std::any_of(compact.begin(), compact.end(), [](char c) { return c != 0; });
+    const bool dual = laplacian && dual_stream && std::any_of(compact.begin(), compact.end(), [](char c) { return c != 0; });
     const bool multi = dual && multi_stream && (long)B * N * li.TP <= (1L << 20);      // (large batches fill the GPU kernel by kernel)
     struct BufEv { hipEvent_t ev; int sid; };
     std::vector<std::vector<BufEv>> buf_w(dual ? bufs.size() : 0);
@@ -429,7 +429,7 @@
           a.logpsi = logpsi; a.sign = sign; a.e_loc = e_loc; a.stats = stats; a.stats_ld = stats_ld; a.grad = grad;
           a.phq = phq;
           if (laplacian) { a.cond = reinterpret_cast<double*>(d_ws + off_cond); a.kappa_out = reinterpret_cast<double*>(d_ws + off_kappa); }
-          if (flag_on && laplacian) {
+          if (opts.flag && laplacian) {
             a.flag_count = d_flag; a.flag_idx = d_flag + 1; a.refine_thresh = refine_thresh; a.thresh_dev = d_thresh; a.b_offset = b_offset;
             a.score_out = d_score;
           }
@@ -448,7 +448,6 @@
     HIP_TRY(hipGetLastError());
     return DQMC_OK;
   }
-  bool timing_serial() const { return false; }
   // The LDS-resident kernel is the faster VALUE path for the small systems it was built for (N <= 4: one launch per
   // Metropolis sub-step) and for small batches of any system (one launch against ~50); for larger systems at large
   // batch the layered MFMA kernels win (N2 / FermiNet, 4096 walkers: 1.38 ms against 1.61 ms per value pass).
@@ -464,9 +463,9 @@
   }
   // the pass in this context's own precision: forward-Laplacian evaluation, plus the non-local ECP quadrature when the
   // Hamiltonian has one and a local energy is asked for
-  int pass_own(const real* r, const real* R, int B, real* logpsi, int32_t* sign, real* e_loc, real* stats, real* grad) {
-    if (ecp_n_nl == 0 || !e_loc || ecp_skip_nl || ecp_defer) return run(r, R, B, true, logpsi, sign, e_loc, stats, grad);
-    return local_energy_ecp(r, R, B, e_loc, stats, grad, logpsi, sign);
+  int pass_own(const real* r, const real* R, int B, real* logpsi, int32_t* sign, real* e_loc, real* stats, real* grad, const PassOpts& opts) {
+    if (ecp_n_nl == 0 || !e_loc || opts.skip_nl) return run(r, R, B, true, logpsi, sign, e_loc, stats, grad, opts);
+    return local_energy_ecp(r, R, B, e_loc, stats, grad, logpsi, sign, opts);
   }
 
   // log|psi|, sign and grad log|psi| from the forward-Laplacian pass alone: no potentials beyond k_final's, no

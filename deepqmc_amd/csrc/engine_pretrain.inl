@@ -110,14 +110,15 @@
     if (chunk < 1) chunk = 1;
     if (chunk > B) chunk = B;
     last_chunks[0] = (int)((B + chunk - 1) / chunk);
-    const size_t o_sg = (sizeof(real) * (size_t)chunk + 255) / 256 * 256;
-    { const int rc = grad_ws_reserve(o_sg + sizeof(int32_t) * (size_t)chunk); if (rc) return rc; }
+    Slab slab;                                   // log|psi| of a chunk, then (unpadded) its signs
+    const auto o_lp = slab.take<real>((size_t)chunk);
+    const Slab::Slice<int32_t> o_sg{slab.bytes};
+    { const int rc = grad_ws_reserve(slab.bytes + sizeof(int32_t) * (size_t)chunk); if (rc) return rc; }
     const UnfusedForward unfused(*this);
     const int ob = dqmc::OrbitalsOp(ops[orb_op]).dst(), NN = N * N;
     for (int b0 = 0; b0 < B; b0 += (int)chunk) {
       const int nb = (B - b0) < chunk ? (B - b0) : (int)chunk;
-      const int rc = run_chunk(r + (size_t)b0 * N * 3, (const real*)R, nb, false, reinterpret_cast<real*>(g_ws.p),
-                               reinterpret_cast<int32_t*>(g_ws + o_sg), nullptr, nullptr, nb, nullptr, 0);
+      const int rc = run_chunk(r + (size_t)b0 * N * 3, (const real*)R, nb, false, o_lp.in(g_ws), o_sg.in(g_ws), nullptr, nullptr, nb, nullptr, 0);
       if (rc) return rc;
       dqmc::launch_orbitals_copy<real>(st, bptr(ob), bufs[ob].width, orb + (size_t)b0 * sys.n_det * NN, NN, NN, (long)nb * sys.n_det);
     }

@@ -115,20 +115,19 @@
     const bool jac = q.mode == Rev::Jac, kfac = q.mode == Rev::Kfac, coords = q.mode == Rev::Coords, orbs = q.mode == Rev::Orbs;
     // adjoint workspace of this chunk
     std::vector<size_t> adj(bufs.size());
-    size_t off = 0;
-    auto bump = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    for (size_t k = 0; k < bufs.size(); ++k) adj[k] = bump(sizeof(real) * (size_t)B * bufs[k].rows * bufs[k].width);
-    const size_t adj_end = off;
-    const size_t o_z = bump(sizeof(real) * (size_t)B * grad_zrow()), o_dz = bump(sizeof(real) * (size_t)B * grad_zrow());
-    const size_t o_dzs = bump(sizeof(real) * (size_t)B * max_ldw());
-    const size_t o_orb = bump(sizeof(double) * (size_t)B * (!coords && grad_orb_partials() ? grad_orb_partials() : 1));
-    const size_t o_dl = bump(sizeof(double) * (size_t)B * sys.n_det), o_pw = bump(sizeof(double) * (size_t)B * (sys.n_det + 2));
-    const size_t o_lp = bump(sizeof(real) * (size_t)B), o_sg = bump(sizeof(int32_t) * (size_t)B);
-    const size_t o_part = bump(coords ? 0 : grad_part_bytes());
-    const size_t o_kw = bump(kfac ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = bump(kfac ? kfac_part_bytes() : 0);
-    const size_t o_slot = bump(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
-    const size_t o_tgt = bump(orbs && !q.cot_orb ? (size_t)B * pt_target_bytes_per_walker() : 0);
-    { const int rc = grad_ws_reserve(off); if (rc) return rc; }
+    Slab slab;
+    for (size_t k = 0; k < bufs.size(); ++k) adj[k] = slab.take_bytes(sizeof(real) * (size_t)B * bufs[k].rows * bufs[k].width);
+    const size_t adj_end = slab.bytes;
+    const size_t o_z = slab.take_bytes(sizeof(real) * (size_t)B * grad_zrow()), o_dz = slab.take_bytes(sizeof(real) * (size_t)B * grad_zrow());
+    const size_t o_dzs = slab.take_bytes(sizeof(real) * (size_t)B * max_ldw());
+    const size_t o_orb = slab.take_bytes(sizeof(double) * (size_t)B * (!coords && grad_orb_partials() ? grad_orb_partials() : 1));
+    const size_t o_dl = slab.take_bytes(sizeof(double) * (size_t)B * sys.n_det), o_pw = slab.take_bytes(sizeof(double) * (size_t)B * (sys.n_det + 2));
+    const size_t o_lp = slab.take_bytes(sizeof(real) * (size_t)B), o_sg = slab.take_bytes(sizeof(int32_t) * (size_t)B);
+    const size_t o_part = slab.take_bytes(coords ? 0 : grad_part_bytes());
+    const size_t o_kw = slab.take_bytes(kfac ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = slab.take_bytes(kfac ? kfac_part_bytes() : 0);
+    const size_t o_slot = slab.take_bytes(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
+    const size_t o_tgt = slab.take_bytes(orbs && !q.cot_orb ? (size_t)B * pt_target_bytes_per_walker() : 0);
+    { const int rc = grad_ws_reserve(slab.bytes); if (rc) return rc; }
     char* gw = g_ws;
     auto A = [&](int b) { return reinterpret_cast<real*>(gw + adj[b]); };
     real* lp = q.logpsi ? q.logpsi : reinterpret_cast<real*>(gw + o_lp);

@@ -17,7 +17,7 @@ for f in engine kernel_linear kernel_fused2 kernel_attention kernel_attention_mf
   stale_inl=0
   if [ "$f" = engine ]; then for i in "$SRC"/engine_*.inl; do [ "$i" -nt "$OUT/$f.o" ] && stale_inl=1; done; fi
   if [ ! -f "$OUT/$f.o" ] || [ $stale_inl = 1 ] || [ "$SRC/$f.hip" -nt "$OUT/$f.o" ] || [ "$SRC/common.h" -nt "$OUT/$f.o" ] || \
-     [ "$SRC/kernels.h" -nt "$OUT/$f.o" ] || [ "$SRC/op_view.h" -nt "$OUT/$f.o" ] || [ "$SRC/spec_device.h" -nt "$OUT/$f.o" ] || [ "$HERE/hip/hip_runtime.h" -nt "$OUT/$f.o" ] || \
+     [ "$SRC/kernels.h" -nt "$OUT/$f.o" ] || [ "$SRC/op_view.h" -nt "$OUT/$f.o" ] || [ "$SRC/refine_policy.h" -nt "$OUT/$f.o" ] || [ "$SRC/spec_device.h" -nt "$OUT/$f.o" ] || [ "$HERE/hip/hip_runtime.h" -nt "$OUT/$f.o" ] || \
      [ "$HERE/../../include/dqmc.h" -nt "$OUT/$f.o" ]; then
     g++ $FLAGS -c "$SRC/$f.hip" -o "$OUT/$f.o" &
     pids="$pids $!"
