@@ -475,6 +475,9 @@ struct Engine : dqmc_ctx {
     HIP_TRY(hipStreamSynchronize(st));
     rc = validate();
     if (rc) return rc;
+    // the determinant kernels of 45 .. 64 electrons use more LDS than the 64 KB a kernel gets unasked
+    if (N > 44 && (dqmc::slogdet_set_lds_limit<real>() != 0 || dqmc::slogdet_bwd_set_lds_limit<real>() != 0))
+      return fail(DQMC_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the determinant kernels of more than 44 electrons");
     analyse_lanes();
     analyse_chains();
     analyse_streams();

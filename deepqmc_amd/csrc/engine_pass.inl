@@ -3,7 +3,7 @@
 // streams, hipGraph capture and replay; wf_eval / local_energy / psi_grad entry points.
 
   static bool lanes_supported(int TP) {
-    return TP == 1 || TP == 16 || TP == 32 || TP == 48 || TP == 64 || TP == 96 || TP == 128;
+    return TP == 1 || (TP >= 16 && TP <= 208 && TP % 16 == 0);      // (every case of launch_linear: up to 64 electrons)
   }
 
   int plan(int B, int TP) {

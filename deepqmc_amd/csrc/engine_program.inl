@@ -62,7 +62,7 @@
           for (int t = 0; ok && t < 4; ++t) ok = o.w(t) >= 0 && fits_w(o.w(t), ne);
           break;
         }
-        case DQMC_OP_SLOGDET: ok = okb(v.slogdet.src()) && bufs[v.slogdet.src()].rows == sys.n_det && bufs[v.slogdet.src()].width >= N * N && N <= 44; break;
+        case DQMC_OP_SLOGDET: ok = okb(v.slogdet.src()) && bufs[v.slogdet.src()].rows == sys.n_det && bufs[v.slogdet.src()].width >= N * N && N <= 64; break;
         case DQMC_OP_FINAL:
           ok = (!v.fin.has_jastrow() || (okb(v.fin.jastrow()) && bufs[v.fin.jastrow()].rows == 1)) && (!v.fin.has_conf_coeff() || (size_t)(v.fin.conf_coeff() + sys.n_det) <= n_weights) &&
                v.fin.alphas() >= 0 && (size_t)(v.fin.alphas() + 2) <= n_weights && v.fin.cusp_kind() >= 0 && v.fin.cusp_kind() <= 2;

@@ -96,7 +96,7 @@
     const std::string name = rev_name(q.mode);
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
     if (has_attention()) return fail(DQMC_E_UNSUPPORTED, name + ": no reverse pass for ATTENTION ops");
-    if (q.mode != Rev::Orbs && N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 44 electrons");   // (Orbs forms no inverse)
+    if (q.mode != Rev::Orbs && N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 64 electrons");   // (Orbs forms no inverse)
     { const int rc = grad_tables(); if (rc) return rc; }
     if (q.mode == Rev::Orbs) { const int rc = orb_tables(); if (rc) return rc; }
     const long chunk = rev_chunk_len(q.mode, B);

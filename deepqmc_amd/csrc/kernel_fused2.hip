@@ -80,11 +80,13 @@ __device__ __forceinline__ void fused2_load_group(BSet<real>& s, const typename 
     s.b[1][dd] = w[qi + cb1];
   }
 }
-// first group of the unit described by nd (w_off, w_cb1, qstride, quads of its first piece)
+// first group of the unit described by nd (w_off, w_cb1, qstride, quads of its first piece; a unit on the bf16 pipe: the three
+// planes of its first chunk, 64 Vec4 apart -- as the nx_* fields a unit carries for its successor)
 template <typename real>
 __device__ __forceinline__ void fused2_prefetch_unit(const Fused2Args<real>& a, DescPtr nd, BSet<real>& s) {
   const typename RVec4<real>::type* nb = reinterpret_cast<const typename RVec4<real>::type*>(a.wpk) + nd->w_off + (threadIdx.x & 63);
-  fused2_load_group<real>(s, nb, nd->w_cb1, nd->qstride, nd->a_nq[0]);
+  const bool bf = nd->kind == 6 || nd->kind == 7;
+  fused2_load_group<real>(s, nb, nd->w_cb1, bf ? 64 : nd->qstride, bf ? 3 : nd->a_nq[0]);
 }
 
 // Epilogue shared by the unit bodies: bias + activation + residual, store to LDS (or HBM for buffers later kernels read).

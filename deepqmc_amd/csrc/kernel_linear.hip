@@ -1121,6 +1121,13 @@ template <typename real, int MR, int NR, int GPW, int WN> static void launch_cfg
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_linear<real, MR, NR, GPW, WN>), dim3(gx, gy), dim3(256 * WN), 0, st, a);
 }
+// the plain (f32 / f64 MFMA) kernel of one-wave groups, whatever the bf16-pipe option says
+template <typename real, int MR, int NR, int GPW, int WN> static void launch_cfg_plain(hipStream_t st, const LinArgs<real>& a) {
+  static_assert(GPW > 0 && MR > 1, "one-wave Laplacian groups");
+  const long n_groups = (long)a.B * a.nrows;
+  const unsigned gx = (unsigned)((n_groups + 4 * GPW - 1) / (4 * GPW)), gy = (unsigned)((a.ldw + 16 * NR * WN - 1) / (16 * NR * WN));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_linear<real, MR, NR, GPW, WN>), dim3(gx, gy), dim3(256 * WN), 0, st, a);
+}
 template <typename real, int MR, int NR, int GPW> static void launch_chain_cfg(hipStream_t st, const LinArgs<real>& a) {
   constexpr int BM = 64 * MR;
   const long n_groups = (long)a.B * a.nrows;
@@ -1177,6 +1184,16 @@ template <typename real, int MRH> static bool launch_split(hipStream_t st, const
   return false;
 }
 
+// Tall groups (80, 112 and 144 .. 208 lanes: 21-26, 32-36 and 43-64 electrons): one wave per group, MR row blocks, ONE column
+// tile of 4 (float32) / 2 (float64) column blocks per workgroup.  Not launch_nr: its 8-wave float32 form for even MR spills from
+// MR = 10 on, and the bf16-pipe form does from MR = 12 on; these instances use no scratch (DESIGN.md section 6 has the table).
+template <typename real, int MR> static void launch_tall(hipStream_t st, const LinArgs<real>& a) {
+  if constexpr (sizeof(real) == 4) {
+    if (a.ldw > 32) { launch_cfg_plain<real, MR, 4, 1, 1>(st, a); return; }
+  }
+  launch_cfg_plain<real, MR, 2, 1, 1>(st, a);      // (also the layers of up to 16 columns: no third instance per lane count)
+}
+
 template <typename real> void launch_linear(hipStream_t st, const LinArgs<real>& a) {
   switch (a.TP) {
     case 1: {
@@ -1213,8 +1230,15 @@ template <typename real> void launch_linear(hipStream_t st, const LinArgs<real>&
     case 32: launch_nr<real, 2, 1>(st, a); break;      // (H2O / PauliNet, 4096 walkers: E_loc-only +3 % against <4, 2>)
     case 48: launch_nr<real, 3, 1>(st, a); break;
     case 64: launch_nr<real, 4, 1>(st, a); break;
+    case 80: launch_tall<real, 5>(st, a); break;
     case 96: if (!launch_split<real, 3>(st, a)) launch_nr<real, 6, 1>(st, a); break;
+    case 112: launch_tall<real, 7>(st, a); break;
     case 128: if (!launch_split<real, 4>(st, a)) launch_nr<real, 8, 1>(st, a); break;
+    case 144: launch_tall<real, 9>(st, a); break;
+    case 160: launch_tall<real, 10>(st, a); break;
+    case 176: launch_tall<real, 11>(st, a); break;
+    case 192: launch_tall<real, 12>(st, a); break;
+    case 208: launch_tall<real, 13>(st, a); break;
     default: break;  // rejected by the engine before launch (lanes_supported)
   }
 }

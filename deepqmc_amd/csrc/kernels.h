@@ -174,6 +174,8 @@ __host__ __device__ inline int fused2_scratch_bytes(int WT, int N, int K, int re
 }
 template <typename real> void launch_fused2_value(hipStream_t st, const Fused2Args<real>& a, int n_blocks, size_t lds_bytes, int occ);
 template <typename real> int fused2_set_lds_limit(size_t lds_bytes);
+template <typename real> int slogdet_set_lds_limit();       // kernels_head.hip: the Laplacian-mode determinant kernels of 45..64 electrons
+template <typename real> int slogdet_bwd_set_lds_limit();   // kernels_grad.inl: k_slogdet_bwd past 44 electrons
 
 // ---- kernel_attention.hip ----
 // returns 0, or -1 if the (N, head_dim) tile set does not fit the 160 KiB LDS, -2 on a HIP error
@@ -426,7 +428,7 @@ template <typename real> struct FinalBwdArgs {
   int B, N, n_up, K;
 };
 template <typename real> void launch_final_bwd(hipStream_t st, const FinalBwdArgs<real>& a);
-constexpr int GRAD_GJ_NMAX = 44;      // largest N of the Gauss-Jordan inverse of k_slogdet_bwd (as the forward slogdet)
+constexpr int GRAD_GJ_NMAX = 64;      // largest N of the Gauss-Jordan inverse of k_slogdet_bwd (as the forward slogdet)
 template <typename real> void launch_slogdet_bwd(hipStream_t st, const real* orb, int orb_w, const double* dL, real* dorb, int B, int K, int N);
 // pw: per-walker partials double[B][4][K*N][n_nuc*n_env] of the pi_up / pi_down / zeta_up / zeta_down tables, or nullptr (the
 // backflow adjoint alone)

@@ -264,16 +264,17 @@ __global__ void __launch_bounds__(256) k_final_bwd(const real* __restrict__ r, c
 }
 
 // dA_k = dL_k A_k^-T for one (walker, determinant) per workgroup: Gauss-Jordan with partial pivoting on [A | I] in LDS,
-// double, N <= 44.  Matrices with dL_k = 0 (no weight, or a singular A_k: s_k = 0) keep a zero adjoint.
+// double, N <= GRAD_GJ_NMAX = 64.  Matrices with dL_k = 0 (no weight, or a singular A_k: s_k = 0) keep a zero adjoint.
 
 template <typename real>
 __global__ void __launch_bounds__(64) k_slogdet_bwd(const real* __restrict__ orb, int orb_w, const double* __restrict__ dL,
                                                     real* __restrict__ dorb, int N) {
-  __shared__ double M[GRAD_GJ_NMAX * 2 * GRAD_GJ_NMAX];
-  __shared__ double f[GRAD_GJ_NMAX];
+  HIP_DYNAMIC_SHARED(char, smem_raw)                 // M[N][2 N], f[N]: 66 KB at N = 64 (slogdet_bwd_set_lds_limit)
   __shared__ int piv;
   const long mat = blockIdx.x;
   const int t = threadIdx.x, W = 2 * N;
+  double* M = reinterpret_cast<double*>(smem_raw);
+  double* f = M + N * W;
   const double g = dL[mat];
   if (g == 0) return;
   const real* A = orb + mat * orb_w;
@@ -444,8 +445,15 @@ void launch_final_bwd(hipStream_t st, const FinalBwdArgs<real>& a) {
 }
 template <typename real>
 void launch_slogdet_bwd(hipStream_t st, const real* orb, int orb_w, const double* dL, real* dorb, int B, int K, int N) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_bwd<real>), dim3((unsigned)((long)B * K)), dim3(64), 0, st, orb, orb_w, dL, dorb, N);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_bwd<real>), dim3((unsigned)((long)B * K)), dim3(64), sizeof(double) * ((size_t)2 * N * N + N), st, orb, orb_w, dL, dorb, N);
 }
+// (called when a context of more than 44 electrons is created: the launch itself may be part of a captured graph)
+template <typename real> int slogdet_bwd_set_lds_limit() {
+  return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slogdet_bwd<real>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(sizeof(double) * (2 * GRAD_GJ_NMAX * GRAD_GJ_NMAX + GRAD_GJ_NMAX)));
+}
+template int slogdet_bwd_set_lds_limit<float>();
+template int slogdet_bwd_set_lds_limit<double>();
 template <typename real>
 void launch_orbitals_bwd(hipStream_t st, const real* r, const real* R, const real* bf, int bf_w, real* dbf, const real* dorb, int orb_w,
                          const real* pi_up, const real* pi_dn, const real* ze_up, const real* ze_dn, double* pw, int B, int N, int n_up,

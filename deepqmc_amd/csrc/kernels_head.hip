@@ -190,15 +190,11 @@ __global__ void __launch_bounds__(256) k_orbitals(const real* __restrict__ r, co
 // Gauss-Jordan with partial pivoting in LDS (double), sign = (-1)^swaps * prod sign(pivot)
 // -- the restatement of LAPACK getrf's sign/log|det| used by jnp.linalg.slogdet
 // (reference wf/nn_wave_function.py:36-39).  One 64-lane workgroup per (walker, determinant).
-template <typename real, int NMAX>
-__global__ void __launch_bounds__(64) k_slogdet(const real* __restrict__ orb, int orb_width,
-                                                double* __restrict__ logdet, int32_t* __restrict__ sign_k, int K,
-                                                LaneInfo li, double* __restrict__ cond) {
-  __shared__ double A[NMAX * NMAX];
-  __shared__ double Inv[NMAX * NMAX];
-  __shared__ double M[NMAX * NMAX];
-  __shared__ double colp[NMAX];
-  __shared__ int piv_s;
+// (the body: k_slogdet<NMAX> keeps its arrays in static LDS, N <= NMAX <= 44; k_slogdet_dyn in dynamic LDS, N <= 64)
+template <typename real>
+__device__ __forceinline__ void slogdet_scalar(double* A, double* Inv, double* M, double* colp, int& piv_s, const real* __restrict__ orb,
+                                               int orb_width, double* __restrict__ logdet, int32_t* __restrict__ sign_k,
+                                               LaneInfo li, double* __restrict__ cond) {
   const int N = li.N, NN = N * N;
   const int lane = threadIdx.x;
   const long bk = blockIdx.x;  // b*K + k
@@ -292,6 +288,28 @@ __global__ void __launch_bounds__(64) k_slogdet(const real* __restrict__ orb, in
     __syncthreads();
   }
   for (int t = li.T + lane; t < li.TP; t += 64) logdet[bk * li.TP + t] = 0.0;
+}
+template <typename real, int NMAX>
+__global__ void __launch_bounds__(64) k_slogdet(const real* __restrict__ orb, int orb_width,
+                                                double* __restrict__ logdet, int32_t* __restrict__ sign_k, int K,
+                                                LaneInfo li, double* __restrict__ cond) {
+  __shared__ double A[NMAX * NMAX];
+  __shared__ double Inv[NMAX * NMAX];
+  __shared__ double M[NMAX * NMAX];
+  __shared__ double colp[NMAX];
+  __shared__ int piv_s;
+  slogdet_scalar<real>(A, Inv, M, colp, piv_s, orb, orb_width, logdet, sign_k, li, cond);
+}
+// 45..64 electrons: 3 N^2 + N doubles of dynamic LDS (98.8 KB at N = 64: slogdet_set_lds_limit raises the kernel's limit)
+template <typename real>
+__global__ void __launch_bounds__(64) k_slogdet_dyn(const real* __restrict__ orb, int orb_width,
+                                                    double* __restrict__ logdet, int32_t* __restrict__ sign_k,
+                                                    LaneInfo li, double* __restrict__ cond) {
+  HIP_DYNAMIC_SHARED(char, smem_raw)
+  __shared__ int piv_s;
+  double* A = reinterpret_cast<double*>(smem_raw);
+  const int NN = li.N * li.N;
+  slogdet_scalar<real>(A, A + NN, A + 2 * NN, A + 3 * NN, piv_s, orb, orb_width, logdet, sign_k, li, cond);
 }
 
 // Laplacian-mode variant for 5..16 electrons: ONE wave per matrix like k_slogdet, but the per-lane products
@@ -623,6 +641,191 @@ __global__ void __launch_bounds__(256, 2) k_slogdet_mfma(const real* __restrict_
   for (int t = T + tid; t < li.TP; t += nthr) logdet[bk * li.TP + t] = 0.0;
 }
 
+// Laplacian-mode variant for 49..64 electrons: 4 x 4 tiles, EIGHT waves per matrix.  k_slogdet_mfma above stops at 3 x 3: its fourth
+// wave reduces the traces, and the B fragments of two lanes in flight for four column blocks would be 256 registers in float64.
+// Here wave w owns row block w & 3 and the column HALF w >> 2 (two tiles per lane: 64 fragment registers in flight in either
+// precision -- two lanes ahead in float32, one in float64), and there is no trace wave: sum_c tr(M_c^2) is only ever needed summed over c, so every thread
+// accumulates its 8 products M_ij M_ji of the PREVIOUS lane (from the other LDS buffer) in a register and the workgroup reduces
+// once, after the last lane; tr(M_c) is one wave reduction over the diagonal per lane (wave 7).  The inverse is the pivoted
+// Gauss-Jordan of k_slogdet_mfma on 512 threads -- same pivoting rule (first maximum in getrf's order), same sign convention, same
+// kappa.  LDS: two [64][65] double tiles (value matrix and inverse; M_c of even / odd lanes afterwards) = 67 KB: over the 64 KB a
+// kernel may use unasked, hence slogdet_set_lds_limit at context creation.
+constexpr size_t SLOGDET_MFMA64_LDS = sizeof(double) * (2 * 64 * 65 + 64 + 16);
+template <typename real>
+__global__ void __launch_bounds__(512) k_slogdet_mfma64(const real* __restrict__ orb, int orb_width,
+                                                        double* __restrict__ logdet, int32_t* __restrict__ sign_k,
+                                                        LaneInfo li, double* __restrict__ cond) {
+  HIP_DYNAMIC_SHARED(char, smem_raw)
+  constexpr int N16 = 64, NS = N16 + 1, NTHR = 512;
+  const int N = li.N, NN = N * N, T = li.T;      // 48 < N <= 64
+  double* A = reinterpret_cast<double*>(smem_raw);     // [64][NS] value matrix, then M_c of the odd lanes
+  double* Inv = A + N16 * NS;                           // [64][NS], zero outside N x N; then M_c of the even lanes
+  double* colp = Inv + N16 * NS;                        // [64]
+  __shared__ int piv_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const long bk = blockIdx.x;  // b*K + k
+  const real* base = orb + bk * li.TP * orb_width;
+  for (int e = tid; e < N16 * N16; e += NTHR) {
+    const int i = e >> 6, j = e & 63;
+    const bool in = i < N && j < N;
+    A[i * NS + j] = in ? (double)base[i * N + j] : 0.0;
+    Inv[i * NS + j] = (in && i == j) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  double logabs = 0.0;
+  int sgn = 1;
+  constexpr int MAXU = 8;                                   // N * N <= 4096 = 8 x 512
+  int e_row[MAXU], e_off[MAXU];
+#pragma unroll
+  for (int u = 0; u < MAXU; ++u) {
+    const int e = tid + u * NTHR;
+    const int i = e / N, j = e - i * N;
+    e_row[u] = e < NN ? i : -1;
+    e_off[u] = i * NS + j;
+  }
+  for (int p = 0; p < N; ++p) {
+    if (wave == 0) {
+      // pivot search by one wave (N <= 64 rows): largest |A[i][p]|, i >= p; ties to the smaller row, as LAPACK idamax
+      double bv = (lane >= p && lane < N) ? fabs(A[lane * NS + p]) : -1.0;
+      int best = lane;
+#pragma unroll
+      for (int m = 1; m < 64; m <<= 1) {
+        const double ov = __shfl_xor(bv, m, 64);
+        const int ob = __shfl_xor(best, m, 64);
+        if (ov > bv || (ov == bv && ob < best)) { bv = ov; best = ob; }
+      }
+      if (lane == 0) piv_s = best;
+    }
+    __syncthreads();
+    const int q = piv_s;
+    if (q != p) {
+      for (int j = tid; j < N; j += NTHR) {
+        double t0 = A[p * NS + j]; A[p * NS + j] = A[q * NS + j]; A[q * NS + j] = t0;
+        t0 = Inv[p * NS + j]; Inv[p * NS + j] = Inv[q * NS + j]; Inv[q * NS + j] = t0;
+      }
+      sgn = -sgn;
+    }
+    __syncthreads();
+    const double piv = A[p * NS + p];
+    if (tid == 0) logabs += log(fabs(piv));                 // (only thread 0 writes log|det|)
+    if (piv < 0) sgn = -sgn;
+    if (piv == 0) sgn = 0;
+    __syncthreads();
+    const double ip = 1.0 / piv;
+    for (int j = tid; j < N; j += NTHR) { A[p * NS + j] *= ip; Inv[p * NS + j] *= ip; }
+    for (int i = tid; i < N; i += NTHR) colp[i] = A[i * NS + p];
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+      const int i = e_row[u];
+      if (i >= 0 && i != p) {
+        const double f = colp[i];
+        const int j = e_off[u] - i * NS;
+        A[e_off[u]] -= f * A[p * NS + j];
+        Inv[e_off[u]] -= f * Inv[p * NS + j];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    logdet[bk * li.TP] = logabs;
+    sign_k[bk] = sgn;
+  }
+  if (cond) {      // kappa = sum |A_ij| |(A^-1)_ji| / N; colp is free after the elimination
+    double c = 0.0;
+    for (int e = tid; e < NN; e += NTHR) {
+      const int i = e / N, j = e - i * N;
+      c += fabs((double)base[e]) * fabs(Inv[j * NS + i]);
+    }
+    c = wave_sum<double>(c);
+    if (lane == 0) colp[wave] = c;
+    __syncthreads();
+    if (tid == 0) cond[bk] = (((colp[0] + colp[1]) + (colp[2] + colp[3])) + ((colp[4] + colp[5]) + (colp[6] + colp[7]))) / N;
+    __syncthreads();
+  }
+  // ---- derivative lanes: M_c = A^-1 dA_c, B fragments of dA_c straight from global memory in operand order, two lanes ahead ----
+  typedef Mfma<double>::acc_t acc_t;
+  const int rb = wave & 3, ch = wave >> 2;
+  double fa[16];                                            // this wave's row block of A^-1 as MFMA A fragments
+#pragma unroll
+  for (int kk = 0; kk < 16; ++kk) fa[kk] = Inv[(rb * 16 + l15) * NS + kk * 4 + l4];
+  __syncthreads();                                          // (Inv and A are free from here on)
+  double* Mbuf[2] = {Inv, A};
+  // dA_c[4 kk + l4][16 (2 ch + cb) + l15] of two lanes in flight -- of one in float64, where two sets (128 registers) next to fa
+  // and the accumulators do not fit the 256 registers of two waves per SIMD (the compiler spilled 5 .. 85 of them)
+  constexpr int AHEAD = sizeof(real) == 8 ? 1 : 2;
+  real fbA[2][16], fbB[2][16];
+  // (rows k >= N are read from row N - 1 instead of being predicated: they meet the zero columns of A^-1; one predicate per column
+  // block is all a thread keeps.  This assumes FINITE orbitals and inverse: an Inf / NaN in row N - 1 of dA_c or in A^-1 -- a
+  // singular matrix, sign 0 -- reaches every lane of that determinant through 0 * Inf, where the predicated 3 x 3 kernel would
+  // confine it to the entries it touches; such a walker's lanes are non-finite either way)
+  const int col0 = ch * 32 + l15;
+  const bool cok0 = col0 < N, cok1 = col0 + 16 < N;
+  const int off_lo = l4 * N + col0;
+  int off_hi[4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x) off_hi[x] = ((48 + 4 * x + l4 < N) ? 48 + 4 * x + l4 : N - 1) * N + col0;
+  auto load_frags = [&](real (&fb)[2][16], int t) {
+    if (t >= T) return;                                     // (uniform; the stale fragments are never multiplied)
+    const real* At = base + (long)t * orb_width;
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      // (rows below 48 exist whatever N: one lane offset and a uniform row base per load)
+      const real* row = kk < 12 ? At + (kk * 4) * N + off_lo : At + off_hi[kk < 12 ? 0 : kk - 12];
+      fb[0][kk] = cok0 ? row[0] : (real)0;
+      fb[1][kk] = cok1 ? row[16] : (real)0;
+    }
+  };
+  double t2_acc = 0.0, tr_last = 0.0;
+  // iteration `it`: M of lane it (it < T) goes to Mbuf[it & 1]; the traces of lane it - 1 are taken from the other buffer
+  auto step = [&](real (&fb)[2][16], int it) {
+    if (it < T) {
+      double* Mo = Mbuf[it & 1];
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        acc_t acc = acc_t{0, 0, 0, 0};
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) acc = Mfma<double>::run(fa[kk], (double)fb[cb][kk], acc);
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) Mo[(rb * 16 + Mfma<double>::row_of(lane, rg)) * NS + (ch * 2 + cb) * 16 + l15] = acc[rg];
+      }
+      load_frags(fb, it + AHEAD);                           // this register set is free again
+    }
+    if (it >= 2 && it <= T) {
+      const int t = it - 1;                                 // 1 <= t < T
+      const double* Mi = Mbuf[t & 1];
+      const bool need2 = t < T - 1;
+      if (need2) {
+        // (the tile is zero outside N x N: rows from the zero rows of A^-1, columns from the zero B fragments)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = wave + 8 * u;
+          t2_acc += Mi[i * NS + lane] * Mi[lane * NS + i];
+        }
+      }
+      if (wave == 7) {
+        const double tr = wave_sum<double>(Mi[lane * NS + lane]);
+        if (need2) { if (lane == 0) logdet[bk * li.TP + t] = tr; }
+        else tr_last = tr;
+      }
+    }
+    __syncthreads();
+  };
+  load_frags(fbA, 1);
+  if (AHEAD == 2) load_frags(fbB, 2);
+  for (int it = 1; it <= T; it += 2) {
+    step(fbA, it);
+    step(AHEAD == 2 ? fbB : fbA, it + 1);
+  }
+  t2_acc = wave_sum<double>(t2_acc);
+  if (lane == 0) colp[wave] = t2_acc;
+  __syncthreads();
+  if (wave == 7 && lane == 0)
+    logdet[bk * li.TP + T - 1] = tr_last - (((colp[0] + colp[1]) + (colp[2] + colp[3])) + ((colp[4] + colp[5]) + (colp[6] + colp[7])));
+  for (int t = T + tid; t < li.TP; t += NTHR) logdet[bk * li.TP + t] = 0.0;
+}
+
 // Value-only variant (Metropolis sub-steps, ECP quadrature walkers; T = 1): sign and log|det| need only
 // the LU factorisation, not the inverse.  One wave per matrix, the matrix in LDS (double, odd row stride);
 // per pivot: wave-wide arg-max over the column (first maximum, as LAPACK idamax), row swap, and the rank-1
@@ -740,29 +943,18 @@ __global__ void __launch_bounds__(256) k_slogdet_lu16(const real* __restrict__ o
   }
 }
 
-// Value-only variant for 17..44 electrons: the register scheme of k_slogdet_lu16 with LPM = 32 (two matrices per wave,
-// N <= 32) or 64 lanes per matrix, lane i keeps row i (NC >= N columns) in registers.  The LDS-resident k_slogdet_lu
+// Value-only variant for 17..64 electrons: the register scheme of k_slogdet_lu16 with LPM = 32 (two matrices per wave,
+// N <= 32) or 64 lanes per matrix (NC = 44 or 64 columns), lane i keeps row i (NC >= N columns) in registers.  The LDS-resident k_slogdet_lu
 // above spends two workgroup barriers and a 64-wide reduction per pivot on a matrix that fits the register file: 4.9 ms
 // for the 368 k 30 x 30 determinants of one quadrature batch of benzene + ECP.  Same pivoting rule (first maximum in
 // getrf's swapped order), same sign convention.
-template <typename real, int NC, int LPM>
-__global__ void __launch_bounds__(256) k_slogdet_reg(const real* __restrict__ orb, int orb_width, double* __restrict__ logdet,
-                                                     int32_t* __restrict__ sign_k, long n_mat, LaneInfo li) {
-  const int N = li.N;
-  const int lane = threadIdx.x & 63, row = lane & (LPM - 1), g0 = lane & ~(LPM - 1);      // g0: first lane of this matrix's group
-  const long bk_raw = ((long)blockIdx.x * blockDim.x + threadIdx.x) / LPM;
-  const bool live = bk_raw < n_mat;
-  const long bk = live ? bk_raw : n_mat - 1;               // idle groups shadow the last matrix (all lanes stay in the shuffles)
-  const real* base = orb + bk * li.TP * orb_width;
-  double a[NC];
+// BLK consecutive pivots P0 .. P0 + BLK - 1 of k_slogdet_reg.  The 32- and 44-column instances run all their pivots as one block;
+// the 64-column one takes four blocks of 16: 64 pivots x up to 63 columns in ONE loop nest is more than `#pragma unroll` will
+// unroll -- the pivot loop stayed a loop and a[] went to scratch.
+template <int P0, int BLK, int NC, int LPM>
+__device__ __forceinline__ void reg_lu_pivots(double (&a)[NC], int& pos, bool& used, double& logabs, int& sgn, int N, int row, int g0) {
 #pragma unroll
-  for (int j = 0; j < NC; ++j) a[j] = (row < N && j < N) ? (double)base[row * N + j] : 0.0;
-  int pos = row;                                           // current position of this row in getrf's swapped order
-  bool used = row >= N;
-  double logabs = 0.0;
-  int sgn = 1;
-#pragma unroll
-  for (int p = 0; p < NC; ++p) {
+  for (int p = P0; p < P0 + BLK; ++p) {
     if (p < N) {                                           // (uniform over the launch)
       double bv = used ? -1.0 : fabs(a[p]);
       int bpos = used ? 1 << 20 : pos, bl = row;
@@ -789,6 +981,31 @@ __global__ void __launch_bounds__(256) k_slogdet_reg(const real* __restrict__ or
         }
       }
     }
+  }
+}
+template <typename real, int NC, int LPM>
+__global__ void __launch_bounds__(256) k_slogdet_reg(const real* __restrict__ orb, int orb_width, double* __restrict__ logdet,
+                                                     int32_t* __restrict__ sign_k, long n_mat, LaneInfo li) {
+  const int N = li.N;
+  const int lane = threadIdx.x & 63, row = lane & (LPM - 1), g0 = lane & ~(LPM - 1);      // g0: first lane of this matrix's group
+  const long bk_raw = ((long)blockIdx.x * blockDim.x + threadIdx.x) / LPM;
+  const bool live = bk_raw < n_mat;
+  const long bk = live ? bk_raw : n_mat - 1;               // idle groups shadow the last matrix (all lanes stay in the shuffles)
+  const real* base = orb + bk * li.TP * orb_width;
+  double a[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) a[j] = (row < N && j < N) ? (double)base[row * N + j] : 0.0;
+  int pos = row;                                           // current position of this row in getrf's swapped order
+  bool used = row >= N;
+  double logabs = 0.0;
+  int sgn = 1;
+  if constexpr (NC == 64) {
+    reg_lu_pivots<0, 16, NC, LPM>(a, pos, used, logabs, sgn, N, row, g0);
+    reg_lu_pivots<16, 16, NC, LPM>(a, pos, used, logabs, sgn, N, row, g0);
+    reg_lu_pivots<32, 16, NC, LPM>(a, pos, used, logabs, sgn, N, row, g0);
+    reg_lu_pivots<48, 16, NC, LPM>(a, pos, used, logabs, sgn, N, row, g0);
+  } else {
+    reg_lu_pivots<0, NC, NC, LPM>(a, pos, used, logabs, sgn, N, row, g0);
   }
   if (live && row == 0) {
     logdet[bk * li.TP] = logabs;
@@ -1105,7 +1322,8 @@ void launch_orbitals(hipStream_t st, const real* r, const real* R, const real* b
 }
 
 // use_mfma (engine option "slogdet_mfma"): 1 = f64-MFMA derivative traces (N > 16: k_slogdet_mfma, 4 waves per matrix;
-// 5 <= N <= 16: k_slogdet_w16, one wave per matrix), 2 = k_slogdet_mfma from N > 8 on, 3 = as 1 without k_slogdet_w16, 0 = never
+// 5 <= N <= 16: k_slogdet_w16, one wave per matrix; N > 48: k_slogdet_mfma64, 8 waves per matrix), 2 = k_slogdet_mfma from N > 8 on,
+// 3 = as 1 without k_slogdet_w16 and with the LDS-resident value-only k_slogdet_lu, 0 = never (N > 44: k_slogdet_dyn)
 template <typename real>
 void launch_slogdet(hipStream_t st, const real* orb, int orb_width, double* logdet, int32_t* sign_k, int B, int K,
                     LaneInfo li, int use_mfma, double* cond) {
@@ -1131,6 +1349,9 @@ void launch_slogdet(hipStream_t st, const real* orb, int orb_width, double* logd
   else if (li.T == 1 && li.N <= 44 && slogdet_use_mfma != 3)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_reg<real, 44, 64>), dim3((unsigned)((n_mat * 64 + 255) / 256)), dim3(256), 0, st, orb, orb_width,
                        logdet, sign_k, n_mat, li);
+  else if (li.T == 1 && li.N <= 64 && slogdet_use_mfma != 3)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_reg<real, 64, 64>), dim3((unsigned)((n_mat * 64 + 255) / 256)), dim3(256), 0, st, orb, orb_width,
+                       logdet, sign_k, n_mat, li);
   else if (li.T == 1)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_lu<real>), dim3(grid), dim3(64), sizeof(double) * li.N * (li.N | 1), st,
                        orb, orb_width, logdet, sign_k, li);
@@ -1138,6 +1359,11 @@ void launch_slogdet(hipStream_t st, const real* orb, int orb_width, double* logd
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_mfma<real>), dim3(grid), dim3(256),
                        sizeof(double) * ((size_t)3 * (((li.N + 15) / 16) * 16) * ((((li.N + 15) / 16) * 16) + 1) + (((li.N + 15) / 16) * 16) + 16),
                        st, orb, orb_width, logdet, sign_k, li, cond);
+  else if (li.N > 48 && slogdet_use_mfma >= 1)                                 // 4 x 4 tiles on eight waves
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_mfma64<real>), dim3(grid), dim3(512), SLOGDET_MFMA64_LDS, st, orb, orb_width, logdet, sign_k, li, cond);
+  else if (li.N > 44)                                                          // the scalar kernel past its static arrays
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_dyn<real>), dim3(grid), dim3(64), sizeof(double) * ((size_t)3 * li.N * li.N + li.N), st, orb, orb_width,
+                       logdet, sign_k, li, cond);
   else if (li.N <= 16 && slogdet_use_mfma >= 1 && slogdet_use_mfma != 3)     // one wave per matrix, derivative traces on the f64 matrix cores
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet_w16<real>), dim3(grid), dim3(64), 0, st, orb, orb_width, logdet, sign_k, li, cond);
   else if (li.N <= 8)
@@ -1150,6 +1376,16 @@ void launch_slogdet(hipStream_t st, const real* orb, int orb_width, double* logd
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slogdet<real, 44>), dim3(grid), dim3(64), 0, st, orb, orb_width, logdet,
                        sign_k, K, li, cond);
 }
+
+// The two Laplacian-mode kernels of 45..64 electrons need more dynamic LDS than a kernel may use unasked (64 KB): raise their
+// limits once, when a context with such a program is created (not at launch: a launch may be inside a graph capture).
+template <typename real> int slogdet_set_lds_limit() {
+  int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slogdet_mfma64<real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SLOGDET_MFMA64_LDS);
+  rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_slogdet_dyn<real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * (3 * 64 * 64 + 64)));
+  return rc;
+}
+template int slogdet_set_lds_limit<float>();
+template int slogdet_set_lds_limit<double>();
 
 template <typename real> void launch_final(hipStream_t st, const FinalArgs& a) {
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<real>), dim3((unsigned)((a.B + 15) / 16)), dim3(256), 0, st, a);

@@ -106,8 +106,11 @@ enum dqmc_op_kind {
    * n_env = 3 with pi = 1: the SimplifiedNucleusDependentEnvelopes of env.py:110-226). */
   DQMC_OP_ORBITALS = 8,
   /* i: [0]=orbital buf.  sign/log|det| of the K matrices and their forward-Laplacian
-   * lanes, kept in double inside the context (wf/nn_wave_function.py:36-39).  At most 44 electrons (the
-   * largest LDS-resident Gauss-Jordan instance); programs with more are rejected at creation (DQMC_E_ARG). */
+   * lanes, kept in double inside the context (wf/nn_wave_function.py:36-39).  At most 64 electrons (4 x 4
+   * tiles of the float64 MFMA determinant kernel, one wave of rows for the pivot search; the kernels of 45 .. 64
+   * electrons use up to 99 KB of LDS, which creation requests: DQMC_E_HIP if the device refuses); programs with more
+   * are rejected at creation (DQMC_E_ARG).  The forward-Laplacian pass runs with TP = round_up(3 N + 2, 16) lanes,
+   * every multiple of 16 up to 208; nothing is padded beyond that. */
   DQMC_OP_SLOGDET = 9,
   /* i: [0]=jastrow buf or -1 [1]=conf_coeff weight offset or -1 (SumPool) [2]=cusp kind
    * (0 none,1 deepqmc,2 psiformer) [3]=weight offset of {same_alpha, anti_alpha}.
@@ -339,7 +342,7 @@ int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const v
  * Same conventions as dqmc_log_psi_vjp: walkers with sign 0 or a non-finite log|psi| get an all-zero row; constant and
  * padding entries get what their position accumulates (padding of linear layers: exact zeros); walker chunks per
  * "ws_budget_mb" (dqmc_last_chunks); no atomics, so identical calls are bit-identical, and a chunked call equals an
- * unchunked one bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
+ * unchunked one bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as dqmc_log_psi_vjp. */
 int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, void* jac, size_t ld_jac,
                           void* logpsi, int32_t* sign);
 
@@ -365,7 +368,7 @@ int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, vo
  *     (the values dqmc_log_psi_jacobian writes into those columns; invalid walkers get zeros);  logpsi / sign optional.
  * One value pass and one reverse pass (unit cotangent) per walker chunk ("ws_budget_mb", dqmc_last_chunks); the cotangent
  * weights the walker sums of grad.  No atomics: identical calls are bit-identical; with cot == NULL grad equals
- * dqmc_log_psi_vjp's bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
+ * dqmc_log_psi_vjp's bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as dqmc_log_psi_vjp. */
 int dqmc_kfac_layout(dqmc_ctx* ctx, int* n_linear, size_t* n_factor_doubles, size_t* n_rest);
 int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, double* factors,
                       void* rest, void* logpsi, int32_t* sign);
@@ -376,7 +379,7 @@ int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const 
  * no weight gradients: the adjoints of the feature, envelope and cusp inputs are carried into the coordinates.  Sums over
  * the electrons and nuclei run in a fixed order (no atomics): identical calls are bit-identical, and a chunked call equals
  * an unchunked one bit for bit.  Walkers with sign 0 or a non-finite log|psi| get zero rows.  By translation invariance
- * sum_a grad_R[b][a] = -sum_i grad_r[b][i].  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as dqmc_log_psi_vjp. */
+ * sum_a grad_R[b][a] = -sum_i grad_r[b][i].  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as dqmc_log_psi_vjp. */
 int dqmc_log_psi_grad_coords(dqmc_ctx* ctx, const void* r, const void* R, int B, void* grad_r, void* grad_R,
                              void* logpsi, int32_t* sign);
 
@@ -427,7 +430,7 @@ int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, in
  *          parts[1] = -G (BARE: force = parts[0] + parts[1]).
  *   The rotation is the one set by the preceding dqmc_ecp_rotation: the same seed or angles give the vertices of the
  *   dqmc_local_energy call.
- * DQMC_E_ARG when no Gaussian ECP is set or a pseudo-Hamiltonian is; DQMC_E_UNSUPPORTED for ATTENTION programs and N > 44, as
+ * DQMC_E_ARG when no Gaussian ECP is set or a pseudo-Hamiltonian is; DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as
  * dqmc_log_psi_grad_coords.  An ECP with local terms only is valid: parts[1] is zero and no reverse pass runs unless AC_ZB
  * needs gR_0.  A walker with sign 0 or a non-finite log|psi| gets NaN rows in parts[1] and force; a quadrature configuration
  * with sign 0 or a non-finite log|psi| contributes ratio 0.  Fixed-order sums, no atomics: identical calls are bit-identical,
