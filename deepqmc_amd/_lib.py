@@ -54,6 +54,9 @@ SIGNATURES = [
     ('dqmc_psi_ratio', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     ('dqmc_clip_rows', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     ('dqmc_loss_cotangents', c_int, [c_void_p, POINTER(DqmcLossTerms), c_void_p, c_void_p]),
+    ('dqmc_oscillator_strength', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ('dqmc_fd_displace', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p]),
+    ('dqmc_fd_force', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p]),
     ('dqmc_wf_eval', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     ('dqmc_local_energy', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ('dqmc_psi_grad', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

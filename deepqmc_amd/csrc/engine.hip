@@ -10,7 +10,8 @@
 // refine_policy.h), ECP / pseudo-Hamiltonian (engine_ecp.inl), samplers (engine_mcmc.inl), the reverse
 // pass (engine_grad.inl, engine_reverse.inl) and the plans and entry points of its modes (engine_jac.inl, engine_kfac.inl;
 // engine_coords.inl, with the force estimators; engine_ecp_force.inl, the ECP force), SCF-orbital pretraining (engine_pretrain.inl), the device-resident optimiser
-// step (engine_optim.inl), the KFAC preconditioner on its vectors (engine_kfacopt.inl) -- and
+// step (engine_optim.inl), the KFAC preconditioner on its vectors (engine_kfacopt.inl), the loss assembly (engine_loss.inl),
+// the observables of the training loop (engine_observable.inl) -- and
 // are included inside the struct body: one translation unit, as before.  The slot layout of dqmc_op lives in op_view.h: all of
 // the above read an op through its named views, never by slot number.
 #include <hip/hip_runtime.h>
@@ -170,6 +171,10 @@ struct dqmc_ctx {
   virtual int clip_rows(const double* x, const double* w, int n_rows, long B, int center, int scale, double clip_width,
                         double exclude_width, double* x_clip, uint8_t* mask, double* row_stats) = 0;
   virtual int loss_cotangents(const dqmc_loss_terms* t, double* c, double* k) = 0;
+  virtual int oscillator_strength(const void* r, const double* ratio, const void* e_loc, int S, long B, double* os_mean, double* os_err,
+                                  double* cd_mean, double* cd_err) = 0;
+  virtual int fd_displace(const void* r, const void* R, long B, double h, void* r_out, void* R_out) = 0;
+  virtual int fd_force(const void* log_d, const void* log_0, const void* e_d, const void* e_0, long B, double h, double* F) = 0;
   virtual int mcmc(void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R, int B, int n_sub,
                    int max_age, double target, uint64_t seed, const void* noise, const void* unif, uint8_t* accept_out,
                    double* stats7) = 0;
@@ -504,6 +509,7 @@ struct Engine : dqmc_ctx {
 #include "engine_optim.inl"
 #include "engine_kfacopt.inl"
 #include "engine_loss.inl"
+#include "engine_observable.inl"
 };
 
 }  // namespace
@@ -708,6 +714,22 @@ int dqmc_loss_cotangents(dqmc_ctx* ctx, const dqmc_loss_terms* terms, double* c,
   if (!ctx || !terms || !c) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->loss_cotangents(terms, c, k);
+}
+int dqmc_oscillator_strength(dqmc_ctx* ctx, const void* r, const double* psi_ratio, const void* e_loc, int S, int B, double* os_mean,
+                             double* os_err, double* cd_mean, double* cd_err) {
+  if (!ctx || !r || !psi_ratio || !e_loc || !os_mean || !os_err || !cd_mean || !cd_err) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->oscillator_strength(r, psi_ratio, e_loc, S, B, os_mean, os_err, cd_mean, cd_err);
+}
+int dqmc_fd_displace(dqmc_ctx* ctx, const void* r, const void* R, int B, double h, void* r_out, void* R_out) {
+  if (!ctx || !r || !R || !r_out || !R_out) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->fd_displace(r, R, B, h, r_out, R_out);
+}
+int dqmc_fd_force(dqmc_ctx* ctx, const void* log_d, const void* log_0, const void* e_d, const void* e_0, int B, double h, double* F) {
+  if (!ctx || !log_d || !log_0 || !e_d || !e_0 || !F) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->fd_force(log_d, log_0, e_d, e_0, B, h, F);
 }
 int dqmc_mcmc_steps(dqmc_ctx* ctx, void* r, void* logpsi, int32_t* sign, int32_t* age, void* tau, const void* R,
                     int B, int n_sub, int max_age, double target_acceptance, uint64_t seed, const void* noise,

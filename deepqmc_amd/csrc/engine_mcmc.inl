@@ -233,6 +233,7 @@
   }
 
   int debug_read(int buf, double* out, size_t n) override {
+    if (buf == -5) return read_os_moments(out, n);      // (engine_observable.inl; needs no evaluation pass)
     if (last_B == 0) return fail(DQMC_E_ARG, "no evaluation has run yet");
     HIP_TRY(hipStreamSynchronize(st));
     if (buf == -1) {

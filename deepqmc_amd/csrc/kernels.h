@@ -622,4 +622,18 @@ void launch_clip_rows(hipStream_t st, const double* x, const double* w, int n_ro
                       double clip_width, double exclude_width, double* x_clip, uint8_t* mask, double* row_stats);
 void launch_loss_cotangents(hipStream_t st, const LossCotArgs& a);
 
+// ---- kernels_observable.inl (included by kernels_ecp.hip): observables of the training loop (dqmc_oscillator_strength, dqmc_fd_displace, dqmc_fd_force) ----
+// r: real[S][B][N][3], ratio: double[S][S][B], e_loc: real[S][B]; mom: double[2 S + 3 S^2] scratch = E mean, E std, cd std;
+// os_mean, os_err: double[S][S]; cd_mean, cd_err: double[S][S][3].  Two launches.
+template <typename real>
+void launch_oscillator_strength(hipStream_t st, const real* r, const double* ratio, const real* e_loc, int S, long B, int N, double* mom,
+                                double* os_mean, double* os_err, double* cd_mean, double* cd_err);
+// r_out: real[3 n_nuc][B][N][3], R_out: real[3 n_nuc][n_nuc][3]: the displaced copies of the finite-difference force, one launch
+template <typename real>
+void launch_fd_displace(hipStream_t st, const real* r, const real* R, long B, int N, int n_nuc, double h, real* r_out, real* R_out);
+// F: double[B][D] from log_d, e_d: real[D][B] and log_0, e_0: real[B]
+template <typename real>
+void launch_fd_force(hipStream_t st, const real* log_d, const real* log_0, const real* e_d, const real* e_0, long B, int D, double h,
+                     double* F);
+
 }  // namespace dqmc

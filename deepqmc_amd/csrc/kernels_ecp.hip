@@ -615,3 +615,5 @@ DQMC_INST(double)
 #undef DQMC_INST
 
 }  // namespace dqmc
+
+#include "kernels_observable.inl"

@@ -46,7 +46,7 @@ def _call(wf, est, rows, rng, params, phys_conf, ecp_phi=None, e_loc=None, energ
     r, R = _split(phys_conf)
     eng = wf.engine(params, R)
     if est == 'ac_zb':
-        e_loc = eng._t(e_loc).reshape(-1)
+        e_loc, energy = _force._centred(eng, e_loc, energy)      # (a device-tensor energy is subtracted on the device)
     return eng.ecp_force(est, r, R, rng=rng, ecp_phi=ecp_phi, e_loc=e_loc, energy=float(energy), rows=rows,
                          return_parts=return_parts)
 

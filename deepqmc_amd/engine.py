@@ -439,6 +439,53 @@ class Engine:
         self._check(self.lib.dqmc_loss_cotangents(self._ctx, ctypes.byref(t), c.data_ptr(), _ptr(k)))
         return c, k
 
+    # ---- observables of the training loop (dqmc_oscillator_strength, dqmc_fd_displace, dqmc_fd_force) ----
+    def oscillator_strength(self, r, psi_ratio, e_loc):
+        """Oscillator strengths between S electronic states from r [S, B, N, 3] and e_loc [S, B] (the engine's dtype) and
+        psi_ratio [S, S, B] (float64, as `psi_ratio` returns it): (os_mean [S, S], os_err [S, S], cd_mean [S, S, 3],
+        cd_err [S, S, 3]), float64 device tensors (dqmc_oscillator_strength; formulas in include/dqmc.h).  The diagonal is
+        os_mean 0, os_err NaN, as in the reference.  Two launches, nothing waits for the host."""
+        r = self._arg('r', self._t(r), self.dtype, (None, None, self.N, 3))
+        S, B = r.shape[:2]
+        self._arg('psi_ratio', psi_ratio, torch.float64, (S, S, B))
+        e_loc = self._arg('e_loc', self._t(e_loc), self.dtype, (S, B))
+        os_mean, os_err = (torch.empty(S, S, dtype=torch.float64, device=self.device) for _ in range(2))
+        cd_mean, cd_err = (torch.empty(S, S, 3, dtype=torch.float64, device=self.device) for _ in range(2))
+        self._check(self.lib.dqmc_oscillator_strength(self._ctx, r.data_ptr(), psi_ratio.data_ptr(), e_loc.data_ptr(), S, B,
+                                                      os_mean.data_ptr(), os_err.data_ptr(), cd_mean.data_ptr(), cd_err.data_ptr()))
+        return os_mean, os_err, cd_mean, cd_err
+
+    def oscillator_moments(self, S):
+        """Test access (dqmc_debug_read -5; a host copy): the moments of the last oscillator_strength call between its two
+        launches, (E [S], std_E [S], cd_std [S, S, 3]) as NumPy arrays."""
+        out = np.empty(S * (2 + 3 * S), np.float64)
+        self._check(self.lib.dqmc_debug_read(self._ctx, -5, _np_ptr(out), out.size))
+        return out[:S], out[S:2 * S], out[2 * S:].reshape(S, S, 3)
+
+    def fd_displace(self, r, R=None, h=1e-3):
+        """The displaced copies of the finite-difference force (dqmc_fd_displace): (r_d [D, B, N, 3], R_d [D, n_nuc, 3]) in the
+        engine's dtype, D = 3 n_nuc; displacement d = 3 n0 + j0 moves nucleus n0 by -h along j0 and every electron by +h times
+        its softmax weight of that nucleus (computed in float64)."""
+        r, R, B = self._walkers(r, R)
+        D = 3 * self.hamil.n_nuc
+        r_d = torch.empty(D, B, self.N, 3, dtype=self.dtype, device=self.device)
+        R_d = torch.empty(D, self.hamil.n_nuc, 3, dtype=self.dtype, device=self.device)
+        self._check(self.lib.dqmc_fd_displace(self._ctx, r.data_ptr(), R.data_ptr(), B, float(h), r_d.data_ptr(), R_d.data_ptr()))
+        return r_d, R_d
+
+    def fd_force(self, log_d, log_0, e_d, e_0, h):
+        """F [B, n_nuc, 3] float64 = exp(2 (log_d - log_0)) (e_d - e_0) / h from log_d, e_d [D, B] and log_0, e_0 [B] in the
+        engine's dtype (dqmc_fd_force)."""
+        D = 3 * self.hamil.n_nuc
+        B = self._arg('log_0', log_0, self.dtype, (None,)).shape[0]
+        self._arg('log_d', log_d, self.dtype, (D, B))
+        self._arg('e_d', e_d, self.dtype, (D, B))
+        self._arg('e_0', e_0, self.dtype, (B,))
+        F = torch.empty(B, self.hamil.n_nuc, 3, dtype=torch.float64, device=self.device)
+        self._check(self.lib.dqmc_fd_force(self._ctx, log_d.data_ptr(), log_0.data_ptr(), e_d.data_ptr(), e_0.data_ptr(), B, float(h),
+                                           F.data_ptr()))
+        return F
+
     # ---- ansatz.apply ---------------------------------------------------
     def wf_eval(self, r, R=None):
         r, R, B = self._walkers(r, R)

@@ -13,6 +13,11 @@ pseudo-Hamiltonian are not supported by the estimators of this module (NotImplem
 rejects them, and the bare ECP force needs the gradient of the non-local term, which `deepqmc_amd.ecp_force` provides for
 Gaussian-type ECPs (evaluate_hf_force_bare, evaluate_hf_force_ac_zb; they work with `antithetic_wrapper` below).  The AC-ZV
 and AC-ZVZB estimators (the local energy of d psi / d R, make_zv_term_via_jvp) are not provided.
+
+`evaluate_finite_difference_force` needs no derivative of psi and no restriction on the Hamiltonian: one launch displaces the
+walkers with every nuclear coordinate (dqmc_fd_displace), the engine evaluates log|psi| and E_loc at the 3 n_nuc displaced
+copies, and one launch forms the importance-weighted quotient (dqmc_fd_force).  The estimators that take `(e_loc, energy)`
+accept `energy` as a float or as a device tensor; the latter never waits for the host (`_centred`).
 """
 from __future__ import annotations
 
@@ -31,6 +36,17 @@ def _check_hamil(hamil, name):
     if hamil.pot is not None:
         raise NotImplementedError(f'{name}: Hamiltonians with an effective core potential or a pseudo-Hamiltonian are not '
                                   'supported (the ZVQ family rejects them; the bare force needs the non-local ECP gradient)')
+
+
+def _centred(eng, e_loc, energy):
+    """(e_loc [B] in the engine's dtype, energy as a float) for the estimators with a zero-bias term.  A float `energy` crosses
+    the C ABI by value.  A device tensor (what the observable monitors pass: the mean of e_loc) is subtracted from e_loc on the
+    device instead, in float64, so that nothing waits for the host; the kernel then sees energy 0.  In a float64 context the two
+    ways are bit-identical; in a float32 one the centred energies are rounded to float32 once."""
+    e_loc = eng._t(e_loc).reshape(-1)
+    if isinstance(energy, torch.Tensor):
+        return (e_loc.double() - energy.to(e_loc.device).double()).to(eng.dtype), 0.0
+    return e_loc, float(energy)
 
 
 def nuclear_force(R, phys_conf, nuclear_charges):
@@ -88,8 +104,7 @@ def _estimator(hamil, wf, est, *, takes_rng, needs_energy):
                 raise NotImplementedError(f'evaluate_hf_force_{est}: unsupported for this program ({eng.program.grad_unsupported})')
             grad_R = eng.log_psi_grad_coords(r, R, want_r=False)[3]
         if needs_energy:
-            e_loc = eng._t(e_loc).reshape(-1)
-            energy = float(energy)
+            e_loc, energy = _centred(eng, e_loc, energy)
         return eng.hf_force(est, r, R, grad_r=grad_r, grad_R=grad_R, e_loc=e_loc if needs_energy else None,
                             energy=energy if needs_energy else 0.0)
 
@@ -131,6 +146,45 @@ def evaluate_hf_force_ac_zvqzb(hamil, wf):
     return _estimator(hamil, wf, 'ac_zvqzb', takes_rng=False, needs_energy=True)
 
 
+def evaluate_finite_difference_force(hamil, wf, step_size):
+    """force.py evaluate_finite_difference_force: f(rng, params, phys_conf, e_loc, energy=None, return_parts=False) ->
+    [B, n_nuc, 3] float64, the one force estimator that needs no derivative of psi.  For every displacement d = (n0, j0) of the
+    D = 3 n_nuc nuclear coordinates, with the reference's signs (formulas at dqmc_fd_displace in include/dqmc.h):
+
+        R_d = R - h e_(n0, j0),   r_d[b, e, j0] = r[b, e, j0] + h w[b, n0, e],   w = softmax_n(-|R_n - r_be|)
+        F[b, n0, j0] = exp(2 (log|psi|(r_d, R_d) - log|psi|(r, R))) (E_loc(r_d, R_d) - e_loc[b]) / h
+
+    One launch forms all displaced copies (dqmc_fd_displace, w in float64), D value evaluations and D local-energy calls of the
+    engine follow -- `wf.engine(params, R_d)`, so ansatzes that fold the geometry get a context per displaced geometry, and
+    the same `rng` keys the ECP quadrature of every displaced call -- and one launch forms the quotient (dqmc_fd_force).
+    `energy` is accepted for uniformity and unused.  Hamiltonians with an ECP or a pseudo-Hamiltonian are evaluated as
+    `hamil.local_energy` evaluates them.  return_parts: (F, (r_d [D, B, N, 3], R_d [D, n_nuc, 3], log_d [D, B], e_d [D, B])).
+
+    The quotient divides the error of E_loc by h: with float32 local energies (relative error ~1e-5 after the refinement)
+    and h = 1e-3 the per-walker force carries an error of order 1e-2 |E_loc|.  A float64 context is what the estimator is
+    meant for."""
+    h = float(step_size)
+    n_nuc = hamil.n_nuc
+
+    def force(rng, params, phys_conf, e_loc, energy=None, return_parts=False):
+        r, R = _split(phys_conf)
+        eng = wf.engine(params, R)
+        r, Rt, B = eng._walkers(r, R)
+        r_d, R_d = eng.fd_displace(r, Rt, h)
+        log_0 = eng.wf_eval(r, Rt)[1]
+        log_d = torch.empty(3 * n_nuc, B, dtype=eng.dtype, device=eng.device)
+        e_d = torch.empty_like(log_d)
+        for d in range(3 * n_nuc):
+            eng_d = wf.engine(params, R_d[d])
+            log_d[d] = eng_d.wf_eval(r_d[d], R_d[d])[1]
+            e_d[d] = eng_d.local_energy(PhysicalConfiguration(R_d[d], r_d[d], None), rng=rng)[0]
+        F = eng.fd_force(log_d, log_0, e_d, eng._t(e_loc).reshape(-1), h)
+        return (F, (r_d, R_d, log_d, e_d)) if return_parts else F
+
+    force.takes_rng, force.needs_energy, force.estimator = True, True, 'finite_difference'
+    return force
+
+
 def antithetic_sampler(phys_conf, r_cut, R=None):
     """force.py antithetic_sampler: (phys_conf, mirrored) where every electron within r_cut of its nearest nucleus is reflected
     through that nucleus.  Works on [B, N, 3] device tensors (R from phys_conf, else `R`)."""
@@ -170,5 +224,6 @@ def antithetic_wrapper(evaluate_force, wf, r_cut):
 
 
 __all__ = ['nuclear_force', 'Q', 'make_grad_nuc_log_wf', 'evaluate_hf_force_bare', 'evaluate_hf_force_ac_zvq',
-           'evaluate_hf_force_ac_zvzbq', 'evaluate_hf_force_ac_zb', 'evaluate_hf_force_ac_zvqzb', 'antithetic_sampler',
+           'evaluate_hf_force_ac_zvzbq', 'evaluate_hf_force_ac_zb', 'evaluate_hf_force_ac_zvqzb', 'evaluate_finite_difference_force',
+           'antithetic_sampler',
            'antithetic_wrapper']

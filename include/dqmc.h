@@ -28,6 +28,8 @@
  *                          evaluate_hf_force_ac_zvq / _zvzbq / _zb), per walker
  *   dqmc_ecp_force      <- evaluate_hf_force_bare / _ac_zb for a Hamiltonian with a Gaussian-type ECP (force.py:286-299 with
  *                          hamil.pot.grad_nonloc_potential, ecp/gaussian_type_ecp.py:257-330, ecp/ecp_force_utils.py)
+ *   dqmc_oscillator_strength <- OscillatorStrengthMonitor.compute_observable, observable.py:556-605
+ *   dqmc_fd_displace / dqmc_fd_force <- the displacements and the quotient of evaluate_finite_difference_force, force.py:550-606
  *
  * Conventions: plain pointers and sizes only.  Unless marked "host", every pointer is a
  * DEVICE pointer.  Walker-major contiguous layouts: r[B][N][3], R[n_nuc][3].  `real` is
@@ -309,6 +311,48 @@ typedef struct dqmc_loss_terms {
  *             Row q of spin / spin_mask / spin_stats belongs to state states[q]. */
 int dqmc_loss_cotangents(dqmc_ctx* ctx, const dqmc_loss_terms* terms, double* c, double* k);
 
+/* ---- Observables of the training loop (reference observable.py, force.py evaluate_finite_difference_force) ----
+ * As the loss assembly: the calls run on the context's stream, copy nothing to the host and do not synchronise; every sum has
+ * a fixed order and there are no atomics, so identical calls give bit-identical results.  One molecule, one process. */
+
+/* Oscillator strengths between S electronic states (OscillatorStrengthMonitor, observable.py:556-605).
+ *   r: real[S][B][N][3], the walkers of every state;  psi_ratio: double[S][S][B] as dqmc_psi_ratio writes it;  e_loc: real[S][B].
+ *   os_mean, os_err: double[S][S];  cd_mean, cd_err: double[S][S][3].
+ * First launch, one workgroup per ordered pair (i, j), means and population standard deviations over b (the mean, then in a
+ * second pass the squared deviations from it):
+ *   d[j][b][c]     = -sum_n r[j][b][n][c]                       (formed on the fly, the electrons added in ascending order)
+ *   cd[i][j][b][c] = d[j][b][c] psi_ratio[i][j][b]   ->  cd_mean[i][j][c], cd_std[i][j][c]
+ *   E[i], std_E[i] = those of e_loc[i]                          (the workgroups (i, i))
+ * Second launch, one workgroup, IEEE double with every operation rounded on its own, as written:
+ *   err_E[i]   = std_E[i] / sqrt(B)
+ *   ex[i][j]   = E[j] - E[i]
+ *   ex_err     = sqrt(err_E[i]^2 + err_E[j]^2)
+ *   cd_err     = cd_std / sqrt(B)
+ *   rel        = cd_err / cd_mean
+ *   ds_vec[i][j][c] = cd_mean[i][j][c] cd_mean[j][i][c]
+ *   ds_err_vec = |ds_vec| sqrt(rel[i][j][c]^2 + rel[j][i][c]^2)
+ *   ds         = sum_c ds_vec
+ *   ds_err     = sqrt(sum_c ds_err_vec^2)
+ *   os_mean    = (2/3) ex ds
+ *   os_err     = (2/3) |os_mean| sqrt((ex_err / ex)^2 + (ds_err / ds)^2)
+ * The diagonal is not special-cased: os_mean[i][i] = 0 and os_err[i][i] = NaN, as in the reference.  1 <= S <= 32.  The context
+ * keeps the moments between the launches in a scratch of 2 S + 3 S^2 doubles, allocated by the first call (dqmc_debug_read -5). */
+int dqmc_oscillator_strength(dqmc_ctx* ctx, const void* r, const double* psi_ratio, const void* e_loc, int S, int B, double* os_mean,
+                             double* os_err, double* cd_mean, double* cd_err);
+
+/* The finite-difference force (force.py:550-606), per walker b, with the reference's signs.  D = 3 n_nuc displacements
+ * d = 3 n0 + j0 (nucleus n0, Cartesian component j0) of step h:
+ *   R_d = R - h e_(n0, j0)
+ *   w[b][n][e] = exp(-|R_n - r_be|) / sum_n' exp(-|R_n' - r_be|)          (double, whatever the context's dtype)
+ *   r_d[b][e][j0] = r[b][e][j0] + h w[b][n0][e]                            (the other components unchanged)
+ *   F[b][n0][j0] = exp(2 (log|psi|(r_d, R_d) - log|psi|(r, R))) (E_loc(r_d, R_d) - e_loc[b]) / h
+ * dqmc_fd_displace writes all D displaced copies in one launch: r_out real[D][B][N][3], R_out real[D][n_nuc][3] (each value
+ * computed in double and rounded once to real); they must not alias r and R.  Between the two calls the caller evaluates
+ * log|psi| (dqmc_wf_eval) and E_loc (dqmc_local_energy) at every (r_d, R_d).
+ * dqmc_fd_force: log_d, e_d real[D][B]; log_0, e_0 real[B]; F double[B][n_nuc][3], the quotient formed in double.  h != 0. */
+int dqmc_fd_displace(dqmc_ctx* ctx, const void* r, const void* R, int B, double h, void* r_out, void* R_out);
+int dqmc_fd_force(dqmc_ctx* ctx, const void* log_d, const void* log_0, const void* e_d, const void* e_0, int B, double h, double* F);
+
 /* psi for B walkers.  r: real[B][N][3], R: real[n_nuc][3]; out logpsi: real[B],
  * sign: int32[B] (values -1, 0, +1; bit-exact item of the parity contract). */
 int dqmc_wf_eval(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logpsi, int32_t* sign);
@@ -565,7 +609,8 @@ int dqmc_merge_energy_stats(const double* records_host, int n_ranks, double* out
 /* Debug / test access: copy activation buffer `buf` of the last evaluation (layout
  * real[B][rows][TP][width]) to host as double[].  n must equal B*rows*TP*width.
  * buf = -1: log|det| lanes double[B][K][TP]; buf = -2: det signs as double[B][K]; buf = -4: the psi-weighted
- * conditioning record of the Slater matrices, double[B] (Laplacian-mode evaluations). */
+ * conditioning record of the Slater matrices, double[B] (Laplacian-mode evaluations); buf = -5: the moments of the last
+ * dqmc_oscillator_strength call, double[2 S + 3 S^2] = E[S], std_E[S], cd_std[S][S][3] (needs no evaluation). */
 int dqmc_debug_read(dqmc_ctx* ctx, int buf, double* out_host, size_t n);
 /* Lanes (TP) used by the last evaluation. */
 int dqmc_debug_lanes(dqmc_ctx* ctx);
