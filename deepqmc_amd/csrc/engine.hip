@@ -287,6 +287,7 @@ struct Engine : dqmc_ctx {
   int attention_ncb = -1;      // 1: kernel instance for the exact number of key tiles, 0: the four-tile instance, -1: exact in float32 only (measured)
   int attention_split = -1;    // float64 contexts: eight-wave variant (a pair of waves per query row block) for Laplacian passes (1 / -1), 0: never
   int slogdet_mfma = 1;        // 1: where profitable (N > 16), 2: from N > 8 on, 0: never
+  int attention_reverse = 0;   // 1: the reverse pass runs through ATTENTION ops (engine_grad.inl: attention_refused), 0: it refuses them
   std::vector<char> compact;
   // two-layer row-wise MLPs run as ONE launch (kernel_linear.hip: CHAIN): mlp_child[k] = op index of the second layer
   // of the LINEAR op k, or -1; mlp_skip[k]: op k is such a second layer (executed with its parent)

@@ -7,9 +7,23 @@
   DevBuf<int32_t> g_tab;
   std::vector<int> g_tab_of;     // per op: {rows table offset, Sr, senders table offset, Ss} into g_tab (CONV, EDGE_SUM)
 
-  bool has_attention() const {
-    for (const auto& o : ops) if (o.kind == DQMC_OP_ATTENTION) return true;
+  // The one refusal of every entry point that needs the reverse pass: a program with an ATTENTION op is refused unless option
+  // "attention_reverse" is on, and whatever the option when an ATTENTION op has constant key / value rows (the nuclear tokens
+  // of the TransPsiformer are folded on the host from parameters and R: their adjoints have nowhere to go).
+  bool attention_refused() const {
+    for (const auto& o : ops)
+      if (o.kind == DQMC_OP_ATTENTION && (!attention_reverse || dqmc::AttentionOp(o).n_const() > 0)) return true;
     return false;
+  }
+  // what the reverse pass reads and writes of an op: op_io, which leaves ATTENTION out because the forward planners that
+  // call it never reach one
+  static void rev_op_io(const dqmc_op& op, std::vector<int>& rd, std::vector<int>& wr) {
+    op_io(op, rd, wr);
+    if (op.kind == DQMC_OP_ATTENTION) {
+      const dqmc::AttentionOp a(op);
+      for (int q = 0; q < 3; ++q) rd.push_back(a.buf(q));
+      wr.push_back(a.dst());
+    }
   }
   size_t grad_zrow() const {     // largest nrows * ldw of a LINEAR op
     size_t z = 4;

@@ -26,7 +26,7 @@
     std::vector<char> live_buf(bufs.size(), 0);
     std::vector<int> rd, wr;
     for (size_t k = (size_t)orb_op + 1; k-- > 0;) {
-      op_io(ops[k], rd, wr);
+      rev_op_io(ops[k], rd, wr);
       bool live = (int)k == orb_op;
       for (int b : wr) live = live || live_buf[b];
       if (!live) continue;
@@ -134,7 +134,7 @@
   }
 
   int pretrain_loss_grad(const void* r, const void* R, int B, double n_total, double* grad, double* per_sample_loss) override {
-    if (has_attention()) return fail(DQMC_E_UNSUPPORTED, "pretrain_loss_grad: no reverse pass for ATTENTION ops");
+    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "pretrain_loss_grad: no reverse pass for ATTENTION ops");
     if (!pt_n_conf) return fail(DQMC_E_ARG, "pretrain_loss_grad: no target set (dqmc_set_pretrain_target)");
     if (!(n_total >= 1)) return fail(DQMC_E_ARG, "pretrain_loss_grad: n_total must be at least 1");
     HIP_TRY(hipMemsetAsync(grad, 0, sizeof(double) * n_weights, st));

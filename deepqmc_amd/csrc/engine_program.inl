@@ -326,6 +326,7 @@
     if (s == "attention_mfma") { attention_mfma = value; return DQMC_OK; }
     if (s == "attention_ncb") { attention_ncb = value; return DQMC_OK; }
     if (s == "attention_split") { attention_split = value; return DQMC_OK; }
+    if (s == "attention_reverse") { if (value != 0 && value != 1) return fail(DQMC_E_ARG, "attention_reverse must be 0 or 1"); attention_reverse = value; return DQMC_OK; }
     if (s == "ws_budget_mb") { if (value < 1) return fail(DQMC_E_ARG, "ws_budget_mb must be positive"); ws_budget = (size_t)value << 20; return DQMC_OK; }
     if (s == "slogdet_mfma") { slogdet_mfma = value; return DQMC_OK; }
     if (s == "lane_compact") { lane_compact = value != 0; analyse_lanes(); last_B = 0; return DQMC_OK; }

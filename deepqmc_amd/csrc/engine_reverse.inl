@@ -95,7 +95,7 @@
   int reverse_pass(const real* r, const real* R, int B, const RevReq& q) {
     const std::string name = rev_name(q.mode);
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
-    if (has_attention()) return fail(DQMC_E_UNSUPPORTED, name + ": no reverse pass for ATTENTION ops");
+    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, name + ": no reverse pass for ATTENTION ops");
     if (q.mode != Rev::Orbs && N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 64 electrons");   // (Orbs forms no inverse)
     { const int rc = grad_tables(); if (rc) return rc; }
     if (q.mode == Rev::Orbs) { const int rc = orb_tables(); if (rc) return rc; }
@@ -243,6 +243,19 @@
           const dqmc::EdgeSumOp& e = v.edge_sum;
           dqmc::launch_edge_rows_bwd<real>(st, A(e.edge()), bufs[e.edge()].rows, bufs[e.edge()].width, nullptr, 1, 4, A(e.dst()), bufs[e.dst()].width,
                                            e.dst_col0(), gt + t[0], t[1], e.width(), B, N, e.scale());
+          break;
+        }
+        case DQMC_OP_ATTENTION: {    // no parameters: the same in every mode (dq, dk, dv are added into the adjoint buffers)
+          const dqmc::AttentionOp& at = v.att;
+          for (int x = 0; x < 4; ++x)
+            for (int y = x + 1; y < 4; ++y)
+              if (at.buf(x) == at.buf(y)) return fail(DQMC_E_UNSUPPORTED, std::string(rev_name(q.mode)) + ": ATTENTION op with shared q / k / v / dst buffers");
+          t_begin("attention_bwd", 2.0 * B * at.heads() * (double)N * N * at.head_dim() * 5.0);
+          const int rc2 = dqmc::launch_attention_bwd<real>(st, bptr(at.q()), bptr(at.k()), bptr(at.v()), A(at.dst()), A(at.q()), A(at.k()), A(at.v()),
+                                                           bufs[at.q()].width, at.heads(), at.head_dim(), B, N);
+          t_end();
+          if (rc2 == -1) return fail(DQMC_E_UNSUPPORTED, std::string(rev_name(q.mode)) + ": attention backward tile set (N, head_dim) exceeds the LDS or the register tile");
+          if (rc2) return fail(DQMC_E_HIP, "attention backward launch failed");
           break;
         }
         case DQMC_OP_CONST: {

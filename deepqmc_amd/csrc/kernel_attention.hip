@@ -275,4 +275,6 @@ template int launch_attention<float>(hipStream_t, const float*, const float*, co
 template int launch_attention<double>(hipStream_t, const double*, const double*, const double*, double*, int, int,
                                       int, int, LaneInfo, int, const double*, const double*);
 
+#include "kernels_attention_bwd.inl"
+
 }  // namespace dqmc

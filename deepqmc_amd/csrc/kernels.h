@@ -183,6 +183,12 @@ template <typename real>
 int launch_attention(hipStream_t st, const real* q, const real* k, const real* v, real* out, int width, int H, int hd,
                      int B, LaneInfo li, int n_const, const real* k_const, const real* v_const);
 template <typename real> size_t attention_lds_bytes(int N, int hd, int n_const);
+// kernels_attention_bwd.inl: the reverse pass's backward of the op (TP = 1, no constant keys); dq, dk, dv are added into.
+// Returns 0, or -1 if the shape is not supported (LDS tile set, N * hd per thread), -2 on a HIP error
+template <typename real>
+int launch_attention_bwd(hipStream_t st, const real* q, const real* k, const real* v, const real* dout, real* dq, real* dk, real* dv,
+                         int width, int H, int hd, int B, int N);
+template <typename real> size_t attention_bwd_lds_bytes(int N, int hd);
 
 // ---- kernel_attention_mfma.hip: contractions on MFMA, float32 and float64 (head_dim % 16 == 0, <= 64 queries / keys) ----
 template <typename real> size_t attention_mfma_lds_bytes(int N, int hd, int n_const);

@@ -558,7 +558,8 @@ class Engine:
     def log_psi_grad_coords(self, r, R=None, want_r=True, want_R=True):
         """d log|psi(r_b)| / d r and d log|psi(r_b)| / d R per walker from the reverse pass (dqmc_log_psi_grad_coords).
         Returns (sign, logpsi, grad_r [B, N, 3] or None, grad_R [B, n_nuc, 3] or None) in the engine's dtype on its device.
-        Walkers with sign 0 or a non-finite log|psi| get zero rows.  Programs with attention ops raise DqmcError (-4)."""
+        Walkers with sign 0 or a non-finite log|psi| get zero rows.  Programs with attention ops raise DqmcError (-4) unless
+        option 'attention_reverse' is set to 1 (NeuralNetworkWaveFunction(..., attention_reverse=True))."""
         if not (want_r or want_R):
             raise ValueError('log_psi_grad_coords: want_r and want_R are both False')
         r, R, B = self._walkers(r, R)
@@ -593,7 +594,7 @@ class Engine:
         same vertices.  rows: 'own' keeps, for each non-local nucleus, only its own row of the ratio gradient (what the
         reference computes); 'all' keeps every row, the full dV_nl/dR.  return_parts: (force, parts) with parts [2, B, n_nuc, 3]
         = (F_nuc - dV_loc/dR, -G).  Walkers with sign 0 or a non-finite log|psi| get NaN rows.  Attention programs raise
-        DqmcError (-4)."""
+        DqmcError (-4) unless option 'attention_reverse' is set to 1."""
         if estimator not in ('bare', 'ac_zb'):
             raise ValueError(f"unknown ECP force estimator {estimator!r}; one of ('bare', 'ac_zb')")
         if rows not in ('own', 'all'):
@@ -658,7 +659,8 @@ class Engine:
     def orbitals_vjp(self, r, cot, R=None, want_orbitals=True):
         """sum_{b,k,i,mu} cot[b,k,i,mu] d A[b,k,i,mu] / d w over the flat weight buffer (dqmc_orbitals_vjp).  cot: [B, K, N, N].
         Returns (orbitals [B, K, N, N] or None, grad_flat float64 [n_weights]); map grad_flat onto the parameter tree with
-        `self.program.unflatten_grad`.  Programs with attention ops raise DqmcError (-4)."""
+        `self.program.unflatten_grad`.  Programs with attention ops raise DqmcError (-4) unless
+        option 'attention_reverse' is set to 1 (NeuralNetworkWaveFunction(..., attention_reverse=True))."""
         r, R, B = self._orb_check(r, R)
         shape = (B, self.spec.n_determinants, self.N, self.N)
         c = self._arg('cot', self._t(cot), self.dtype, shape)

@@ -30,13 +30,19 @@ from .types import PhysicalConfiguration, Psi
 
 class NeuralNetworkWaveFunction:
     def __init__(self, hamil: MolecularHamiltonian, spec='paulinet', *, dtype=torch.float32, device='cuda',
-                 norm_eps=None, lib=None):
+                 norm_eps=None, lib=None, attention_reverse=False):
+        """`attention_reverse`: opt in to the reverse pass through attention ops (library option "attention_reverse"), which
+        the parameter- and coordinate-gradient entry points below, the force and ECP-force estimators, pretraining,
+        `create_loss_fn` and the optimisers of `fit_wf` need for a Psiformer.  Off (the default) those calls fail with
+        `dqmc error -4` for an attention ansatz.  The TransPsiformer stays unsupported either way (its nuclear tokens are
+        folded on the host)."""
         self.hamil = hamil
         if spec == 'transpsiformer':
             self.spec: AnsatzSpec = ANSATZES[spec](hamil.mol.charges)      # atom types of the nuclei embedding
         else:
             self.spec = ANSATZES[spec]() if isinstance(spec, str) else spec
         self.dtype, self.device, self.norm_eps, self._lib = dtype, device, norm_eps, lib
+        self.attention_reverse = bool(attention_reverse)
         self._engines = []       # [(params tree, Engine)], most recently used last (one per electronic state)
         self.max_engines = 8
         self._evictions = 0
@@ -89,6 +95,8 @@ class NeuralNetworkWaveFunction:
             R0 = None if gkey is None else np.frombuffer(gkey, np.float64).reshape(self.hamil.n_nuc, 3)
             eng = Engine(self.spec, self.hamil, params, dtype=self.dtype, device=self.device,
                          norm_eps=self.norm_eps, lib=self._lib, R=R0)
+            if self.attention_reverse:      # before any set_kfac_map or graph capture (setting an option bumps the graph epoch)
+                eng.set_option('attention_reverse', 1)
         self._engines.append((params, gkey, eng))
         return eng
 
@@ -190,11 +198,14 @@ class NeuralNetworkWaveFunction:
     def log_psi_vjp(self, params, phys_conf, cotangent=None):
         """jax.vjp of vmap(ansatz.apply)(params, r).log (loss/loss_function.py:59-75) with one cotangent per walker:
         returns (Psi(sign, log), grad tree {module: {leaf: ndarray}}) with grad = sum_b cotangent[b] d log|psi(r_b)| / d params.
-        cotangent None = all ones.  Programs whose packing is not a copy of the parameters (nuclear tokens) and programs
-        with attention ops are not supported."""
+        cotangent None = all ones.  Programs with attention ops (Psiformer) are supported when the wave function was made
+        with `attention_reverse=True`; programs whose packing is not a copy of the parameters (nuclear tokens:
+        TransPsiformer) are not supported."""
         r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
         R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
         eng = self.engine(params, R)
+        if self.attention_reverse and eng.program.grad_unsupported:
+            raise NotImplementedError(f'log_psi_vjp: unsupported for this program ({eng.program.grad_unsupported})')
         sign, log, g = eng.log_psi_vjp(r, cotangent, R)
         return Psi(sign, log), eng.program.unflatten_grad(g)
 

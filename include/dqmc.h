@@ -375,7 +375,9 @@ int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logp
  * linear layers: exact zeros); mapping the flat gradient back onto the parameters is the caller's (Program.unflatten_grad).
  * Per walker chunk ("ws_budget_mb", adjoint buffers included) a value pass op by op, then the ops in reverse; the
  * walker sums run in a fixed order, so two identical calls give bit-identical results.
- * DQMC_E_UNSUPPORTED for programs with ATTENTION ops (Psiformer, TransPsiformer). */
+ * DQMC_E_UNSUPPORTED for programs with ATTENTION ops (Psiformer, TransPsiformer) unless option "attention_reverse" is 1
+ * (dqmc_set_option); with it, only ATTENTION ops with constant key / value rows (n_const > 0, the TransPsiformer's nuclear
+ * tokens) stay refused.  The same gate holds for every entry point that runs this reverse pass. */
 int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot,
                      double* grad, void* logpsi, int32_t* sign);
 
@@ -386,7 +388,8 @@ int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const v
  * Same conventions as dqmc_log_psi_vjp: walkers with sign 0 or a non-finite log|psi| get an all-zero row; constant and
  * padding entries get what their position accumulates (padding of linear layers: exact zeros); walker chunks per
  * "ws_budget_mb" (dqmc_last_chunks); no atomics, so identical calls are bit-identical, and a chunked call equals an
- * unchunked one bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as dqmc_log_psi_vjp. */
+ * unchunked one bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs without
+ * option "attention_reverse" and for N > 64, as dqmc_log_psi_vjp. */
 int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, void* jac, size_t ld_jac,
                           void* logpsi, int32_t* sign);
 
@@ -412,7 +415,8 @@ int dqmc_log_psi_jacobian(dqmc_ctx* ctx, const void* r, const void* R, int B, vo
  *     (the values dqmc_log_psi_jacobian writes into those columns; invalid walkers get zeros);  logpsi / sign optional.
  * One value pass and one reverse pass (unit cotangent) per walker chunk ("ws_budget_mb", dqmc_last_chunks); the cotangent
  * weights the walker sums of grad.  No atomics: identical calls are bit-identical; with cot == NULL grad equals
- * dqmc_log_psi_vjp's bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as dqmc_log_psi_vjp. */
+ * dqmc_log_psi_vjp's bit for bit.  DQMC_E_UNSUPPORTED for ATTENTION programs without
+ * option "attention_reverse" and for N > 64, as dqmc_log_psi_vjp. */
 int dqmc_kfac_layout(dqmc_ctx* ctx, int* n_linear, size_t* n_factor_doubles, size_t* n_rest);
 int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot, double* grad, double* factors,
                       void* rest, void* logpsi, int32_t* sign);
@@ -423,7 +427,8 @@ int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const 
  * no weight gradients: the adjoints of the feature, envelope and cusp inputs are carried into the coordinates.  Sums over
  * the electrons and nuclei run in a fixed order (no atomics): identical calls are bit-identical, and a chunked call equals
  * an unchunked one bit for bit.  Walkers with sign 0 or a non-finite log|psi| get zero rows.  By translation invariance
- * sum_a grad_R[b][a] = -sum_i grad_r[b][i].  DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as dqmc_log_psi_vjp. */
+ * sum_a grad_R[b][a] = -sum_i grad_r[b][i].  DQMC_E_UNSUPPORTED for ATTENTION programs without
+ * option "attention_reverse" and for N > 64, as dqmc_log_psi_vjp. */
 int dqmc_log_psi_grad_coords(dqmc_ctx* ctx, const void* r, const void* R, int B, void* grad_r, void* grad_R,
                              void* logpsi, int32_t* sign);
 
@@ -474,9 +479,9 @@ int dqmc_hf_force(dqmc_ctx* ctx, int estimator, const void* r, const void* R, in
  *          parts[1] = -G (BARE: force = parts[0] + parts[1]).
  *   The rotation is the one set by the preceding dqmc_ecp_rotation: the same seed or angles give the vertices of the
  *   dqmc_local_energy call.
- * DQMC_E_ARG when no Gaussian ECP is set or a pseudo-Hamiltonian is; DQMC_E_UNSUPPORTED for ATTENTION programs and N > 64, as
- * dqmc_log_psi_grad_coords.  An ECP with local terms only is valid: parts[1] is zero and no reverse pass runs unless AC_ZB
- * needs gR_0.  A walker with sign 0 or a non-finite log|psi| gets NaN rows in parts[1] and force; a quadrature configuration
+ * DQMC_E_ARG when no Gaussian ECP is set or a pseudo-Hamiltonian is; DQMC_E_UNSUPPORTED for ATTENTION programs without option
+ * "attention_reverse" and for N > 64, as dqmc_log_psi_grad_coords.  An ECP with local terms only is valid: parts[1] is zero
+ * and no reverse pass runs unless AC_ZB needs gR_0.  A walker with sign 0 or a non-finite log|psi| gets NaN rows in parts[1] and force; a quadrature configuration
  * with sign 0 or a non-finite log|psi| contributes ratio 0.  Fixed-order sums, no atomics: identical calls are bit-identical,
  * and a chunked call equals an unchunked one bit for bit.  dqmc_last_chunks[0] afterwards: the walker chunks of the call. */
 int dqmc_ecp_force(dqmc_ctx* ctx, int estimator, int all_rows, const void* r, const void* R, int B, const void* e_loc,
@@ -506,7 +511,7 @@ int dqmc_ecp_force(dqmc_ctx* ctx, int estimator, int all_rows, const void* r, co
  *   determinants, the CI sum and every op from which no path leads to the matrices (the Jastrow factor) are skipped and
  *   their entries are exact zeros.  No walker is left out (orbitals are finite wherever the walker is).  Fixed-order
  *   sums: identical calls are bit-identical, chunked and unchunked calls differ in the last bits.
- *   DQMC_E_UNSUPPORTED for ATTENTION programs, as dqmc_log_psi_vjp; any number of electrons.
+ *   DQMC_E_UNSUPPORTED for ATTENTION programs without option "attention_reverse", as dqmc_log_psi_vjp; any number of electrons.
  * dqmc_pretrain_loss_grad: value pass -> target -> loss and its cotangent -> reverse pass, all on the device:
  *   per_sample_loss[b] (device double[B]) = mean_{k, i < n_up, mu} (A - T)^2 + mean_{k, i >= n_up, mu} (A - T)^2, with
  *   T[k] = target configuration k mod n_conf, its [:n_up, :n_up] and [n_up:, n_up:] blocks, zeros elsewhere;
