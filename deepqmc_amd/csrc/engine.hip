@@ -289,6 +289,7 @@ struct Engine : dqmc_ctx {
   int slogdet_mfma = 1;        // 1: where profitable (N > 16), 2: from N > 8 on, 0: never
   int attention_reverse = 0;   // 1: the reverse pass runs through ATTENTION ops (engine_grad.inl: attention_refused), 0: it refuses them
   std::vector<char> compact;
+  std::vector<int> pad_end;    // per op: the CONV / EDGE_SUM op that also zeroes its destination's columns up to pad_end (0: none)
   // two-layer row-wise MLPs run as ONE launch (kernel_linear.hip: CHAIN): mlp_child[k] = op index of the second layer
   // of the LINEAR op k, or -1; mlp_skip[k]: op k is such a second layer (executed with its parent)
   std::vector<int> mlp_child;
@@ -486,6 +487,8 @@ struct Engine : dqmc_ctx {
       return fail(DQMC_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the determinant kernels of more than 44 electrons");
     analyse_lanes();
     analyse_chains();
+    rc = analyse_pad_columns();
+    if (rc) return rc;
     analyse_streams();
     if (sizeof(real) == 4) spec_k = dqmc::find_spec_kernel(program_hash());
     rc = set_weights(w, nw);

@@ -222,6 +222,11 @@
       if (ops[k].kind == DQMC_OP_FEAT_EE)
         for (int r = 0; r < e.n_rows(); ++r) if (h_itable[e.table() + 2 * r + 1] < 0) return DQMC_OK;
     }
+    // An aggregate buffer with padding columns (engine_program.inl: analyse_pad_columns): a linear unit of the LDS-resident
+    // kernel reads them like the staged kernels do, its CONV / EDGE_SUM code writes only the ops' own columns, and what the
+    // previous kernel left in that LDS is not zero.  Such programs (odd two_particle_dim) get no plan: wf_eval and the
+    // Metropolis sub-steps both take the one-launch-per-op path, where the padding is zeroed.
+    for (int k = 0; k < n_f; ++k) if (pad_end[k]) return DQMC_OK;
     fused_n_ops = n_f;
     if (fused_sched_mode == 3) {
       // largest per-level budget (= fewest levels) whose packed 4-walker tile leaves room for 4 workgroups per CU

@@ -347,6 +347,8 @@
           t_begin("graph", 0, so);
           dqmc::launch_conv<real>(so, bptr(v.conv.edge()), eb.rows, eb.width, bptr(v.conv.node()), nb.rows, nb.width, bptr(v.conv.dst()), bufs[v.conv.dst()].width,
                                   v.conv.dst_col0(), d_it + v.conv.table(), v.conv.S(), v.conv.width(), B, li, li.TP > 1 && compact[v.conv.edge()]);
+          if (pad_end[opi])
+            dqmc::launch_zero_cols<real>(so, bptr(v.conv.dst()), (long)B * li.N * li.TP, bufs[v.conv.dst()].width, v.conv.dst_col0() + v.conv.width(), pad_end[opi]);
           t_end();
           break;
         }
@@ -355,6 +357,8 @@
           t_begin("graph", 0, so);
           dqmc::launch_edge_sum<real>(so, bptr(e.edge()), bufs[e.edge()].rows, bufs[e.edge()].width, bptr(e.dst()), bufs[e.dst()].width, e.dst_col0(),
                                       d_it + e.table(), e.S(), e.width(), e.scale(), B, li, li.TP > 1 && compact[e.edge()]);
+          if (pad_end[opi])
+            dqmc::launch_zero_cols<real>(so, bptr(e.dst()), (long)B * li.N * li.TP, bufs[e.dst()].width, e.dst_col0() + e.width(), pad_end[opi]);
           t_end();
           break;
         }
@@ -384,6 +388,10 @@
                                                     attention_ncb < 0 ? (sizeof(real) == 4 ? 1 : 0) : attention_ncb);
           else
             rc2 = dqmc::launch_attention<real>(st, q, k, vv, out, ld, at.heads(), hd, B, li, nc, ck, cv);
+          // the kernels write the heads' own columns: the padding past H * hd (an embedding_dim that is no multiple of 4) is
+          // read by the output projection against zero weight rows, like the aggregate padding of CONV / EDGE_SUM above
+          if (!rc2 && at.heads() * hd < bufs[at.dst()].width)
+            dqmc::launch_zero_cols<real>(st, out, (long)B * li.N * li.TP, bufs[at.dst()].width, at.heads() * hd, bufs[at.dst()].width);
           t_end();
           if (rc2) return fail(DQMC_E_HIP, "attention launch failed");
           break;

@@ -174,6 +174,33 @@
     }
   }
 
+  // The aggregate buffer of a layer (width padded to 4) is written by its CONV / EDGE_SUM ops, `width` columns each; the LINEAR
+  // op that consumes it reads whole groups of 4 columns against zero weight rows.  Where the ops do not fill the padded width
+  // (an odd two_particle_dim: 2 x 5 columns of 12) nobody wrote the remaining columns, and a NaN the workspace happened to hold
+  // there became NaN x 0 in every output of the layer.  The op that writes the highest columns zeroes them, too.  That is
+  // all the padding only if the ops of a destination tile its columns from 0 upwards without a gap, which is what the program
+  // compiler emits; any other layout (say, every op aligned to 4 columns) is refused here instead of read unwritten.
+  int analyse_pad_columns() {
+    pad_end.assign(ops.size(), 0);
+    std::vector<std::vector<int>> writers(bufs.size());
+    for (size_t k = 0; k < ops.size(); ++k)
+      if (ops[k].kind == DQMC_OP_CONV || ops[k].kind == DQMC_OP_EDGE_SUM) writers[dqmc::EdgeOp(ops[k]).dst()].push_back((int)k);
+    for (size_t b = 0; b < bufs.size(); ++b) {
+      std::vector<int>& w = writers[b];
+      if (w.empty()) continue;
+      std::stable_sort(w.begin(), w.end(), [&](int x, int y) { return dqmc::EdgeOp(ops[x]).dst_col0() < dqmc::EdgeOp(ops[y]).dst_col0(); });
+      int end = 0;
+      for (int k : w) {
+        const dqmc::EdgeOp c(ops[k]);
+        if (c.dst_col0() != end)
+          return fail(DQMC_E_UNSUPPORTED, "CONV / EDGE_SUM ops of buffer " + std::to_string(b) + " leave a gap or overlap at column " + std::to_string(end));
+        end += c.width();
+      }
+      if (end < bufs[b].width) pad_end[w.back()] = bufs[b].width;
+    }
+    return DQMC_OK;
+  }
+
   // Which buffers can carry pair-compact lanes: outputs of FEAT_EE and of row-wise LINEAR ops on them (all
   // pieces compact, none broadcast; residual compact with the same row pairs).  Consumers that understand the
   // compact layout: LINEAR, CONV (edge operand), EDGE_SUM.  Anything else turns the optimisation off.

@@ -204,6 +204,19 @@ __global__ void __launch_bounds__(256) k_attention(const real* __restrict__ q, c
             }
           }
         }
+        // the hd % TD features past the last whole group: one (query, feature) per thread (no trip when TD divides hd)
+        const int dr = ntd * TD, nr = hd - dr;
+        for (int e = tid; e < N * nr; e += nthr) {
+          const int i = e / nr, d = dr + (e - i * nr);
+          real o = 0, ol = 0;
+          for (int j = 0; j < M; ++j) {
+            const real dp = dP[i * M + j], vcd = vc[j * S + d];
+            o += dp * v0[j * S + d] + P[i * M + j] * vcd;
+            ol += dp * vcd;
+          }
+          OL[i * S + d] += 2 * ol;
+          out[(qrow0 + (long)i * TP + t) * width + col0 + d] = o;
+        }
       }
     } else {
       // L_P = A1 + P*(L_S - rowsum(P*L_S) - A2);  out_L = L_P v0 + P v_L + 2 sum_c dP_c v_c

@@ -29,6 +29,8 @@ void launch_conv(hipStream_t st, const real* we, int we_rows, int we_width, cons
 template <typename real>
 void launch_edge_sum(hipStream_t st, const real* e, int e_rows, int e_width, real* out, int out_width, int col0,
                      const int32_t* tab, int S, int W, double scale, int B, LaneInfo li, int compact);
+template <typename real>
+void launch_zero_cols(hipStream_t st, real* x, long rows, int width, int c0, int c1);     // x[rows][width], columns [c0, c1) = 0
 
 // ---- kernel_linear.hip ----
 // One concat piece of the A operand: logical row (b, rr, t) reads

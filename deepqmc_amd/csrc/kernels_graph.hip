@@ -253,10 +253,27 @@ __global__ void __launch_bounds__(256) k_edge_sum(const real* __restrict__ e, in
   o[0] = acc * scale;
 }
 
+// Columns [c0, c1) of every row of x[rows][width] = 0: the padding past the last aggregate feature, which the next LINEAR op
+// reads against zero weight rows (engine_program.inl: analyse_pad_columns).
+template <typename real>
+__global__ void __launch_bounds__(256) k_zero_cols(real* __restrict__ x, long rows, int width, int c0, int c1) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int nc = c1 - c0;
+  if (idx >= rows * nc) return;
+  const long row = idx / nc;
+  x[row * width + c0 + (int)(idx - row * nc)] = (real)0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 
 static inline unsigned nblk(long total) { return (unsigned)((total + 255) / 256); }
+
+template <typename real>
+void launch_zero_cols(hipStream_t st, real* x, long rows, int width, int c0, int c1) {
+  if (rows <= 0 || c1 <= c0) return;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_zero_cols<real>), dim3(nblk(rows * (c1 - c0))), dim3(256), 0, st, x, rows, width, c0, c1);
+}
 
 template <typename real>
 void launch_feat_en(hipStream_t st, const real* r, const real* R, real* x, int B, int n_nuc, int n_up, int width,
@@ -334,7 +351,8 @@ void launch_edge_sum(hipStream_t st, const real* e, int e_rows, int e_width, rea
   template void launch_conv<real>(hipStream_t, const real*, int, int, const real*, int, int, real*, int, int,        \
                                   const int32_t*, int, int, int, LaneInfo, int);                                     \
   template void launch_edge_sum<real>(hipStream_t, const real*, int, int, real*, int, int, const int32_t*, int, int, \
-                                      double, int, LaneInfo, int);
+                                      double, int, LaneInfo, int);                                                  \
+  template void launch_zero_cols<real>(hipStream_t, real*, long, int, int, int);
 DQMC_INST(float)
 DQMC_INST(double)
 #undef DQMC_INST

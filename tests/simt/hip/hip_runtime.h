@@ -42,11 +42,13 @@ inline const char* hipGetErrorString(hipError_t) { return "simt-emu"; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 // allocation bookkeeping for the tests (simt_runtime.cpp): blocks alive, blocks ever allocated, and a size above which
-// hipMalloc fails (0: no limit)
-extern "C" long long simt_live_allocs, simt_total_allocs, simt_alloc_limit;
+// hipMalloc fails (0: no limit); simt_alloc_fill: the byte every new block is filled with (0 by default; 0xFF makes every
+// float and double of fresh device memory a NaN, as stale memory of a real device can be)
+extern "C" long long simt_live_allocs, simt_total_allocs, simt_alloc_limit, simt_alloc_fill;
 inline hipError_t hipMalloc(void** p, size_t n) {
   *p = (simt_alloc_limit > 0 && n > (size_t)simt_alloc_limit) ? nullptr : calloc(n ? n : 1, 1);
   if (!*p) return 2;
+  if (simt_alloc_fill) memset(*p, (int)simt_alloc_fill, n ? n : 1);
   ++simt_live_allocs; ++simt_total_allocs;
   return hipSuccess;
 }

@@ -11,7 +11,7 @@
 #include <vector>
 
 dim3 threadIdx, blockIdx, blockDim, gridDim;
-extern "C" { long long simt_live_allocs = 0, simt_total_allocs = 0, simt_alloc_limit = 0; }
+extern "C" { long long simt_live_allocs = 0, simt_total_allocs = 0, simt_alloc_limit = 0, simt_alloc_fill = 0; }
 
 namespace simt {
 namespace {
