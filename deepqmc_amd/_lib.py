@@ -30,6 +30,20 @@ class DqmcKfacMap(ctypes.Structure):
                 ('diag_col', POINTER(c_int64))]
 
 
+class DqmcNucLinear(ctypes.Structure):
+    """dqmc_nuc_linear of include/dqmc.h."""
+    _fields_ = [('w', c_int64), ('b', c_int64), ('n_in', c_int32), ('n_out', c_int32), ('act', c_int32), ('reserved', c_int32)]
+
+
+class DqmcNucStream(ctypes.Structure):
+    """dqmc_nuc_stream of include/dqmc.h."""
+    _fields_ = [('n_nuc', c_int32), ('n_layers', c_int32), ('heads', c_int32), ('dim', c_int32), ('n_det', c_int32), ('n_env', c_int32),
+                ('n_edge_lin', c_int32), ('n_embed_lin', c_int32), ('n_mlp_lin', c_int32), ('n_lin', c_int32),
+                ('lin', POINTER(DqmcNucLinear)), ('zbias_up', c_int64), ('zbias_down', c_int64), ('nuc_types', POINTER(c_int32)),
+                ('R', POINTER(c_double)), ('n_derived', c_int64), ('sc_row', POINTER(c_int64)), ('sc_col', POINTER(c_int32)),
+                ('theta', POINTER(c_double))]
+
+
 # every symbol include/dqmc.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ('dqmc_create', c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(DqmcSystem), POINTER(c_double),
@@ -39,6 +53,7 @@ SIGNATURES = [
     ('dqmc_last_error', c_char_p, []),
     ('dqmc_set_weights', c_int, [c_void_p, POINTER(c_double), c_size_t]),
     ('dqmc_set_param_map', c_int, [c_void_p, POINTER(c_int32), c_size_t, c_size_t]),
+    ('dqmc_set_nuclear_stream', c_int, [c_void_p, POINTER(DqmcNucStream)]),
     ('dqmc_weights_from_params', c_int, [c_void_p, c_void_p]),
     ('dqmc_grad_to_params', c_int, [c_void_p, c_void_p, c_void_p]),
     ('dqmc_adam_step', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_double, c_double, c_double, c_double,

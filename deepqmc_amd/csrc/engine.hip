@@ -154,6 +154,7 @@ struct dqmc_ctx {
   virtual int orbitals_vjp(const void* r, const void* R, int B, const void* cot, double* grad, void* orb) = 0;
   virtual int pretrain_loss_grad(const void* r, const void* R, int B, double n_total, double* grad, double* per_sample_loss) = 0;
   virtual int set_param_map(const int32_t* src, size_t n, size_t n_params) = 0;
+  virtual int set_nuclear_stream(const dqmc_nuc_stream* d) = 0;
   virtual int weights_from_params(const double* theta) = 0;
   virtual int load_weights_device(const double* w64) = 0;
   virtual int grad_to_params(const double* grad_w, double* grad_theta) = 0;
@@ -511,6 +512,7 @@ struct Engine : dqmc_ctx {
 #include "engine_ecp_force.inl"
 #include "engine_pretrain.inl"
 #include "engine_optim.inl"
+#include "engine_nuc.inl"
 #include "engine_kfacopt.inl"
 #include "engine_loss.inl"
 #include "engine_observable.inl"
@@ -650,6 +652,11 @@ int dqmc_set_param_map(dqmc_ctx* ctx, const int32_t* src_host, size_t n_weights,
   if (!ctx || !src_host) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->set_param_map(src_host, n_weights, n_params);
+}
+int dqmc_set_nuclear_stream(dqmc_ctx* ctx, const dqmc_nuc_stream* desc_host) {
+  if (!ctx || !desc_host) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->set_nuclear_stream(desc_host);
 }
 int dqmc_weights_from_params(dqmc_ctx* ctx, const double* theta) {
   if (!ctx || !theta) return fail(DQMC_E_ARG, "null argument");

@@ -40,7 +40,7 @@
       HIP_TRY(hipGetLastError());
       return DQMC_OK;
     }
-    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "ecp_force: no reverse pass for ATTENTION ops");
+    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "ecp_force: " + attention_refusal_text(true));
     if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, "ecp_force: more than 64 electrons");
     { const int rc = coord_tables(); if (rc) return rc; }
     const size_t per_walker = (size_t)n_nl * N * 12;

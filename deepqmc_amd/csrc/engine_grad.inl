@@ -10,10 +10,32 @@
   // The one refusal of every entry point that needs the reverse pass: a program with an ATTENTION op is refused unless option
   // "attention_reverse" is on, and whatever the option when an ATTENTION op has constant key / value rows (the nuclear tokens
   // of the TransPsiformer are folded on the host from parameters and R: their adjoints have nowhere to go).
-  bool attention_refused() const {
+  // With option "nuclear_reverse" and a registered nuclear stream (engine_nuc.inl) the constant rows are admitted by the calls
+  // that sum their partials over the walkers (per_walker false: the Vjp and Orbs modes).  Every other mode would need one nuclear
+  // backward per walker and keeps refusing.  0: runs, 1: no reverse pass for ATTENTION ops, 2: nuclear tokens, per-walker mode.
+  int attention_refusal(bool per_walker) const {
     for (const auto& o : ops)
-      if (o.kind == DQMC_OP_ATTENTION && (!attention_reverse || dqmc::AttentionOp(o).n_const() > 0)) return true;
-    return false;
+      if (o.kind == DQMC_OP_ATTENTION) {
+        if (!attention_reverse) return 1;
+        if (dqmc::AttentionOp(o).n_const() > 0) {
+          if (!nuclear_reverse || !nuc_set) return 1;
+          if (per_walker) return 2;
+        }
+      }
+    return 0;
+  }
+  bool attention_refused(bool per_walker = true) const { return attention_refusal(per_walker) != 0; }
+  std::string attention_refusal_text(bool per_walker) const {
+    return attention_refusal(per_walker) == 2
+               ? "the nuclear-token stream has no per-walker partials (all walkers share it: one nuclear backward per walker); only "
+                 "log_psi_vjp, orbitals_vjp and pretrain_loss_grad run with nuclear tokens"
+               : "no reverse pass for ATTENTION ops";
+  }
+  size_t grad_att_const() const {      // largest n_const * heads * head_dim of an ATTENTION op
+    size_t m = 0;
+    for (const auto& o : ops)
+      if (o.kind == DQMC_OP_ATTENTION) { const dqmc::AttentionOp a(o); m = std::max(m, (size_t)a.n_const() * a.heads() * a.head_dim()); }
+    return m;
   }
   // what the reverse pass reads and writes of an op: op_io, which leaves ATTENTION out because the forward planners that
   // call it never reach one
@@ -43,6 +65,7 @@
     b += sizeof(real) * (2 * grad_zrow() + max_ldw());                      // Z, dZ, dZs
     b += sizeof(double) * (grad_orb_partials() + 2 * (size_t)sys.n_det + 2);   // table partials, dL, conf_coeff / alpha partials
     b += sizeof(real) + sizeof(int32_t);                                        // log|psi|, sign when the caller passes none
+    b += sizeof(real) * 2 * grad_att_const();                                   // dKc, dVc partials of the constant rows
     return b;
   }
   size_t grad_part_bytes() const {

@@ -21,7 +21,7 @@
   bool kf_set = false;
 
   int set_kfac_map(const dqmc_kfac_map* hm) override {
-    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: no reverse pass for ATTENTION ops");
+    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: " + attention_refusal_text(true));
     if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: more than 64 electrons");
     if (!d_pm_src) return fail(DQMC_E_ARG, "no parameter map set (dqmc_set_param_map)");
     { const int rc = kfac_plan(); if (rc) return rc; }

@@ -13,6 +13,9 @@
 // caller's buffers) and by-value arguments that are functions of the program, the options and the batch size -- never of a
 // weight VALUE.  No buffer is reallocated here (d_w, d_wpk and d_tape keep their sizes), op_bf is decided from the shapes
 // alone, and the refinement threshold is read from device memory.  graph_epoch therefore stays as it is.
+//
+// With a nuclear stream registered (engine_nuc.inl) a device update also folds the stream from theta and scatters the derived
+// constants into d_w / d_w64 before the re-pack, and dqmc_grad_to_params ends with the stream's transpose.
 
   DevBuf<int32_t> d_pm_src;             // [n_weights] parameter element of every flat weight entry, -1: none
   DevBuf<int32_t> d_pm_row;             // [n_params + 1] transpose of the map, CSR: entries of element e are d_pm_col[row[e] .. row[e + 1])
@@ -112,6 +115,7 @@
   int weights_from_params(const double* theta) override {
     if (!d_pm_src) return fail(DQMC_E_ARG, "no parameter map set (dqmc_set_param_map)");
     dqmc::launch_weights_from_params<real>(st, theta, d_pm_src, d_w, d_w64, (long)n_weights);
+    if (nuc_set) nuc_fold_and_scatter(theta);      // (engine_nuc.inl: the constants of the nuclear stream, before the re-pack reads them)
     repack_from_dw();
     dev_ahead = true;
     if (twin) return twin->weights_from_params(theta);
@@ -131,13 +135,21 @@
   int seed_twin_from_device() {
     if (!twin || !d_pm_src) return DQMC_OK;
     int rc = twin->set_param_map(pm_src_h.data(), pm_src_h.size(), pm_n_params);
+    if (!rc && nuc_set) rc = twin->set_nuclear_stream(nuc_host_desc());
     if (!rc && dev_ahead) rc = twin->load_weights_device(d_w64);
     return rc;
   }
 
   int grad_to_params(const double* grad_w, double* grad_theta) override {
     if (!d_pm_src) return fail(DQMC_E_ARG, "no parameter map set (dqmc_set_param_map)");
+    if (nuc_set && !nuc_fresh)
+      return fail(DQMC_E_ARG, "dqmc_grad_to_params: the nuclear stream's activations are older than the weights (dqmc_set_weights since the "
+                              "last dqmc_weights_from_params)");
     dqmc::launch_grad_to_params(st, grad_w, d_pm_row, d_pm_col, grad_theta, (long)pm_n_params);
+    if (nuc_set) {      // the adjoints of the derived vector from the constant entries (ascending), then the stream's transpose
+      dqmc::launch_grad_to_params(st, grad_w, d_nuc_row, d_nuc_col, d_nuc_adj, (long)nuc_n_derived);
+      nuc_fold_vjp(grad_theta);
+    }
     return DQMC_OK;
   }
   int adam_step(double* theta, double* mu, double* nu, const double* g, size_t n, double lr, double b1, double b2, double eps, int64_t t,
@@ -166,7 +178,8 @@
     if (which == 0) { p = d_w; have = sizeof(real) * n_weights; }
     else if (which == 1) { if (d_tape && spec_k) { p = d_tape; have = (size_t)spec_k->tape_bytes; } }
     else if (which == 2) { if (d_wpk && fused_n_ops > 0) { p = d_wpk; have = sizeof(real) * wpk_len; } }
-    else return fail(DQMC_E_ARG, "which must be 0 (weights), 1 (tape), 2 (fused planes) or 3 (the twin's weights)");
+    else if (which == 4) { if (d_w64) { p = d_w64; have = sizeof(double) * n_weights; } }
+    else return fail(DQMC_E_ARG, "which must be 0 (weights), 1 (tape), 2 (fused planes), 3 (the twin's weights) or 4 (the double copy)");
     if (!p) return fail(DQMC_E_UNSUPPORTED, "this context has no such buffer");
     if (!out) return (int)have;
     if (bytes != have) return fail(DQMC_E_ARG, "buffer of " + std::to_string(bytes) + " bytes for " + std::to_string(have));

@@ -134,7 +134,7 @@
   }
 
   int pretrain_loss_grad(const void* r, const void* R, int B, double n_total, double* grad, double* per_sample_loss) override {
-    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "pretrain_loss_grad: no reverse pass for ATTENTION ops");
+    if (attention_refused(false)) return fail(DQMC_E_UNSUPPORTED, "pretrain_loss_grad: no reverse pass for ATTENTION ops");
     if (!pt_n_conf) return fail(DQMC_E_ARG, "pretrain_loss_grad: no target set (dqmc_set_pretrain_target)");
     if (!(n_total >= 1)) return fail(DQMC_E_ARG, "pretrain_loss_grad: n_total must be at least 1");
     HIP_TRY(hipMemsetAsync(grad, 0, sizeof(double) * n_weights, st));

@@ -294,6 +294,7 @@
     if (n != n_weights) return fail(DQMC_E_ARG, "weight buffer length differs from the one given at creation");
     ++graph_epoch;
     dev_ahead = false;                       // (engine_optim.inl: the host copies below are the newest again)
+    nuc_fresh = false;                       // (engine_nuc.inl: the constants below were folded on the host)
     if (d_w64) HIP_TRY(hipMemcpyAsync(d_w64, w, sizeof(double) * n, hipMemcpyHostToDevice, st));
     wtmp.resize(n);
     for (size_t k = 0; k < n; ++k) wtmp[k] = (real)w[k];
@@ -354,6 +355,12 @@
     if (s == "attention_ncb") { attention_ncb = value; return DQMC_OK; }
     if (s == "attention_split") { attention_split = value; return DQMC_OK; }
     if (s == "attention_reverse") { if (value != 0 && value != 1) return fail(DQMC_E_ARG, "attention_reverse must be 0 or 1"); attention_reverse = value; return DQMC_OK; }
+    if (s == "nuclear_reverse") {
+      if (value != 0 && value != 1) return fail(DQMC_E_ARG, "nuclear_reverse must be 0 or 1");
+      if (value && !nuc_set) return fail(DQMC_E_ARG, "nuclear_reverse needs a registered nuclear stream (dqmc_set_nuclear_stream)");
+      nuclear_reverse = value;
+      return DQMC_OK;
+    }
     if (s == "ws_budget_mb") { if (value < 1) return fail(DQMC_E_ARG, "ws_budget_mb must be positive"); ws_budget = (size_t)value << 20; return DQMC_OK; }
     if (s == "slogdet_mfma") { slogdet_mfma = value; return DQMC_OK; }
     if (s == "lane_compact") { lane_compact = value != 0; analyse_lanes(); last_B = 0; return DQMC_OK; }

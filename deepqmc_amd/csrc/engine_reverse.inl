@@ -95,7 +95,8 @@
   int reverse_pass(const real* r, const real* R, int B, const RevReq& q) {
     const std::string name = rev_name(q.mode);
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
-    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, name + ": no reverse pass for ATTENTION ops");
+    const bool per_walker = q.mode != Rev::Vjp && q.mode != Rev::Orbs;
+    if (attention_refused(per_walker)) return fail(DQMC_E_UNSUPPORTED, name + ": " + attention_refusal_text(per_walker));
     if (q.mode != Rev::Orbs && N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 64 electrons");   // (Orbs forms no inverse)
     { const int rc = grad_tables(); if (rc) return rc; }
     if (q.mode == Rev::Orbs) { const int rc = orb_tables(); if (rc) return rc; }
@@ -127,6 +128,7 @@
     const size_t o_kw = slab.take_bytes(kfac ? sizeof(double) * 2 * (size_t)B : 0), o_kpart = slab.take_bytes(kfac ? kfac_part_bytes() : 0);
     const size_t o_slot = slab.take_bytes(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
     const size_t o_tgt = slab.take_bytes(orbs && !q.cot_orb ? (size_t)B * pt_target_bytes_per_walker() : 0);
+    const size_t o_cpart = slab.take_bytes(sizeof(real) * (size_t)B * 2 * grad_att_const());      // (nuclear tokens: [B][2][n_const][H * hd])
     { const int rc = grad_ws_reserve(slab.bytes); if (rc) return rc; }
     char* gw = g_ws;
     auto A = [&](int b) { return reinterpret_cast<real*>(gw + adj[b]); };
@@ -245,14 +247,21 @@
                                            e.dst_col0(), gt + t[0], t[1], e.width(), B, N, e.scale());
           break;
         }
-        case DQMC_OP_ATTENTION: {    // no parameters: the same in every mode (dq, dk, dv are added into the adjoint buffers)
-          const dqmc::AttentionOp& at = v.att;
+        case DQMC_OP_ATTENTION: {    // dq, dk, dv are added into the adjoint buffers, the same in every mode; constant key / value
+          const dqmc::AttentionOp& at = v.att;      // rows (Vjp, Orbs only) are weight entries: per-walker partials, summed below
           for (int x = 0; x < 4; ++x)
             for (int y = x + 1; y < 4; ++y)
               if (at.buf(x) == at.buf(y)) return fail(DQMC_E_UNSUPPORTED, std::string(rev_name(q.mode)) + ": ATTENTION op with shared q / k / v / dst buffers");
           t_begin("attention_bwd", 2.0 * B * at.heads() * (double)N * N * at.head_dim() * 5.0);
+          const int nc = at.n_const(), HD = at.heads() * at.head_dim();
+          real* cpart = reinterpret_cast<real*>(gw + o_cpart);
           const int rc2 = dqmc::launch_attention_bwd<real>(st, bptr(at.q()), bptr(at.k()), bptr(at.v()), A(at.dst()), A(at.q()), A(at.k()), A(at.v()),
-                                                           bufs[at.q()].width, at.heads(), at.head_dim(), B, N);
+                                                           bufs[at.q()].width, at.heads(), at.head_dim(), B, N, nc, nc ? d_w + at.const_k() : nullptr,
+                                                           nc ? d_w + at.const_v() : nullptr, nc ? cpart : nullptr);
+          if (rc2 == 0 && nc) {
+            emit_partials((const real*)cpart, 2L * nc * HD, nc * HD, at.const_k());
+            emit_partials((const real*)cpart + (size_t)nc * HD, 2L * nc * HD, nc * HD, at.const_v());
+          }
           t_end();
           if (rc2 == -1) return fail(DQMC_E_UNSUPPORTED, std::string(rev_name(q.mode)) + ": attention backward tile set (N, head_dim) exceeds the LDS or the register tile");
           if (rc2) return fail(DQMC_E_HIP, "attention backward launch failed");

@@ -289,5 +289,6 @@ template int launch_attention<double>(hipStream_t, const double*, const double*,
                                       int, int, LaneInfo, int, const double*, const double*);
 
 #include "kernels_attention_bwd.inl"
+#include "kernels_nuc.inl"
 
 }  // namespace dqmc

@@ -185,12 +185,37 @@ template <typename real>
 int launch_attention(hipStream_t st, const real* q, const real* k, const real* v, real* out, int width, int H, int hd,
                      int B, LaneInfo li, int n_const, const real* k_const, const real* v_const);
 template <typename real> size_t attention_lds_bytes(int N, int hd, int n_const);
-// kernels_attention_bwd.inl: the reverse pass's backward of the op (TP = 1, no constant keys); dq, dk, dv are added into.
-// Returns 0, or -1 if the shape is not supported (LDS tile set, N * hd per thread), -2 on a HIP error
+// kernels_attention_bwd.inl: the reverse pass's backward of the op (TP = 1); dq, dk, dv are added into.  n_const > 0: the
+// constant key / value rows kc, vc [n_const][H * hd] come first in the key order as in the forward, and their per-walker
+// partials are WRITTEN to cpart [B][2][n_const][H * hd] (dKc then dVc).  n_const == 0: kc, vc, cpart are not read.
+// Returns 0, or -1 if the shape is not supported (LDS tile set, N * hd or n_const * hd per thread), -2 on a HIP error
 template <typename real>
 int launch_attention_bwd(hipStream_t st, const real* q, const real* k, const real* v, const real* dout, real* dq, real* dk, real* dv,
-                         int width, int H, int hd, int B, int N);
-template <typename real> size_t attention_bwd_lds_bytes(int N, int hd);
+                         int width, int H, int hd, int B, int N, int n_const, const real* kc, const real* vc, real* cpart);
+template <typename real> size_t attention_bwd_lds_bytes(int N, int hd, int n_const);
+
+// ---- kernels_nuc.inl (included by kernel_attention.hip): the nuclear-token stream of the TransPsiformer in float64 ----
+// (engine_nuc.inl says what is chained how; activation codes as DQMC_OP_LINEAR: 0 none, 1 tanh, 2 silu)
+void launch_nuc_edge_feat(hipStream_t st, const double* R, const int32_t* types, double eps, double* F, int n);
+// Z = X W + b, Y = act(Z) (+ res); Z == Y where act is 0
+void launch_nuc_linear(hipStream_t st, const double* X, const double* W, const double* b, double* Z, double* Y, const double* res, int rows,
+                       int n_in, int n_out, int act);
+// dZ = dY act'(Z) (act 0: dY itself, dZ unused); gW += X^T dZ, gb += column sums (gb may be nullptr); dX += dZ W^T (dX may be nullptr)
+void launch_nuc_linear_bwd(hipStream_t st, const double* X, const double* W, const double* Z, const double* dY, double* dZ, double* dX,
+                           double* gW, double* gb, int rows, int n_in, int n_out, int act);
+void launch_nuc_sender_sum(hipStream_t st, const double* in, double* out, int n, int w);
+void launch_nuc_sender_sum_bwd(hipStream_t st, const double* dout, double* din, int n, int w);
+void launch_nuc_add(hipStream_t st, double* a, const double* b, long n);
+void launch_nuc_attention(hipStream_t st, const double* q, const double* k, const double* v, double* P, double* o, int n, int H, int hd);
+void launch_nuc_attention_bwd(hipStream_t st, const double* q, const double* k, const double* v, const double* P, const double* dO, double* dS,
+                              double* dq, double* dk, double* dv, int n, int H, int hd);
+void launch_nuc_layernorm(hipStream_t st, const double* h, double* ln, double* rstd, int n, int D);
+void launch_nuc_layernorm_bwd(hipStream_t st, const double* ln, const double* rstd, const double* dln, double* dh, int n, int D);
+void launch_nuc_glu(hipStream_t st, const double* zw, const double* zv, const double* bias, double* zeta, long n);
+void launch_nuc_glu_bwd(hipStream_t st, const double* zw, const double* zv, const double* dzeta, double* dzw, double* dzv, double* gbias,
+                        long n);
+template <typename real>
+void launch_nuc_scatter(hipStream_t st, const double* derived, const int32_t* row, const int32_t* col, real* w, double* w64, long n);
 
 // ---- kernel_attention_mfma.hip: contractions on MFMA, float32 and float64 (head_dim % 16 == 0, <= 64 queries / keys) ----
 template <typename real> size_t attention_mfma_lds_bytes(int N, int hd, int n_const);

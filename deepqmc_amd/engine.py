@@ -53,12 +53,15 @@ def _ptr(t):
 
 class Engine:
     def __init__(self, spec: AnsatzSpec, hamil: MolecularHamiltonian, params, *, dtype=torch.float32,
-                 device='cuda', norm_eps: Optional[float] = None, lib=None, R=None, compiler=None):
+                 device='cuda', norm_eps: Optional[float] = None, lib=None, R=None, compiler=None, nuclear_reverse=False):
         """`R` [n_nuc,3]: the geometry this context is compiled for (default: the Hamiltonian's).  It matters only
         for ansatzes with nuclear tokens, whose nuclear stream is folded into the program; every other ansatz
         takes the geometry per call.  `compiler(params) -> Program` replaces the default `compile_program(spec, ...)`
         (e.g. program_featurewise.compile_featurewise for the reference's test ansatz family); `spec` may then be
-        any object with `n_determinants` and `nuclei_tokens`."""
+        any object with `n_determinants` and `nuclei_tokens`.  `nuclear_reverse`: for an ansatz with nuclear tokens, register
+        the nuclear stream with the library (dqmc_set_nuclear_stream) and switch on options "attention_reverse" and
+        "nuclear_reverse": device updates fold the stream on the device and grad_to_params transposes it, so the
+        walker-summed gradients (log_psi_vjp, orbitals_vjp, pretrain_loss_grad) and the Adam step run."""
         self.lib = lib if lib is not None else _lib.load()
         self.spec, self.hamil = spec, hamil
         self.dtype = dtype
@@ -70,7 +73,8 @@ class Engine:
         self.R0 = np.asarray(hamil.mol.coords if R is None else R, np.float64).reshape(hamil.n_nuc, 3)
         R0_, eps_ = self.R0, self.norm_eps      # (no `self` in the closure: a cycle would leave the context -- tens of GB of
         self._compile = compiler if compiler is not None else (       # workspace -- to the cyclic collector instead of the reference count)
-            lambda p_: compile_program(spec, p_, hamil.n_up, hamil.n_down, hamil.n_nuc, R=R0_, eps=eps_))
+            lambda p_: compile_program(spec, p_, hamil.n_up, hamil.n_down, hamil.n_nuc, R=R0_, eps=eps_,
+                                       nuclear_reverse=bool(nuclear_reverse) and bool(spec.nuclei_tokens)))
         self.program: Program = self._compile(params)
         self._theta_ref = None         # the device vector of the last device update (params_flat)
         self.params_ahead = False      # set by a device update: the context's weights are newer than the tree it is cached under
@@ -107,6 +111,30 @@ class Engine:
             self._check(self.lib.dqmc_set_ecp(self._ctx, pot.loc_params.shape[3], _np_ptr(pot.loc_params, or_null=True),
                                               pot.nl_params.shape[1], pot.nl_params.shape[3], _np_ptr(pot.nl_params, or_null=True)))
         self.R = torch.tensor(self.R0, dtype=dtype, device=self.device)      # (a copy: R0 may be the molecule's read-only array)
+        self._theta_host = None        # nuclear stream: the parameters of the last host upload (some leaves have no copy in the weights)
+        if p.nuclear_stream is not None:
+            self._theta_host = p.flatten_params(params)
+            self._register_nuclear_stream()
+            self.set_option('attention_reverse', 1)
+            self.set_option('nuclear_reverse', 1)
+
+    def _register_nuclear_stream(self):
+        """dqmc_set_nuclear_stream from Program.nuclear_stream and the current parameters."""
+        self._ensure_param_map()
+        ns = self.program.nuclear_stream
+        lin = (_lib.DqmcNucLinear * len(ns['lin']))()
+        for k, (w, b, n_in, n_out, act) in enumerate(ns['lin']):
+            lin[k].w, lin[k].b, lin[k].n_in, lin[k].n_out, lin[k].act = w, b, n_in, n_out, act
+        types = np.ascontiguousarray(ns['nuc_types'], np.int32)
+        Rn = np.ascontiguousarray(ns['R'], np.float64)
+        row = np.ascontiguousarray(ns['sc_row'], np.int64)
+        col = np.ascontiguousarray(ns['sc_col'], np.int32)
+        theta = np.ascontiguousarray(self._theta_host, np.float64)
+        d = _lib.DqmcNucStream(self.hamil.n_nuc, ns['n_layers'], ns['heads'], ns['dim'], ns['n_det'], ns['n_env'], ns['n_edge_lin'],
+                               ns['n_embed_lin'], ns['n_mlp_lin'], len(ns['lin']), lin, ns['zbias'][0], ns['zbias'][1],
+                               _np_ptr(types, ctypes.c_int32), _np_ptr(Rn), ns['n_derived'], _np_ptr(row, ctypes.c_int64),
+                               _np_ptr(col, ctypes.c_int32), _np_ptr(theta))
+        self._check(self.lib.dqmc_set_nuclear_stream(self._ctx, ctypes.byref(d)))
 
     # ------------------------------------------------------------------
     def _check(self, rc: int):
@@ -186,6 +214,14 @@ class Engine:
         w = self._w_host = np.ascontiguousarray(prog.weights, np.float64)
         self._check(self.lib.dqmc_set_weights(self._ctx, _np_ptr(w), w.size))
         self.params_ahead, self._theta_ref = False, None
+        if prog.nuclear_stream is not None:
+            # the host upload carries constants folded on the host; the transpose of the fold needs the activations of a device
+            # fold of the same parameters (include/dqmc.h: the invariant of dqmc_set_nuclear_stream), so fold them there as well
+            self._theta_host = prog.flatten_params(params)
+            theta = torch.as_tensor(self._theta_host, dtype=torch.float64, device=self.device).contiguous()
+            self._check(self.lib.dqmc_weights_from_params(self._ctx, theta.data_ptr()))
+            if self.device.type == 'cuda':
+                torch.cuda.current_stream(self.device).synchronize()      # (theta is a temporary)
 
     # ---- device-resident parameters and optimiser step (dqmc_set_param_map ... dqmc_apply_update) ----
     def _ensure_param_map(self):
@@ -217,6 +253,8 @@ class Engine:
         prog = self.program
         if prog.grad_unsupported:
             raise NotImplementedError(f'params_flat: unsupported for this program ({prog.grad_unsupported})')
+        if self._theta_host is not None:
+            return torch.as_tensor(self._theta_host, dtype=torch.float64, device=self.device).contiguous()
         m = prog.grad_src >= 0
         theta = np.zeros(prog.n_params(), np.float64)
         theta[prog.grad_src[m]] = self._w_host[m]
@@ -364,7 +402,8 @@ class Engine:
 
     def debug_read_weights(self, which: int):
         """Raw bytes (np.uint8) of a weight buffer of the context (dqmc_debug_read_weights): 0 flat weights, 1 the sub-step
-        kernel's tape, 2 the fused kernel's planes, 3 the float64 twin's flat weights.  None if the context has no such buffer."""
+        kernel's tape, 2 the fused kernel's planes, 3 the float64 twin's flat weights, 4 the double copy of a float32 context's flat
+        weights.  None if the context has no such buffer."""
         n = self.lib.dqmc_debug_read_weights(self._ctx, int(which), None, 0)
         if n == -4:         # DQMC_E_UNSUPPORTED
             return None

@@ -82,6 +82,8 @@ def make_grad_nuc_log_wf(wf):
         eng = wf.engine(params, R)
         if eng.program.grad_unsupported:
             raise NotImplementedError(f'make_grad_nuc_log_wf: unsupported for this program ({eng.program.grad_unsupported})')
+        if eng.program.nuclear_stream is not None:
+            raise NotImplementedError(f'make_grad_nuc_log_wf: {eng.program.PER_WALKER_NUCLEAR}')
         return eng.log_psi_grad_coords(r, R, want_r=False)[3].double()
 
     return grad_nuc_log_wf
@@ -102,6 +104,8 @@ def _estimator(hamil, wf, est, *, takes_rng, needs_energy):
         if nuc:
             if eng.program.grad_unsupported:
                 raise NotImplementedError(f'evaluate_hf_force_{est}: unsupported for this program ({eng.program.grad_unsupported})')
+            if eng.program.nuclear_stream is not None:
+                raise NotImplementedError(f'evaluate_hf_force_{est}: {eng.program.PER_WALKER_NUCLEAR}')
             grad_R = eng.log_psi_grad_coords(r, R, want_r=False)[3]
         if needs_energy:
             e_loc, energy = _centred(eng, e_loc, energy)

@@ -744,7 +744,7 @@ class LossFunction:
                 rr = torch.cat([torch.as_tensor(rr, dtype=eng.dtype, device=eng.device), rp.reshape(B * n_up, *rp.shape[2:])])
                 cot = torch.cat([cot + k[q] * rho.sum(-1), (-k[q][:, None] * rho).reshape(-1)])
             _, _, g = eng.log_psi_vjp(rr, cot.to(eng.dtype).contiguous(), Rs[0])
-            grads.append(eng.grad_to_params(g) if flat else eng.program.unflatten_grad(g))
+            grads.append(eng.grad_to_params(g) if flat else self.ansatz._grad_tree(eng, g))
         return v['loss'], grads, (v['e_loc'], v['psi_ratio'], v['stats'])
 
     __call__ = loss_and_grad

@@ -67,6 +67,13 @@ class _Optimizer:
         Rs = [None] if phys_conf is None else _unpack(phys_conf)[1]
         return [self.ansatz.engine(p, Rs[0]) for p in params]
 
+    def _refuse_nuclear_stream(self, params, batch):
+        """The optimisers that need per-walker partials of log|psi| (Jacobian rows, KFAC factors) cannot take a program whose
+        nuclear-token stream is shared by all walkers."""
+        for eng in self._engines(params, batch[0] if batch is not None else None):
+            if eng.program.nuclear_stream is not None:
+                raise NotImplementedError(f'{type(self).__name__}: {eng.program.PER_WALKER_NUCLEAR}')
+
     @staticmethod
     def _batch(batch):
         phys_conf, weight = batch[0], batch[1] if len(batch) > 1 else None
@@ -153,6 +160,7 @@ class NaturalGradientOptimizer(_Optimizer):
                                       'contraction with the Jacobian of log|psi|')
 
     def init(self, rng, params, batch):
+        self._refuse_nuclear_stream(params, batch)
         return self._new_state(params, batch, moments=False)
 
     def step(self, rng, params, opt_state, batch):
@@ -196,6 +204,7 @@ class KFACOptimizer(_Optimizer):
                                       'contraction with the Jacobian of log|psi|')
 
     def init(self, rng, params, batch):
+        self._refuse_nuclear_stream(params, batch)
         state = self._new_state(params, batch, moments=False)
         for st in state:
             st['kfac'] = None          # allocated by the first step (Engine.kfac_state), which overwrites it

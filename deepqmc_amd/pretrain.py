@@ -139,7 +139,8 @@ def pretrain_loss_and_grad(wf, params: Sequence, phys_conf_r, dataset, target_fn
             eng._pretrain_key, eng._pretrain_target_ref = key, target_fn      # (the reference keeps id() from being recycled)
         p, g = eng.pretrain_loss_grad(r[0, s].contiguous(), Rs[0], n_total=n_total)
         loss = loss + float(p.sum()) / n_total
-        grads.append(eng.program.unflatten_grad(g))
+        # (a device-folded nuclear stream is transposed on the device: Engine.grad_to_params)
+        grads.append(wf._grad_tree(eng, g))
         ps.append(p)
     return loss, grads, torch.stack(ps)[None]
 

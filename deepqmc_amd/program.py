@@ -103,12 +103,26 @@ class Program:
     grad_src: Optional[np.ndarray] = None
     grad_leaves: Optional[Dict[Tuple[str, str], Tuple[int, tuple]]] = None
     grad_unsupported: Optional[str] = None
+    # compile_program(..., nuclear_reverse=True): the nuclear-token stream as the library folds it on the device
+    # (dqmc_set_nuclear_stream): {'n_layers', 'heads', 'dim', 'n_det', 'n_env', 'n_edge_lin', 'n_embed_lin', 'n_mlp_lin',
+    # 'lin': [(w, b, n_in, n_out, act)] offsets into theta, 'zbias': (up, down), 'nuc_types', 'R', 'n_derived',
+    # 'sc_row', 'sc_col': CSR of the weight entries that are copies of each derived element}.  Its leaves (nuclei_embedding,
+    # nuclear_gnn_head) are part of grad_leaves without a copy in the weight buffer; the transpose of the fold exists on the
+    # device only (Engine.grad_to_params).
+    nuclear_stream: Optional[dict] = None
+
+    PER_WALKER_NUCLEAR = ('the nuclear-token stream has no per-walker partials (all walkers share it: one nuclear backward per '
+                          'walker); only the walker-summed gradients (log_psi_vjp, orbitals_vjp, pretraining, AdamOptimizer) run '
+                          'with nuclear tokens')
 
     def unflatten_grad(self, g):
         """Flat gradient over the weight buffer (dqmc_log_psi_vjp) -> haiku tree {module: {leaf: array}}: the transpose of
         the packing (copies, zero padding, broadcasts and column scatters are summed back onto their parameter element)."""
         if self.grad_unsupported:
             raise NotImplementedError(f'unflatten_grad: unsupported for this program ({self.grad_unsupported})')
+        if self.nuclear_stream is not None:
+            raise NotImplementedError('unflatten_grad: the transpose of the nuclear-stream fold runs on the device only; use '
+                                      'Engine.grad_to_params(g) and Program.unflatten_params')
         if hasattr(g, 'detach'):
             g = g.detach().cpu().numpy()
         g = np.asarray(g, np.float64).reshape(-1)
@@ -184,6 +198,8 @@ class Program:
         A gather per source multiplicity summed in a fixed order, so the result is deterministic on the GPU."""
         if self.grad_unsupported:
             raise NotImplementedError(f'unflatten_jacobian: unsupported for this program ({self.grad_unsupported})')
+        if self.nuclear_stream is not None:
+            raise NotImplementedError(f'unflatten_jacobian: {self.PER_WALKER_NUCLEAR}')
         import torch
         if J.dim() != 2 or J.shape[1] != self.grad_src.size:
             raise ValueError(f'Jacobian of shape {tuple(J.shape)} for a weight buffer of {self.grad_src.size}')
@@ -230,6 +246,8 @@ class Program:
         diagonal treatment."""
         if self.grad_unsupported:
             raise NotImplementedError(f'kfac_blocks: unsupported for this program ({self.grad_unsupported})')
+        if self.nuclear_stream is not None:
+            raise NotImplementedError(f'kfac_blocks: {self.PER_WALKER_NUCLEAR}')
         lay = self.kfac_layout()
         by_mod: Dict[str, list] = {}
         for q, o in enumerate(lay['ops']):
@@ -324,6 +342,8 @@ class _Builder:
         self.n_el = 0
         self.id_override: Dict[Tuple[str, str], np.ndarray] = {}
         self.grad_unsupported: Optional[str] = None
+        self.dsrc: List[np.ndarray] = []      # per push_w: the derived element of the nuclear stream every entry is a copy of (-1: none)
+        self.nuclear_stream: Optional[dict] = None
 
     def ids(self, module, leaf):
         """Element ids of parameter leaf (module, leaf), shaped like the leaf (or as overridden by a re-layout)."""
@@ -341,6 +361,16 @@ class _Builder:
         prog.grad_src = np.concatenate(self.src).astype(np.int64)
         prog.grad_leaves = dict(self.leaves)
         prog.grad_unsupported = self.grad_unsupported
+        if self.nuclear_stream is not None:
+            ns = dict(self.nuclear_stream)
+            dsrc = np.concatenate(self.dsrc)
+            j = np.nonzero(dsrc >= 0)[0]
+            order = np.argsort(dsrc[j], kind='stable')        # by derived element, ascending entry within an element
+            counts = np.bincount(dsrc[j], minlength=ns['n_derived'])
+            assert counts.size == ns['n_derived'] and counts.min() >= 1
+            ns['sc_row'] = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            ns['sc_col'] = j[order].astype(np.int32)
+            prog.nuclear_stream = ns
         return prog
 
     # -- allocation helpers --
@@ -349,9 +379,9 @@ class _Builder:
         self.names[name] = len(self.bufs) - 1
         return len(self.bufs) - 1
 
-    def push_w(self, arr, slot, src=None):
+    def push_w(self, arr, slot, src=None, derived=None):
         """src: parameter element id of every entry of `arr` (-1: none); default: the leaf itself for 'raw' slots, none
-        for constants."""
+        for constants.  derived: the element of the nuclear stream's derived vector every entry is a copy of."""
         off = self.w_len
         a = np.asarray(arr, np.float64).reshape(-1)
         n = pad4(a.size)
@@ -363,6 +393,10 @@ class _Builder:
         if src is not None:
             sb[:a.size] = np.asarray(src, np.int64).reshape(-1)
         self.src.append(sb)
+        db = np.full(n, -1, np.int64)
+        if derived is not None:
+            db[:a.size] = np.asarray(derived, np.int64).reshape(-1)
+        self.dsrc.append(db)
         self.w.append(buf)
         self.w_len += n
         self.slots.append((off,) + slot)
@@ -453,9 +487,51 @@ class _Builder:
                     c[k]()
 
 
-def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int, R=None, eps=None) -> Program:
+def _nuclear_stream_descriptor(b: '_Builder', spec: AnsatzSpec, R, n_nuc: int) -> dict:
+    """The stream of nuclear_stream.fold as offsets into theta (registers the nuclei_embedding / nuclear_gnn_head leaves and the
+    shared attention leaves in grad_leaves)."""
+    from .nuclear_stream import NUC_EDGE_MLP, NUC_EMB, NUC_HEAD, nuc_embed_mlp
+    D, K = spec.embedding_dim, spec.n_determinants
+    lin = []
+
+    def add(module, act):
+        w = b.ids(module, 'w')
+        has_b = 'b' in b.params[module]
+        lin.append((int(w.reshape(-1)[0]), int(b.ids(module, 'b').reshape(-1)[0]) if has_b else -1, int(w.shape[0]), int(w.shape[1]),
+                    ACT[act]))
+
+    def add_mlp(prefix, mspec, in_dim, out_dim):
+        dims = mspec.dims(in_dim, out_dim)
+        for i in range(len(dims)):
+            add(f'{prefix}/linear_{i}', mspec.layer_act(i, len(dims)))
+        return len(dims)
+
+    n_edge = add_mlp(f'{NUC_EMB}/edge_mlp', NUC_EDGE_MLP, 4 + n_nuc, 32)
+    n_embed = add_mlp(f'{NUC_EMB}/embed_mlp', nuc_embed_mlp(D), 32, D)
+    n_mlp = 0
+    for l in range(spec.n_interactions):
+        uf = f'{layer_name(l)}/~/{attention_feature_name(spec)}'
+        for nm in ('query', 'key', 'value', 'linear'):
+            add(f'{uf}/multi_head_attention/{nm}', None)
+        n_mlp = add_mlp(f'{uf}/mlp', spec.attn_mlp, D, D)
+    n_env, zbias = 0, (-1, -1)
+    if spec.envelope == 'simplified':
+        n_env = spec.n_envelope_per_nucleus
+        for glu in ('zetas_readout_glu', 'zetas_readout_glu_1'):
+            for nm in ('W', 'V'):
+                add(f'{NUC_HEAD}/{glu}/{nm}', None)
+        zbias = tuple(int(b.ids(NUC_HEAD, f'zetas_bias_{spin}').reshape(-1)[0]) for spin in ('up', 'down'))
+    n_derived = 2 * spec.n_interactions * n_nuc * D + (2 * n_nuc * K * n_env if n_env else 0)
+    return dict(n_layers=spec.n_interactions, heads=spec.num_heads, dim=D, n_det=K, n_env=n_env, n_edge_lin=n_edge,
+                n_embed_lin=n_embed, n_mlp_lin=n_mlp, lin=lin, zbias=zbias, nuc_types=np.asarray(spec.nuc_types, np.int32),
+                R=np.ascontiguousarray(R, np.float64).reshape(n_nuc, 3), n_derived=n_derived)
+
+
+def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int, R=None, eps=None, nuclear_reverse=False) -> Program:
     """`R` [n_nuc,3] and the safe-norm `eps` are needed only by ansatzes with nuclear tokens, whose
-    electron-independent nuclear stream is folded into constants here (nuclear_stream.py)."""
+    electron-independent nuclear stream is folded into constants here (nuclear_stream.py).  `nuclear_reverse`: the program also
+    describes that stream for the library (Program.nuclear_stream), which then folds it on the device after a device update
+    and transposes it in Engine.grad_to_params; grad_unsupported stays unset and grad_leaves covers the stream's leaves."""
     b = _Builder(spec, params, n_up, n_down, n_nuc)
     nuc_kv, nuc_zetas = None, None
     if spec.nuclei_tokens:
@@ -463,7 +539,10 @@ def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int
             raise ValueError(f'{spec.name}: the nuclear geometry R and eps are needed to compile nuclear tokens')
         from .nuclear_stream import fold
         nuc_kv, nuc_zetas = fold(params, spec, R, eps)
-        b.grad_unsupported = 'the nuclear-token stream is folded into constants and simplified envelopes (not a copy of parameters)'
+        if nuclear_reverse:
+            b.nuclear_stream = _nuclear_stream_descriptor(b, spec, R, n_nuc)
+        else:
+            b.grad_unsupported = 'the nuclear-token stream is folded into constants and simplified envelopes (not a copy of parameters)'
     N, K, D, E = n_up + n_down, spec.n_determinants, spec.embedding_dim, spec.two_particle_dim
     S2 = 1.0 / np.sqrt(2.0)
 
@@ -517,8 +596,9 @@ def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int
             n_const, kc_off, vc_off = 0, 0, 0
             if nuc_kv is not None:       # nuclear tokens: constant extra key / value rows (no derivative lanes)
                 n_const = n_nuc
-                kc_off = b.push_w(nuc_kv[l][0], ('', '', 'const', ()))
-                vc_off = b.push_w(nuc_kv[l][1], ('', '', 'const', ()))
+                kv_id = 2 * l * n_nuc * H * hd + np.arange(n_nuc * H * hd)       # derived vector: K_nuc then V_nuc of every layer
+                kc_off = b.push_w(nuc_kv[l][0], ('', '', 'const', ()), derived=kv_id)
+                vc_off = b.push_w(nuc_kv[l][1], ('', '', 'const', ()), derived=kv_id + n_nuc * H * hd)
             b.ops.append(Op(OP_ATTENTION, [q, k_, v, att, H, hd, n_const, kc_off, vc_off], note=f'layer {l} attention'))
             # attention FLOPs (QK^T and PV), algorithmic: 2 * 2 * N*(N + n_const)*D per walker
             b.flops += 4.0 * N * (N + n_const) * H * hd
@@ -601,9 +681,13 @@ def compile_program(spec: AnsatzSpec, params, n_up: int, n_down: int, n_nuc: int
         # [K*N orbitals][n_nuc * n_env] table the ORBITALS kernel reads: zeta[(k,mu)][(nuc,e)] = zetas[nuc,k,e]
         n_env = spec.n_envelope_per_nucleus
         offs = [b.push_w(np.ones((K * N, n_nuc * n_env)), ('', '', 'const', ())) for _ in range(2)]
-        for spin in ('up', 'down'):
+        for s, spin in enumerate(('up', 'down')):
             z = np.transpose(nuc_zetas[spin], (1, 0, 2)).reshape(K, 1, n_nuc * n_env)
-            offs.append(b.push_w(np.broadcast_to(z, (K, N, n_nuc * n_env)), ('', '', 'const', ())))
+            # (derived vector: after the K / V rows of every layer, zetas up then down, each [n_nuc][K][n_env])
+            z_id = 2 * len(rows) * n_nuc * D + s * n_nuc * K * n_env + np.arange(n_nuc * K * n_env).reshape(n_nuc, K, n_env)
+            z_id = np.transpose(z_id, (1, 0, 2)).reshape(K, 1, n_nuc * n_env)
+            offs.append(b.push_w(np.broadcast_to(z, (K, N, n_nuc * n_env)), ('', '', 'const', ()),
+                                 derived=np.broadcast_to(z_id, (K, N, n_nuc * n_env))))
     else:
         env = params[f'{WF}/~/exponential_envelopes']
         offs = [b.push_w(env[nm], (f'{WF}/~/exponential_envelopes', nm, 'raw', ())) for nm in

@@ -30,19 +30,25 @@ from .types import PhysicalConfiguration, Psi
 
 class NeuralNetworkWaveFunction:
     def __init__(self, hamil: MolecularHamiltonian, spec='paulinet', *, dtype=torch.float32, device='cuda',
-                 norm_eps=None, lib=None, attention_reverse=False):
+                 norm_eps=None, lib=None, attention_reverse=False, nuclear_reverse=False):
         """`attention_reverse`: opt in to the reverse pass through attention ops (library option "attention_reverse"), which
         the parameter- and coordinate-gradient entry points below, the force and ECP-force estimators, pretraining,
         `create_loss_fn` and the optimisers of `fit_wf` need for a Psiformer.  Off (the default) those calls fail with
-        `dqmc error -4` for an attention ansatz.  The TransPsiformer stays unsupported either way (its nuclear tokens are
-        folded on the host)."""
+        `dqmc error -4` for an attention ansatz.  The TransPsiformer stays unsupported with this flag alone (its nuclear tokens
+        are folded on the host).
+        `nuclear_reverse` (implies `attention_reverse`): the nuclear-token stream of a TransPsiformer is also folded on the
+        device and has a backward there (library option "nuclear_reverse"), which opens `log_psi_vjp`, `orbitals_vjp`,
+        pretraining, `create_loss_fn` and `fit_wf` with AdamOptimizer / NoOptimizer.  The per-walker modes (log_psi_jacobian,
+        log_psi_kfac, log_psi_grad_coords, NaturalGradientOptimizer, KFACOptimizer, forces) stay refused: the stream is shared
+        by all walkers and has no per-walker partials."""
         self.hamil = hamil
         if spec == 'transpsiformer':
             self.spec: AnsatzSpec = ANSATZES[spec](hamil.mol.charges)      # atom types of the nuclei embedding
         else:
             self.spec = ANSATZES[spec]() if isinstance(spec, str) else spec
         self.dtype, self.device, self.norm_eps, self._lib = dtype, device, norm_eps, lib
-        self.attention_reverse = bool(attention_reverse)
+        self.nuclear_reverse = bool(nuclear_reverse) and bool(self.spec.nuclei_tokens)
+        self.attention_reverse = bool(attention_reverse) or bool(nuclear_reverse)
         self._engines = []       # [(params tree, Engine)], most recently used last (one per electronic state)
         self.max_engines = 8
         self._evictions = 0
@@ -94,7 +100,7 @@ class NeuralNetworkWaveFunction:
             import numpy as np
             R0 = None if gkey is None else np.frombuffer(gkey, np.float64).reshape(self.hamil.n_nuc, 3)
             eng = Engine(self.spec, self.hamil, params, dtype=self.dtype, device=self.device,
-                         norm_eps=self.norm_eps, lib=self._lib, R=R0)
+                         norm_eps=self.norm_eps, lib=self._lib, R=R0, nuclear_reverse=self.nuclear_reverse)
             if self.attention_reverse:      # before any set_kfac_map or graph capture (setting an option bumps the graph epoch)
                 eng.set_option('attention_reverse', 1)
         self._engines.append((params, gkey, eng))
@@ -167,6 +173,21 @@ class NeuralNetworkWaveFunction:
 
     __call__ = apply
 
+    @staticmethod
+    def _grad_tree(eng, g):
+        """Flat gradient over the weight buffer -> tree.  Programs with a device-folded nuclear stream take the device route
+        (Engine.grad_to_params transposes the fold there), every other program the host transpose of the packing."""
+        prog = eng.program
+        if prog.nuclear_stream is not None:
+            return prog.unflatten_params(eng.grad_to_params(g))
+        return prog.unflatten_grad(g)
+
+    def _per_walker_check(self, name, eng):
+        if eng.program.grad_unsupported:
+            raise NotImplementedError(f'{name}: unsupported for this program ({eng.program.grad_unsupported})')
+        if eng.program.nuclear_stream is not None:
+            raise NotImplementedError(f'{name}: {eng.program.PER_WALKER_NUCLEAR}')
+
     def _orbital_engine(self, name, params, phys_conf):
         if not self.spec.full_determinant:
             raise NotImplementedError(f'{name}: only full-determinant programs expose their orbital matrices; spin-factorised '
@@ -193,7 +214,7 @@ class NeuralNetworkWaveFunction:
         if isinstance(cotangent, (tuple, list)):
             cotangent = torch.cat([torch.as_tensor(c, dtype=self.dtype, device=self.device) for c in cotangent], dim=2)
         A, g = eng.orbitals_vjp(r, cotangent, R)
-        return (A[:, :, :self.hamil.n_up], A[:, :, self.hamil.n_up:]), eng.program.unflatten_grad(g)
+        return (A[:, :, :self.hamil.n_up], A[:, :, self.hamil.n_up:]), self._grad_tree(eng, g)
 
     def log_psi_vjp(self, params, phys_conf, cotangent=None):
         """jax.vjp of vmap(ansatz.apply)(params, r).log (loss/loss_function.py:59-75) with one cotangent per walker:
@@ -207,7 +228,7 @@ class NeuralNetworkWaveFunction:
         if self.attention_reverse and eng.program.grad_unsupported:
             raise NotImplementedError(f'log_psi_vjp: unsupported for this program ({eng.program.grad_unsupported})')
         sign, log, g = eng.log_psi_vjp(r, cotangent, R)
-        return Psi(sign, log), eng.program.unflatten_grad(g)
+        return Psi(sign, log), self._grad_tree(eng, g)
 
     def log_psi_jacobian(self, params, phys_conf):
         """The per-walker rows of the Jacobian that log_psi_vjp contracts: returns (Psi(sign, log), Jp) with
@@ -217,8 +238,7 @@ class NeuralNetworkWaveFunction:
         r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
         R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
         eng = self.engine(params, R)
-        if eng.program.grad_unsupported:          # before the B x n_weights allocation
-            raise NotImplementedError(f'log_psi_jacobian: unsupported for this program ({eng.program.grad_unsupported})')
+        self._per_walker_check('log_psi_jacobian', eng)          # before the B x n_weights allocation
         sign, log, J = eng.log_psi_jacobian(r, R)
         Jp = eng.program.unflatten_jacobian(J)
         del J
@@ -232,8 +252,7 @@ class NeuralNetworkWaveFunction:
         r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
         R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
         eng = self.engine(params, R)
-        if eng.program.grad_unsupported:
-            raise NotImplementedError(f'log_psi_kfac: unsupported for this program ({eng.program.grad_unsupported})')
+        self._per_walker_check('log_psi_kfac', eng)
         sign, log, g, factors, rest = eng.log_psi_kfac(r, cotangent, R)
         return Psi(sign, log), eng.program.unflatten_grad(g), factors, rest
 
@@ -245,7 +264,6 @@ class NeuralNetworkWaveFunction:
         r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
         R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
         eng = self.engine(params, R)
-        if eng.program.grad_unsupported:
-            raise NotImplementedError(f'log_psi_grad_coords: unsupported for this program ({eng.program.grad_unsupported})')
+        self._per_walker_check('log_psi_grad_coords', eng)
         sign, log, gr, gR = eng.log_psi_grad_coords(r, R)
         return Psi(sign, log), gr, gR

@@ -173,6 +173,45 @@ int dqmc_set_weights(dqmc_ctx* ctx, const double* weights_host, size_t n_weights
  * copy of, -1 for a constant or padding (Program.grad_src).  Builds the device tables of the re-packers; a setup call (it
  * synchronises).  DQMC_E_ARG for n_weights other than the context's or an entry outside [-1, n_params). */
 int dqmc_set_param_map(dqmc_ctx* ctx, const int32_t* src_host, size_t n_weights, size_t n_params);
+/* ---- The nuclear-token stream on the device (TransPsiformer; option "nuclear_reverse") ----
+ * The nuclear tokens of an ansatz with DQMC_OP_ATTENTION constant rows attend to each other only: their stream (nuclei embedding,
+ * per layer token attention + MLP, the envelope head) depends on theta and on the geometry, not on the electrons, and reaches
+ * the layer program as constants of the weight buffer (the key / value rows of every ATTENTION op, the zeta tables of the
+ * simplified envelopes).  dqmc_set_weights receives them folded on the host.  With a stream registered the library evaluates
+ * the same fold on the device, in float64 whatever the context's precision, and owns its transpose:
+ *   dqmc_weights_from_params  also folds theta -> derived vector, scatters it into the constant entries (rounded to the context's
+ *                             precision; the double copy and the float64 twin get the doubles), then re-packs as before
+ *   dqmc_grad_to_params       also gathers the adjoints of the derived vector from the constant entries of grad_w (ascending
+ *                             entry order) and ADDS the stream's parameter gradients into grad_theta
+ * Invariant: constants and the activations the transpose reads are always written together by the same fold; after a
+ * dqmc_set_weights (host fold) dqmc_grad_to_params answers DQMC_E_ARG until the next dqmc_weights_from_params.
+ *
+ * The derived vector: per layer K_nuc then V_nuc [n_nuc][dim]; then, with n_env > 0, zetas up and zetas down [n_nuc][n_det][n_env].
+ * lin: the stream's linear layers y = act(x w + b) as offsets into theta (w [n_in][n_out] row-major, b -1: none; act 0 none,
+ * 1 tanh, 2 silu), in the order: edge MLP (n_edge_lin; input 4 + n_nuc features), embed MLP (n_embed_lin), per layer query, key,
+ * value, linear, then the MLP (n_mlp_lin; the output projection and the MLP carry the residuals of nuclear_stream.fold), and with
+ * n_env > 0 the GLU readouts W_up, V_up, W_down, V_down; zbias_up / zbias_down: offsets of zetas_bias_* [n_nuc][n_det][n_env].
+ * sc_row / sc_col: CSR over the derived elements of the weight entries that are copies of each (entries the parameter map marks
+ * -1).  theta: the current parameters (the call folds them once, so that constants and activations agree from the start).
+ * All pointers are host memory.  A setup call: it synchronises and allocates everything the stream will ever need; it needs
+ * dqmc_set_param_map first.  DQMC_E_ARG for tables that are inconsistent with the program or out of range. */
+typedef struct dqmc_nuc_linear {
+  int64_t w, b;
+  int32_t n_in, n_out, act, reserved;
+} dqmc_nuc_linear;
+typedef struct dqmc_nuc_stream {
+  int32_t n_nuc, n_layers, heads, dim, n_det, n_env;
+  int32_t n_edge_lin, n_embed_lin, n_mlp_lin, n_lin;
+  const dqmc_nuc_linear* lin;
+  int64_t zbias_up, zbias_down;
+  const int32_t* nuc_types;   /* [n_nuc] atom type of every nucleus (column of the one-hot edge feature) */
+  const double* R;            /* [n_nuc][3] the geometry the context was compiled for */
+  int64_t n_derived;
+  const int64_t* sc_row;      /* [n_derived + 1] */
+  const int32_t* sc_col;
+  const double* theta;        /* [n_params] */
+} dqmc_nuc_stream;
+int dqmc_set_nuclear_stream(dqmc_ctx* ctx, const dqmc_nuc_stream* desc_host);
 /* w[j] = theta[src[j]] where src[j] >= 0; the other entries keep the value of creation / the last dqmc_set_weights.  From
  * those doubles everything dqmc_set_weights refreshes is refreshed in place on the device -- the weights in the context's
  * precision, the float64 twin's (a twin created later starts from the current values), the weight tape of a generated
@@ -245,7 +284,8 @@ int dqmc_kfac_direction(dqmc_ctx* ctx, const double* grad_theta, const double* f
 int dqmc_kfac_apply(dqmc_ctx* ctx, double* theta, const double* delta, const double* dot, double lr, double norm_constraint,
                     double* norms4);
 /* Test access to the weight buffers.  which: 0 = the flat weights in the context's precision, 1 = the weight tape of the
- * generated sub-step kernel, 2 = the packed planes of the fused kernel, 3 = the flat weights of the float64 twin.
+ * generated sub-step kernel, 2 = the packed planes of the fused kernel, 3 = the flat weights of the float64 twin, 4 = the
+ * double copy of the flat weights a float32 context keeps once a parameter map is set.
  * out_host NULL: returns the size of the buffer in bytes (> 0).  Otherwise `bytes` must be exactly that size (DQMC_E_ARG);
  * DQMC_E_UNSUPPORTED when the context has no such buffer.  Synchronises the stream. */
 int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t bytes);
@@ -377,7 +417,13 @@ int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logp
  * walker sums run in a fixed order, so two identical calls give bit-identical results.
  * DQMC_E_UNSUPPORTED for programs with ATTENTION ops (Psiformer, TransPsiformer) unless option "attention_reverse" is 1
  * (dqmc_set_option); with it, only ATTENTION ops with constant key / value rows (n_const > 0, the TransPsiformer's nuclear
- * tokens) stay refused.  The same gate holds for every entry point that runs this reverse pass. */
+ * tokens) stay refused.  The same gate holds for every entry point that runs this reverse pass.
+ * Option "nuclear_reverse" 1 (it needs dqmc_set_nuclear_stream; values other than 0 / 1 and a missing stream: DQMC_E_ARG) admits
+ * the constant rows in the calls that sum partials over the walkers -- dqmc_log_psi_vjp, dqmc_orbitals_vjp,
+ * dqmc_pretrain_loss_grad: grad then also carries the walker-summed gradient of the constant key / value rows and of the
+ * folded zeta tables, which dqmc_grad_to_params takes back through the nuclear stream.  The per-walker calls
+ * (dqmc_log_psi_jacobian, dqmc_log_psi_kfac, dqmc_log_psi_grad_coords, dqmc_ecp_force, dqmc_set_kfac_map) keep answering
+ * DQMC_E_UNSUPPORTED for such programs: the stream is shared by all walkers and has no per-walker partials. */
 int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot,
                      double* grad, void* logpsi, int32_t* sign);
 
