@@ -65,6 +65,7 @@ SIGNATURES = [
                                     c_double, c_void_p, c_void_p]),
     ('dqmc_kfac_apply', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p]),
     ('dqmc_debug_read_weights', c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    ('dqmc_debug_nuc_dx_time', c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     ('dqmc_graph_counters', c_int, [c_void_p, POINTER(c_int64)]),
     ('dqmc_psi_ratio', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     ('dqmc_clip_rows', c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p]),

@@ -167,6 +167,7 @@ struct dqmc_ctx {
                              double* state, int first, double ema, double damping, double* delta, double* dot) = 0;
   virtual int kfac_apply(double* theta, const double* delta, const double* dot, double lr, double norm_constraint, double* norms4) = 0;
   virtual int debug_read_weights(int which, void* out, size_t bytes) = 0;
+  virtual int debug_nuc_dx_time(int B, int reps, double* ms2, int* shape3) = 0;
   virtual void graph_counters(int64_t* out2) = 0;
   virtual int psi_ratio(const double* lg, const double* sg, int S, long B, double* ratio) = 0;
   virtual int clip_rows(const double* x, const double* w, int n_rows, long B, int center, int scale, double clip_width,
@@ -704,6 +705,11 @@ int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t byt
   if (!ctx) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->debug_read_weights(which, out_host, bytes);
+}
+int dqmc_debug_nuc_dx_time(dqmc_ctx* ctx, int B, int reps, double* ms2, int* shape3) {
+  if (!ctx || !ms2 || !shape3) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->debug_nuc_dx_time(B, reps, ms2, shape3);
 }
 int dqmc_graph_counters(dqmc_ctx* ctx, int64_t* out2) {
   if (!ctx || !out2) return fail(DQMC_E_ARG, "null argument");

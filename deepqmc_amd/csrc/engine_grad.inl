@@ -11,26 +11,30 @@
   // "attention_reverse" is on, and whatever the option when an ATTENTION op has constant key / value rows (the nuclear tokens
   // of the TransPsiformer are folded on the host from parameters and R: their adjoints have nowhere to go).
   // With option "nuclear_reverse" and a registered nuclear stream (engine_nuc.inl) the constant rows are admitted by the calls
-  // that sum their partials over the walkers (per_walker false: the Vjp and Orbs modes).  Every other mode would need one nuclear
-  // backward per walker and keeps refusing.  0: runs, 1: no reverse pass for ATTENTION ops, 2: nuclear tokens, per-walker mode.
-  int attention_refusal(bool per_walker) const {
+  // that sum their partials over the walkers (per_walker false: the Vjp and Orbs modes).  With option "nuclear_coords" as well
+  // the Coords mode is admitted (coords true: it needs per-walker ADJOINTS of the stream only, nuc_fold_coords).  Every other
+  // mode would need the stream's parameter partials per walker and keeps refusing, as do dqmc_set_kfac_map and dqmc_ecp_force.
+  // 0: runs, 1: no reverse pass for ATTENTION ops, 2: nuclear tokens, per-walker mode.
+  int attention_refusal(bool per_walker, bool coords = false) const {
     for (const auto& o : ops)
       if (o.kind == DQMC_OP_ATTENTION) {
         if (!attention_reverse) return 1;
         if (dqmc::AttentionOp(o).n_const() > 0) {
           if (!nuclear_reverse || !nuc_set) return 1;
-          if (per_walker) return 2;
+          if (per_walker && !(coords && nuclear_coords)) return 2;
         }
       }
     return 0;
   }
-  bool attention_refused(bool per_walker = true) const { return attention_refusal(per_walker) != 0; }
-  std::string attention_refusal_text(bool per_walker) const {
-    return attention_refusal(per_walker) == 2
+  bool attention_refused(bool per_walker = true, bool coords = false) const { return attention_refusal(per_walker, coords) != 0; }
+  std::string attention_refusal_text(bool per_walker, bool coords = false) const {
+    return attention_refusal(per_walker, coords) == 2
                ? "the nuclear-token stream has no per-walker partials (all walkers share it: one nuclear backward per walker); only "
                  "log_psi_vjp, orbitals_vjp and pretrain_loss_grad run with nuclear tokens"
                : "no reverse pass for ATTENTION ops";
   }
+  // the Coords mode carries the stream's part into grad_R: constant rows, option "nuclear_coords", grad_R requested
+  bool nuc_coords_active(bool want_R) const { return want_R && nuclear_coords && nuclear_reverse && nuc_set && grad_att_const() > 0; }
   size_t grad_att_const() const {      // largest n_const * heads * head_dim of an ATTENTION op
     size_t m = 0;
     for (const auto& o : ops)

@@ -11,6 +11,8 @@
 // envelope head, the layers in reverse -- layer l's K / V adjoints enter at that layer's key / value projections -- the embed
 // MLP, the sender sum and the edge MLP, ADDING parameter gradients into grad_theta.  No adjoint of R.  Everything runs on the
 // context's stream in a fixed order without atomics, allocates nothing and never waits for the host.
+// With option "nuclear_coords" nuc_fold_coords runs the same chain once more for the Coords mode of the reverse pass: batched
+// over the walkers of a chunk, adjoints only, and one step further, through the edge features into R (the end of this file).
 //
 // INVARIANT: constants and activations are always written together, by the same fold (weights_from_params: fold, scatter into
 // d_w / d_w64, re-pack), and the fold keeps its own copy of the theta it ran on (the backward reads the weights from it).
@@ -19,7 +21,9 @@
 
   struct NucLin { long w, b; int n_in, n_out, act; size_t z, y; };   // theta offsets (b -1: none); nuc_act offsets of Z and Y (act 0: the same)
   int nuclear_reverse = 0;       // option: the reverse pass admits constant key / value rows in the Vjp and Orbs modes
+  int nuclear_coords = 0;        // option: the Coords mode admits them too and carries the stream's part of d log|psi| / dR (nuc_fold_coords)
   bool nuc_set = false, nuc_fresh = false;
+  std::map<std::pair<long, long>, std::pair<long, long>> nuc_range_of;      // weight range -> derived elements with a copy in it
   int nuc_n = 0, nuc_L = 0, nuc_H = 0, nuc_D = 0, nuc_K = 0, nuc_ne = 0, nuc_n_edge = 0, nuc_n_embed = 0, nuc_n_mlp = 0;
   long nuc_zbias[2] = {-1, -1};
   std::vector<NucLin> nuc_lin;
@@ -100,6 +104,7 @@
     nuc_n_edge = d->n_edge_lin; nuc_n_embed = d->n_embed_lin; nuc_n_mlp = d->n_mlp_lin;
     nuc_zbias[0] = d->zbias_up; nuc_zbias[1] = d->zbias_down;
     nuc_n_derived = n_derived;
+    nuc_range_of.clear();
     // the arena: derived vector first, then the activations
     size_t at = n_derived;
     auto take = [&](size_t m) { const size_t o = at; at += m; return o; };
@@ -235,4 +240,161 @@
     dqmc::launch_nuc_sender_sum_bwd(st, g + nuc_o_esum, g + nuc_lin[nuc_n_edge - 1].y, n, nuc_lin[nuc_n_edge - 1].n_out);
     for (int e = nuc_n_edge; e-- > 0;)
       nuc_linear_bwd(nuc_lin[e], e ? nuc_lin[e - 1].y : nuc_o_F, e > 0, n * n, -1, grad_theta);      // (the features have no adjoint: no dR)
+  }
+
+  // ---- option "nuclear_coords": the same transpose per walker, adjoints only, carried one step further into R ----
+  // The Coords mode of the reverse pass (engine_reverse.inl) keeps the per-walker partials of the constant key / value rows and
+  // of the zeta tables instead of dropping them: nuc_gather_partials sums each walker's partials over the copies of a derived
+  // element into the head of that walker's adjoint arena G + b * nuc_arena (double, chunk workspace, zeroed by the caller; laid
+  // out like nuc_adj, so nuc_lin[q].z / .y address walker b's dZ / dY of stream layer q for the lifetime of the chunk).
+  // nuc_fold_coords then runs nuc_fold_vjp's chain on all arenas at once -- no parameter gradient, the number of launches does
+  // not depend on B -- and adds the edge features' adjoint into grad_R at the registered geometry d_nuc_R.
+
+  // derived elements [lo, hi) that have a copy among the weight entries [w0, w0 + len) (host tables; kept per range)
+  std::pair<long, long> nuc_derived_range(long w0, long len) {
+    const auto key = std::make_pair(w0, len);
+    const auto it = nuc_range_of.find(key);
+    if (it != nuc_range_of.end()) return it->second;
+    long lo = (long)nuc_n_derived, hi = 0;
+    for (long e = 0; e < (long)nuc_n_derived; ++e)
+      for (int64_t k = nuc_row_h[e]; k < nuc_row_h[e + 1]; ++k)
+        if (nuc_col_h[k] >= w0 && nuc_col_h[k] < w0 + len) { lo = std::min(lo, e); hi = std::max(hi, e + 1); }
+    if (hi < lo) lo = hi = 0;
+    return nuc_range_of[key] = std::make_pair(lo, hi);
+  }
+  // src[b * stride + m], m < len: walker b's partials of the weight entries w0 + m
+  template <class T> void nuc_gather_partials(const T* src, long stride, long len, long w0, double* G, int B) {
+    const auto range = nuc_derived_range(w0, len);
+    dqmc::launch_nucb_gather<T>(st, src, stride, w0, len, d_nuc_row, d_nuc_col, range.first, range.second, G, (long)nuc_arena, B);
+  }
+  // every linear layer's W panel must fit the LDS of k_nucb_dx, the token attention's dS tile that of k_nucb_attention_bwd
+  bool nuc_coords_fits() const {
+    for (size_t q = 0; q < nuc_lin.size(); ++q)
+      if (!dqmc::nucb_dx_col_tiles(q == 0 ? 4 : nuc_lin[q].n_in, nuc_lin[q].n_out)) return false;
+    return dqmc::nucb_attention_bwd_lds_bytes(nuc_n) <= (size_t)160 * 1024;
+  }
+  int nuc_coords_linear(double* G, const double* T, int B, const NucLin& m, size_t x_off, int rows, long res_off, int k_cols) {
+    const long A = (long)nuc_arena;
+    if (res_off >= 0) dqmc::launch_nucb_add(st, G + res_off, G + m.y, (long)rows * m.n_out, A, B);
+    return dqmc::launch_nucb_dx(st, G + m.y, m.act ? T + m.z : nullptr, d_nuc_theta + m.w, G + m.z, G + x_off, rows, B, m.n_in, m.n_out,
+                                k_cols, A);
+  }
+  // T[nuc_lin[q].z ..] = act'(Z) of every activated layer q (T: nuc_arena doubles, shared by the walkers)
+  void nuc_dact_table(double* T) {
+    std::vector<int> act;
+    std::vector<long> z, cnt;
+    for (size_t q = 0; q < nuc_lin.size(); ++q)
+      if (nuc_lin[q].act) {
+        act.push_back(nuc_lin[q].act); z.push_back((long)nuc_lin[q].z);
+        cnt.push_back(((int)q < nuc_n_edge ? (long)nuc_n * nuc_n : (long)nuc_n) * nuc_lin[q].n_out);
+      }
+    dqmc::launch_nucb_dact(st, d_nuc_act, T, act.data(), z.data(), cnt.data(), (int)act.size());
+  }
+  // G: the walkers' adjoint arenas, T: nuc_arena doubles of scratch; lp, sg [B]: rows of walkers with sign 0 or a non-finite
+  // log|psi| stay as they are (zero)
+  int nuc_fold_coords(double* G, double* T, int B, const real* lp, const int32_t* sg, real* grad_R) {
+    const double* a = d_nuc_act;
+    const int n = nuc_n, D = nuc_D;
+    const long A = (long)nuc_arena;
+    int rc = 0;
+    nuc_dact_table(T);
+    auto lin = [&](const NucLin& m, size_t x_off, int rows, long res_off, int k_cols) {
+      if (!rc) rc = nuc_coords_linear(G, T, B, m, x_off, rows, res_off, k_cols);
+    };
+    std::vector<size_t> h_off(nuc_L + 1);
+    h_off[0] = nuc_lin[nuc_lin_layer0() - 1].y;
+    for (int l = 0; l < nuc_L; ++l) h_off[l + 1] = nuc_lin[nuc_lin_layer0() + (l + 1) * (4 + nuc_n_mlp) - 1].y;
+    if (nuc_ne) {
+      int q = nuc_lin_head0();
+      for (int s = 0; s < 2; ++s, q += 2) {
+        dqmc::launch_nucb_glu_bwd(st, a + nuc_lin[q].y, a + nuc_lin[q + 1].y, G + nuc_zeta_off(s), G + nuc_lin[q].y, G + nuc_lin[q + 1].y,
+                                  (long)n * nuc_K * nuc_ne, A, B);
+        lin(nuc_lin[q], nuc_o_ln, n, -1, D);
+        lin(nuc_lin[q + 1], nuc_o_ln, n, -1, D);
+      }
+      dqmc::launch_nucb_layernorm_bwd(st, a + nuc_o_ln, a + nuc_o_rstd, G + nuc_o_ln, G + h_off[nuc_L], n, D, A, B);
+    }
+    for (int l = nuc_L; l-- > 0;) {
+      const int q0 = nuc_lin_layer0() + l * (4 + nuc_n_mlp);
+      const size_t att = nuc_lin[q0 + 3].y;
+      for (int e = nuc_n_mlp; e-- > 0;)
+        lin(nuc_lin[q0 + 4 + e], e ? nuc_lin[q0 + 4 + e - 1].y : att, n, e == nuc_n_mlp - 1 ? (long)att : -1, nuc_lin[q0 + 4 + e].n_in);
+      lin(nuc_lin[q0 + 3], nuc_o_o[l], n, (long)h_off[l], D);
+      dqmc::launch_nucb_attention_bwd(st, a + nuc_lin[q0].y, a + nuc_lin[q0 + 1].y, a + nuc_lin[q0 + 2].y, a + nuc_o_P[l], G + nuc_o_o[l],
+                                      G + nuc_lin[q0].y, G + nuc_lin[q0 + 1].y, G + nuc_lin[q0 + 2].y, n, nuc_H, D / nuc_H, A, B);
+      for (int p = 0; p < 3; ++p) lin(nuc_lin[q0 + p], h_off[l], n, -1, D);
+    }
+    for (int e = nuc_n_embed; e-- > 0;) {
+      const int q = nuc_n_edge + e;
+      lin(nuc_lin[q], e ? nuc_lin[q - 1].y : nuc_o_esum, n, -1, nuc_lin[q].n_in);
+    }
+    dqmc::launch_nucb_sender_sum_bwd(st, G + nuc_o_esum, G + nuc_lin[nuc_n_edge - 1].y, n, nuc_lin[nuc_n_edge - 1].n_out, A, B);
+    for (int e = nuc_n_edge; e-- > 0;)      // (of the features only the four columns of d carry an adjoint)
+      lin(nuc_lin[e], e ? nuc_lin[e - 1].y : nuc_o_F, n * n, -1, e ? nuc_lin[e].n_in : 4);
+    if (rc) return rc == -1 ? fail(DQMC_E_UNSUPPORTED, "log_psi_grad_coords: a stream layer's weight panel exceeds the LDS")
+                            : fail(DQMC_E_HIP, "nuclear-stream backward launch failed");
+    dqmc::launch_nucb_edge_feat_bwd<real>(st, d_nuc_R, sys.norm_eps, G + nuc_o_F, n, A, lp, sg, grad_R, B);
+    return DQMC_OK;
+  }
+
+  // dqmc_debug_nuc_dx_time (tools/nuclear_coords_time.py): the batched dX kernel against launch_linear_bwd<double> (dX only:
+  // k_lin_dz, k_lin_dx) on the largest linear layer of the stream's token rows, B walkers, the layer's own weights and
+  // pre-activations.  The two alternate `reps` times after a warm-up round; ms2 = their median times, shape3 = {B n, n_in, n_out}.
+  int debug_nuc_dx_time(int B, int reps, double* ms2, int* shape3) override {
+    if (!nuc_set || !nuc_fresh) return fail(DQMC_E_ARG, "dqmc_debug_nuc_dx_time: no folded nuclear stream");
+    if (B < 1 || reps < 1) return fail(DQMC_E_ARG, "dqmc_debug_nuc_dx_time: B and reps must be positive");
+    int best = nuc_lin_layer0();
+    for (int q = best; q < nuc_lin_head0(); ++q) {
+      const long sz = (long)nuc_lin[q].n_in * nuc_lin[q].n_out, sb = (long)nuc_lin[best].n_in * nuc_lin[best].n_out;
+      if (sz > sb || (sz == sb && nuc_lin[q].act && !nuc_lin[best].act)) best = q;
+    }
+    const NucLin& m = nuc_lin[best];
+    if (m.n_out % 4) return fail(DQMC_E_UNSUPPORTED, "dqmc_debug_nuc_dx_time: the reference kernel needs n_out % 4 == 0");
+    const int n = nuc_n;
+    const size_t ny = (size_t)B * n * m.n_out, nx = (size_t)B * n * m.n_in;
+    const size_t A = (size_t)n * std::max(m.n_in, m.n_out);      // the walker stride of the batched kernel's three buffers
+    { const int rc = grad_ws_reserve(sizeof(double) * (3 * ny + nx + 3 * (size_t)B * A + (size_t)n * m.n_out)); if (rc) return rc; }
+    double* Y = reinterpret_cast<double*>(g_ws.p);
+    double *Zb = Y + ny, *dZ = Zb + ny, *X2 = dZ + ny, *Y1 = X2 + nx, *dZ1 = Y1 + (size_t)B * A, *X1 = dZ1 + (size_t)B * A, *T1 = X1 + (size_t)B * A;
+    for (int b = 0; b < B; ++b) {      // dY of both and the reference's per-walker Z: the layer's pre-activations
+      const size_t bytes = sizeof(double) * n * m.n_out;
+      HIP_TRY(hipMemcpyAsync(Y + (size_t)b * n * m.n_out, d_nuc_act + m.z, bytes, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(Zb + (size_t)b * n * m.n_out, d_nuc_act + m.z, bytes, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(Y1 + (size_t)b * A, d_nuc_act + m.z, bytes, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipMemsetAsync(X2, 0, sizeof(double) * nx, st));
+    HIP_TRY(hipMemsetAsync(X1, 0, sizeof(double) * B * A, st));
+    dqmc::LinBwdArgs<double> a{};
+    a.n_pieces = 1;
+    a.piece[0].X = nullptr; a.piece[0].dX = X2; a.piece[0].ld = m.n_in; a.piece[0].rpw = n; a.piece[0].r0 = 0; a.piece[0].K = m.n_in;
+    a.piece[0].bcast = 0; a.piece[0].w_row = 0;
+    a.W = d_nuc_theta + m.w; a.ldw = m.n_out; a.nout = m.n_out; a.nrows = n; a.B = B; a.act = m.act;
+    a.Z = Zb; a.dZ = dZ; a.dZs = nullptr; a.dY = Y; a.ld_dst = m.n_out; a.rpw_dst = n; a.r0_dst = 0; a.col0_dst = 0;
+    const long zero = 0, tn = (long)n * m.n_out;
+    std::vector<hipEvent_t> ev(3 * (size_t)(reps + 1));
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    int rc = 0;
+    for (int k = 0; k <= reps && !rc; ++k) {
+      (void)hipEventRecord(ev[3 * k], st);
+      if (m.act) dqmc::launch_nucb_dact(st, d_nuc_act + m.z, T1, &m.act, &zero, &tn, 1);      // (per call, not per layer: timed all the same)
+      rc = dqmc::launch_nucb_dx(st, Y1, m.act ? T1 : nullptr, d_nuc_theta + m.w, dZ1, X1, n, B, m.n_in, m.n_out, m.n_in, (long)A);
+      (void)hipEventRecord(ev[3 * k + 1], st);
+      dqmc::launch_linear_bwd<double>(st, a);
+      (void)hipEventRecord(ev[3 * k + 2], st);
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<double> t1, t2;
+    for (int k = 1; k <= reps; ++k) {      // (round 0 is the warm-up)
+      float x = 0, y = 0;
+      (void)hipEventElapsedTime(&x, ev[3 * k], ev[3 * k + 1]);
+      (void)hipEventElapsedTime(&y, ev[3 * k + 1], ev[3 * k + 2]);
+      t1.push_back(x); t2.push_back(y);
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    if (rc) return fail(DQMC_E_UNSUPPORTED, "dqmc_debug_nuc_dx_time: the layer's weight panel exceeds the LDS");
+    std::sort(t1.begin(), t1.end()); std::sort(t2.begin(), t2.end());
+    ms2[0] = t1[t1.size() / 2]; ms2[1] = t2[t2.size() / 2];
+    shape3[0] = B * n; shape3[1] = m.n_in; shape3[2] = m.n_out;
+    HIP_TRY(hipGetLastError());
+    return DQMC_OK;
   }

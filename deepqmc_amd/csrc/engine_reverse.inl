@@ -79,12 +79,14 @@
   // Walkers per chunk under ws_budget: the workspace of grad_chunk per walker, and the part that does not grow with the chunk.
   // The modes differ on purpose (Coords reserves nothing for the split-K partials it never allocates).  Chunk boundaries fix
   // the order in which chunks add into grad and factors, so a change here moves results in the last bits.
-  long rev_chunk_len(Rev mode, int B) const {
+  // nuc: the Coords mode also carries the nuclear stream's part into grad_R (nuc_coords_active): one adjoint arena per walker
+  // (the table partials pw are part of grad_bytes_per_walker in every mode).
+  long rev_chunk_len(Rev mode, int B, bool nuc = false) const {
     size_t per = ws_bytes_per_walker(1) + grad_bytes_per_walker(), fixed = 0;
     switch (mode) {
       case Rev::Vjp: case Rev::Jac: fixed = grad_part_bytes(); break;
       case Rev::Kfac: per += 2 * sizeof(double); fixed = grad_part_bytes() + kfac_part_bytes(); break;
-      case Rev::Coords: per += sizeof(double) * 3 * (size_t)c_n_slots; break;
+      case Rev::Coords: per += sizeof(double) * (3 * (size_t)c_n_slots + (nuc ? nuc_arena : 0)); fixed = nuc ? sizeof(double) * nuc_arena : 0; break;
       case Rev::Orbs: per += pt_target_bytes_per_walker(); fixed = grad_part_bytes(); break;
     }
     const long chunk = per ? (long)((ws_budget > fixed ? ws_budget - fixed : 0) / per) : B;
@@ -96,11 +98,17 @@
     const std::string name = rev_name(q.mode);
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
     const bool per_walker = q.mode != Rev::Vjp && q.mode != Rev::Orbs;
-    if (attention_refused(per_walker)) return fail(DQMC_E_UNSUPPORTED, name + ": " + attention_refusal_text(per_walker));
+    const bool coords = q.mode == Rev::Coords;
+    if (attention_refused(per_walker, coords)) return fail(DQMC_E_UNSUPPORTED, name + ": " + attention_refusal_text(per_walker, coords));
+    const bool nuc = coords && nuc_coords_active(q.grad_R != nullptr);
+    if (nuc && !nuc_fresh)
+      return fail(DQMC_E_ARG, name + ": the nuclear stream's activations are older than the weights (dqmc_set_weights since the last "
+                                     "dqmc_weights_from_params)");
+    if (nuc && !nuc_coords_fits()) return fail(DQMC_E_UNSUPPORTED, name + ": a nuclear-stream layer's weight panel exceeds the LDS");
     if (q.mode != Rev::Orbs && N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, name + ": more than 64 electrons");   // (Orbs forms no inverse)
     { const int rc = grad_tables(); if (rc) return rc; }
     if (q.mode == Rev::Orbs) { const int rc = orb_tables(); if (rc) return rc; }
-    const long chunk = rev_chunk_len(q.mode, B);
+    const long chunk = rev_chunk_len(q.mode, B, nuc);
     last_chunks[0] = chunk >= B ? 1 : (int)((B + chunk - 1) / chunk);
     const UnfusedForward unfused(*this);
     for (int b0 = 0; b0 < B; b0 += (int)chunk) {
@@ -114,6 +122,7 @@
 
   int grad_chunk(const real* r, const real* R, int B, const RevReq& q) {
     const bool jac = q.mode == Rev::Jac, kfac = q.mode == Rev::Kfac, coords = q.mode == Rev::Coords, orbs = q.mode == Rev::Orbs;
+    const bool nuc = coords && nuc_coords_active(q.grad_R != nullptr);      // the stream's part of grad_R (engine_nuc.inl: nuc_fold_coords)
     // adjoint workspace of this chunk
     std::vector<size_t> adj(bufs.size());
     Slab slab;
@@ -121,7 +130,7 @@
     const size_t adj_end = slab.bytes;
     const size_t o_z = slab.take_bytes(sizeof(real) * (size_t)B * grad_zrow()), o_dz = slab.take_bytes(sizeof(real) * (size_t)B * grad_zrow());
     const size_t o_dzs = slab.take_bytes(sizeof(real) * (size_t)B * max_ldw());
-    const size_t o_orb = slab.take_bytes(sizeof(double) * (size_t)B * (!coords && grad_orb_partials() ? grad_orb_partials() : 1));
+    const size_t o_orb = slab.take_bytes(sizeof(double) * (size_t)B * ((!coords || nuc) && grad_orb_partials() ? grad_orb_partials() : 1));
     const size_t o_dl = slab.take_bytes(sizeof(double) * (size_t)B * sys.n_det), o_pw = slab.take_bytes(sizeof(double) * (size_t)B * (sys.n_det + 2));
     const size_t o_lp = slab.take_bytes(sizeof(real) * (size_t)B), o_sg = slab.take_bytes(sizeof(int32_t) * (size_t)B);
     const size_t o_part = slab.take_bytes(coords ? 0 : grad_part_bytes());
@@ -129,8 +138,12 @@
     const size_t o_slot = slab.take_bytes(coords ? sizeof(double) * 3 * (size_t)B * c_n_slots : 0);
     const size_t o_tgt = slab.take_bytes(orbs && !q.cot_orb ? (size_t)B * pt_target_bytes_per_walker() : 0);
     const size_t o_cpart = slab.take_bytes(sizeof(real) * (size_t)B * 2 * grad_att_const());      // (nuclear tokens: [B][2][n_const][H * hd])
+    const size_t o_nuc = slab.take_bytes(nuc ? sizeof(double) * (size_t)B * nuc_arena : 0);      // [B][nuc_arena] adjoint arenas
+    const size_t o_nucT = slab.take_bytes(nuc ? sizeof(double) * nuc_arena : 0);                 // act'(Z) of the stream's layers
     { const int rc = grad_ws_reserve(slab.bytes); if (rc) return rc; }
     char* gw = g_ws;
+    double* nucG = nuc ? reinterpret_cast<double*>(gw + o_nuc) : nullptr;
+    if (nuc) HIP_TRY(hipMemsetAsync(nucG, 0, sizeof(double) * (size_t)B * nuc_arena, st));
     auto A = [&](int b) { return reinterpret_cast<real*>(gw + adj[b]); };
     real* lp = q.logpsi ? q.logpsi : reinterpret_cast<real*>(gw + o_lp);
     int32_t* sg = q.sign ? q.sign : reinterpret_cast<int32_t*>(gw + o_sg);
@@ -166,7 +179,9 @@
     auto emit_partials = [&](const auto* src, long stride, int n, long w_off) {
       using T = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
       switch (q.mode) {
-        case Rev::Coords: return;
+        case Rev::Coords:      // no parameter partials; the nuclear stream's outputs keep theirs per walker
+          if (nuc) nuc_gather_partials(src, stride, (long)n, w_off, nucG, B);
+          return;
         case Rev::Jac: dqmc::launch_jac_scatter<T, real>(st, src, stride, n, B, jo, w_off); return;
         case Rev::Kfac:
           if (q.rest) dqmc::launch_jac_scatter<T, real>(st, src, stride, n, B, ko, k_rest_pos[w_off]);
@@ -278,7 +293,7 @@
           double* pw = reinterpret_cast<double*>(gw + o_orb);
           t_begin("orbitals_bwd", 0);
           dqmc::launch_orbitals_bwd<real>(st, r, R, bptr(o.src()), bufs[o.src()].width, A(o.src()), A(o.dst()), bufs[o.dst()].width, d_w + o.w(0),
-                                          d_w + o.w(1), d_w + o.w(2), d_w + o.w(3), coords ? nullptr : pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det,
+                                          d_w + o.w(1), d_w + o.w(2), d_w + o.w(3), coords && !nuc ? nullptr : pw, B, N, sys.n_up, n_env, sys.n_nuc, sys.n_det,
                                           sys.norm_eps);
           if (coords)
             dqmc::launch_orbitals_coords<real>(st, r, R, bptr(o.src()), bufs[o.src()].width, A(o.dst()), bufs[o.dst()].width, d_w + o.w(0),
@@ -323,6 +338,12 @@
     }
     if (coords)
       dqmc::launch_coords_gather<real>(st, slot, c_n_slots, c_tab, c_S, lp, sg, B, N, sys.n_nuc, q.grad_r, q.grad_R);
+    if (nuc) {
+      t_begin("nuc_coords", 0);
+      const int rc = nuc_fold_coords(nucG, reinterpret_cast<double*>(gw + o_nucT), B, lp, sg, q.grad_R);
+      t_end();
+      if (rc) return rc;
+    }
     HIP_TRY(hipGetLastError());
     return DQMC_OK;
   }

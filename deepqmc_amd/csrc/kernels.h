@@ -216,6 +216,35 @@ void launch_nuc_glu_bwd(hipStream_t st, const double* zw, const double* zv, cons
                         long n);
 template <typename real>
 void launch_nuc_scatter(hipStream_t st, const double* derived, const int32_t* row, const int32_t* col, real* w, double* w64, long n);
+// The stream's backward batched over walkers (option "nuclear_coords"; engine_nuc.inl: nuc_fold_coords): adjoints only.  Walker b's
+// adjoint arena is G + b * A, laid out like nuc_adj; pointers to adjoints point into walker 0's arena, activations are shared.
+// G[b][e] += walker b's partials src[b * stride + (col - w0)] over the copies of derived element e in [w0, w0 + len); e in [e_lo, e_hi)
+template <typename T>
+void launch_nucb_gather(hipStream_t st, const T* src, long stride, long w0, long len, const int32_t* row, const int32_t* col, long e_lo,
+                        long e_hi, double* G, long A, int B);
+void launch_nucb_add(hipStream_t st, double* a, const double* c, long n, long A, int B);
+void launch_nucb_glu_bwd(hipStream_t st, const double* zw, const double* zv, const double* dzeta, double* dzw, double* dzv, long n, long A,
+                         int B);
+void launch_nucb_layernorm_bwd(hipStream_t st, const double* ln, const double* rstd, const double* dln, double* dh, int n, int D, long A,
+                               int B);
+void launch_nucb_sender_sum_bwd(hipStream_t st, const double* dout, double* din, int n, int w, long A, int B);
+size_t nucb_attention_bwd_lds_bytes(int n);
+void launch_nucb_attention_bwd(hipStream_t st, const double* q, const double* k, const double* v, const double* P, const double* dO,
+                               double* dq, double* dk, double* dv, int n, int H, int hd, long A, int B);
+// table[z[j] + e] = act'(acts[z[j] + e]), e < n[j], for `count` activated layers (shared by the walkers: once per call)
+void launch_nucb_dact(hipStream_t st, const double* acts, double* table, const int* act, const long* z, const long* n, int count);
+// dX[m][i] += sum_o dY[m][o] dA[rr][o] W[i][o], i < k_cols <= n_in, rows m = (b, rr < rows), on the float64 MFMA with the W panel
+// in the LDS; dA = act'(Z) of the layer (launch_nucb_dact) or nullptr (no activation); with dA, writes dZ = dY act'(Z).
+// nucb_dx_col_tiles: 16-column tiles per workgroup, 0 if no panel fits the LDS (launch_nucb_dx then returns -1 without
+// launching; -2 on a HIP error)
+int nucb_dx_col_tiles(int k_cols, int n_out);
+size_t nucb_dx_lds_bytes(int ct, int n_out);
+int launch_nucb_dx(hipStream_t st, const double* dY, const double* dA, const double* W, double* dZ, double* dX, int rows, int B, int n_in,
+                   int n_out, int k_cols, long A);
+// the edge features' adjoint dF [B][n n][4 + n] carried into R and added into grad_R [B][n][3] (rows of invalid walkers are kept)
+template <typename real>
+void launch_nucb_edge_feat_bwd(hipStream_t st, const double* R, double eps, const double* dF, int n, long A, const real* lp, const int32_t* sg,
+                               real* grad_R, int B);
 
 // ---- kernel_attention_mfma.hip: contractions on MFMA, float32 and float64 (head_dim % 16 == 0, <= 64 queries / keys) ----
 template <typename real> size_t attention_mfma_lds_bytes(int N, int hd, int n_const);

@@ -6,6 +6,8 @@
 // MLP: small dedicated kernels, one thread per output element, every sum in ascending index order, no atomics.  Gradients
 // of parameters are ADDED into the caller's vector (the electron stream's gradient of the shared leaves is already there).
 // Activation codes as DQMC_OP_LINEAR: 0 none, 1 tanh, 2 silu.
+// The k_nucb_* kernels further down are the backward once more, batched over the walkers of a chunk of the coordinate reverse
+// pass (option "nuclear_coords"): adjoints only, rows B n or B n^2, the linear layers on the float64 MFMA.
 
 constexpr int NUC_BLOCK = 128;
 static inline unsigned nuc_grid(long n) { return (unsigned)((n + NUC_BLOCK - 1) / NUC_BLOCK); }
@@ -227,6 +229,241 @@ __global__ void __launch_bounds__(NUC_BLOCK) k_nuc_scatter(const double* __restr
   }
 }
 
+// ---- the stream's backward batched over walkers: adjoints only, down to R (engine_nuc.inl: nuc_fold_coords) ----
+// Every walker b has an adjoint arena of its own, G + b * A, laid out like nuc_adj (A = the arena's length); the activations
+// (Z, Y, P, ln, rstd) and the weights are the shared ones of the last fold.  Offsets into the arena are passed as pointers
+// into walker 0's arena.  One thread (or one wave tile) owns every element it adds into, sums run in ascending index order:
+// no atomics, two identical calls give identical bits.
+
+// G[b][e] += the sum of walker b's partials src[b * stride + (col - w0)] over the copies col of derived element e that lie in
+// the weight range [w0, w0 + len), in the order of the CSR table; e in [e_lo, e_hi)
+template <typename T>
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_gather(const T* __restrict__ src, long stride, long w0, long len,
+                                                           const int32_t* __restrict__ row, const int32_t* __restrict__ col, long e_lo,
+                                                           long e_hi, double* __restrict__ G, long A, long total) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  const long ne = e_hi - e_lo, b = idx / ne, e = e_lo + (idx - b * ne);
+  double s = 0.0;
+  for (int32_t k = row[e]; k < row[e + 1]; ++k) {
+    const long c = (long)col[k] - w0;
+    if (c >= 0 && c < len) s += (double)src[b * stride + c];
+  }
+  G[b * A + e] += s;
+}
+// a[b][e] += c[b][e], e < n
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_add(double* __restrict__ a, const double* __restrict__ c, long n, long A, long total) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  const long b = idx / n, e = idx - b * n;
+  a[b * A + e] += c[b * A + e];
+}
+// dzw = dzeta zv sig (1 - sig), dzv = dzeta sig (no bias gradient)
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_glu_bwd(const double* __restrict__ zw, const double* __restrict__ zv,
+                                                            const double* __restrict__ dzeta, double* __restrict__ dzw,
+                                                            double* __restrict__ dzv, long n, long A, long total) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  const long b = idx / n, e = idx - b * n;
+  const double s = nuc_sigmoid(zw[e]), g = dzeta[b * A + e];
+  dzw[b * A + e] = g * zv[e] * s * (1.0 - s);
+  dzv[b * A + e] = g * s;
+}
+// dh += rstd (dln - mean(dln) - ln mean(dln ln)); one thread per (walker, row)
+__global__ void __launch_bounds__(64) k_nucb_layernorm_bwd(const double* __restrict__ ln, const double* __restrict__ rstd,
+                                                           const double* __restrict__ dln, double* __restrict__ dh, int n, int D, long A,
+                                                           long total) {
+  const long idx = (long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= total) return;
+  const long b = idx / n;
+  const int r = (int)(idx - b * n);
+  const double* g = dln + b * A + (long)r * D;
+  const double* l = ln + (long)r * D;
+  double a = 0.0, c = 0.0;
+  for (int k = 0; k < D; ++k) { a += g[k]; c += g[k] * l[k]; }
+  a /= D; c /= D;
+  double* o = dh + b * A + (long)r * D;
+  for (int k = 0; k < D; ++k) o[k] += rstd[r] * (g[k] - a - l[k] * c);
+}
+// din[b][s n + r][c] += dout[b][r][c]
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_sender_sum_bwd(const double* __restrict__ dout, double* __restrict__ din, int n, int w,
+                                                                   long A, long total) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  const long per = (long)n * n * w, b = idx / per, e = idx - b * per;
+  din[b * A + e] += dout[b * A + e % ((long)n * w)];
+}
+// Token attention backward, one workgroup per (walker, head), thread t owns query row t and then key row t.  P is shared,
+// dO per walker: dS[t][:] = P (dP - sum P dP) with dP = dO v^T goes to the LDS ([n][n + 1] doubles), dq[t] += s dS k; after
+// the barrier dk[T] += s dS^T q, dv[T] += P^T dO.
+__global__ void __launch_bounds__(64) k_nucb_attention_bwd(const double* __restrict__ q, const double* __restrict__ k,
+                                                           const double* __restrict__ v, const double* __restrict__ P,
+                                                           const double* __restrict__ dO, double* __restrict__ dq, double* __restrict__ dk,
+                                                           double* __restrict__ dv, int n, int H, int hd, long A) {
+  HIP_DYNAMIC_SHARED(char, nucb_smem)
+  double* dS = reinterpret_cast<double*>(nucb_smem);
+  const long b = blockIdx.x / H;
+  const int h = blockIdx.x - (int)b * H, t = threadIdx.x, D = H * hd, c0 = h * hd, S = n + 1;
+  const double sc = 1.0 / sqrt((double)hd);
+  const double* dOb = dO + b * A;
+  if (t < n) {
+    const double* Pr = P + ((long)h * n + t) * n;
+    double* dSr = dS + t * S;
+    double m = 0.0;
+    for (int T = 0; T < n; ++T) {
+      double p = 0.0;
+      for (int d = 0; d < hd; ++d) p += dOb[(long)t * D + c0 + d] * v[(long)T * D + c0 + d];
+      dSr[T] = p;
+      m += Pr[T] * p;
+    }
+    for (int T = 0; T < n; ++T) dSr[T] = Pr[T] * (dSr[T] - m);
+    for (int d = 0; d < hd; ++d) {
+      double a = 0.0;
+      for (int T = 0; T < n; ++T) a += dSr[T] * k[(long)T * D + c0 + d];
+      dq[b * A + (long)t * D + c0 + d] += sc * a;
+    }
+  }
+  __syncthreads();
+  if (t < n) {
+    for (int d = 0; d < hd; ++d) {
+      double ak = 0.0, av = 0.0;
+      for (int tt = 0; tt < n; ++tt) {
+        ak += dS[tt * S + t] * q[(long)tt * D + c0 + d];
+        av += P[((long)h * n + tt) * n + t] * dOb[(long)tt * D + c0 + d];
+      }
+      dk[b * A + (long)t * D + c0 + d] += sc * ak;
+      dv[b * A + (long)t * D + c0 + d] += av;
+    }
+  }
+}
+
+// table[z + e] = act'(Z[z + e]) for the elements of up to NUC_DACT_JOBS activated layers, concatenated: the derivative depends on
+// the SHARED pre-activations alone, so it is evaluated once per call, not once per walker (tanh and exp in double are the
+// expensive part of the A operand of k_nucb_dx)
+constexpr int NUC_DACT_JOBS = 24;
+struct NucDactJobs { int count; int act[NUC_DACT_JOBS]; long z[NUC_DACT_JOBS], n[NUC_DACT_JOBS]; };
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_dact(const double* __restrict__ acts, double* __restrict__ table, NucDactJobs J) {
+  long e = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  for (int j = 0; j < J.count; ++j) {
+    if (e < J.n[j]) { table[J.z[j] + e] = nuc_dact(acts[J.z[j] + e], J.act[j]); return; }
+    e -= J.n[j];
+  }
+}
+
+// dX[m][i] += sum_o dY[m][o] act'(Z[rr][o]) W[i][o] for i < k_cols, on v_mfma_f64_16x16x4_f64.  Row m = (b, rr), rr < rows (the
+// rows per walker), lives at b * A + rr * width of its arena; dA = act'(Z) [rows][n_out] (k_nucb_dact; nullptr: no activation)
+// and W [n_in][n_out] are shared by the walkers.
+// A workgroup of four waves stages the panel W[16 CT blockIdx.y ..][:] in the LDS once (row stride S, odd, zero beyond n_out
+// and k_cols) and walks its share of the 16-row tiles; a wave holds the CT 16 x 16 tiles of one row tile, so the A operand --
+// dY times the activation's derivative, formed while it is loaded, eight k-steps of loads in flight at a time -- is read once
+// per panel.  The first panel also writes dZ = dY act'(Z) (a buffer of its own in the arena, what a per-walker weight gradient
+// would read).
+template <int CT>
+__global__ void __launch_bounds__(256) k_nucb_dx(const double* __restrict__ dY, const double* __restrict__ dA, const double* __restrict__ W,
+                                                 double* __restrict__ dZ, double* __restrict__ dX, int rows, long M, int n_in, int n_out,
+                                                 int k_cols, int S, long A) {
+  typedef Mfma<double>::acc_t acc_t;
+  HIP_DYNAMIC_SHARED(char, nucb_smem)
+  double* Ws = reinterpret_cast<double*>(nucb_smem);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
+  const int i0 = blockIdx.y * 16 * CT;
+  for (int e = threadIdx.x; e < 16 * CT * S; e += 256) {
+    const int c = e / S, o = e - c * S;
+    Ws[e] = (i0 + c < k_cols && o < n_out) ? W[(long)(i0 + c) * n_out + o] : 0.0;
+  }
+  __syncthreads();
+  const long n_tiles = (M + 15) / 16;
+  for (long tile = (long)blockIdx.x * 4 + wv; tile < n_tiles; tile += (long)gridDim.x * 4) {
+    const long ma = tile * 16 + l15;
+    const long ba = ma / rows;
+    const int ra = (int)(ma - ba * rows);
+    const double* yrow = dY + ba * A + (long)ra * n_out;
+    const double* drow = dA ? dA + (long)ra * n_out : nullptr;
+    double* dzrow = dZ + ba * A + (long)ra * n_out;
+    acc_t acc[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) acc[c] = acc_t{0, 0, 0, 0};
+    for (int o0 = 0; o0 < n_out; o0 += 32) {
+      double a[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int o = o0 + 4 * j + l4;
+        a[j] = (ma < M && o < n_out) ? yrow[o] : 0.0;
+      }
+      if (dA) {
+        double d[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int o = o0 + 4 * j + l4;
+          d[j] = (ma < M && o < n_out) ? drow[o] : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] *= d[j];
+        if (blockIdx.y == 0) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int o = o0 + 4 * j + l4;
+            if (ma < M && o < n_out) dzrow[o] = a[j];
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (o0 + 4 * j < n_out) {      // (uniform over the wave; the panel's rows are zero-filled up to the next multiple of 4)
+#pragma unroll
+          for (int c = 0; c < CT; ++c) acc[c] = Mfma<double>::run(a[j], Ws[(c * 16 + l15) * S + o0 + 4 * j + l4], acc[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const int i = i0 + c * 16 + l15;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long m = tile * 16 + Mfma<double>::row_of(lane, j);
+        if (m < M && i < k_cols) {
+          const long b = m / rows;
+          dX[b * A + (m - b * rows) * n_in + i] += acc[c][j];
+        }
+      }
+    }
+  }
+}
+
+// The edge features' adjoint carried into R, added into grad_R (the context's precision) after the electron stream's part.
+// With d = R[r] - R[s], rho = sqrt(eps + |d|^2), s(rho) = log1p(rho) / rho the features of edge (s n + r) are F0 = log1p(rho)
+// and F_{1+c} = d_c s(rho):  dF0/dd_c = d_c / (rho (1 + rho)),  dF_{1+c}/dd_c' = delta_cc' s + d_c d_c' (1 / (1 + rho) - s) / rho^2.
+// The edge's d/dd enters R[r] with + and R[s] with -.  One thread per (walker, nucleus a, component): its 2 n - 2 off-diagonal
+// edges in ascending edge order (the diagonal edge cancels).  Walkers with sign 0 or a non-finite log|psi| keep their rows.
+template <typename real>
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_edge_feat_bwd(const double* __restrict__ R, double eps, const double* __restrict__ dF,
+                                                                  int n, long A, const real* __restrict__ lp, const int32_t* __restrict__ sg,
+                                                                  real* __restrict__ grad_R, long total) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  const int x = (int)(idx % 3);
+  const long q = idx / 3;
+  const int a = (int)(q % n);
+  const long b = q / n;
+  const double l = (double)lp[b];
+  if (sg[b] == 0 || !(l - l == 0)) return;
+  const int w = 4 + n;
+  const double* g = dF + b * A;
+  auto edge = [&](int s, int r) {      // d log|psi| / d d_x of edge (s, r)
+    const double d[3] = {R[3 * r] - R[3 * s], R[3 * r + 1] - R[3 * s + 1], R[3 * r + 2] - R[3 * s + 2]};
+    const double rho = sqrt(eps + (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]));
+    const double ir = 1.0 / (1.0 + rho), sc = log1p(rho) / rho;
+    const double* ge = g + ((long)s * n + r) * w;
+    const double gd = ge[1] * d[0] + ge[2] * d[1] + ge[3] * d[2];
+    return ge[0] * d[x] * ir / rho + ge[1 + x] * sc + d[x] * gd * (ir - sc) / (rho * rho);
+  };
+  double acc = 0.0;
+  for (int s = 0; s < n; ++s) {
+    if (s != a) acc += edge(s, a);
+    else for (int r = 0; r < n; ++r) if (r != a) acc -= edge(a, r);
+  }
+  grad_R[idx] += (real)acc;
+}
+
 void launch_nuc_edge_feat(hipStream_t st, const double* R, const int32_t* types, double eps, double* F, int n) {
   hipLaunchKernelGGL(k_nuc_edge_feat, dim3(nuc_grid((long)n * n)), dim3(NUC_BLOCK), 0, st, R, types, eps, F, n);
 }
@@ -280,3 +517,92 @@ void launch_nuc_scatter(hipStream_t st, const double* derived, const int32_t* ro
 }
 template void launch_nuc_scatter<float>(hipStream_t, const double*, const int32_t*, const int32_t*, float*, double*, long);
 template void launch_nuc_scatter<double>(hipStream_t, const double*, const int32_t*, const int32_t*, double*, double*, long);
+
+template <typename T>
+void launch_nucb_gather(hipStream_t st, const T* src, long stride, long w0, long len, const int32_t* row, const int32_t* col, long e_lo,
+                        long e_hi, double* G, long A, int B) {
+  const long total = (long)B * (e_hi - e_lo);
+  if (total <= 0) return;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nucb_gather<T>), dim3(nuc_grid(total)), dim3(NUC_BLOCK), 0, st, src, stride, w0, len, row, col, e_lo,
+                     e_hi, G, A, total);
+}
+template void launch_nucb_gather<float>(hipStream_t, const float*, long, long, long, const int32_t*, const int32_t*, long, long, double*, long, int);
+template void launch_nucb_gather<double>(hipStream_t, const double*, long, long, long, const int32_t*, const int32_t*, long, long, double*, long,
+                                         int);
+void launch_nucb_add(hipStream_t st, double* a, const double* c, long n, long A, int B) {
+  hipLaunchKernelGGL(k_nucb_add, dim3(nuc_grid(n * B)), dim3(NUC_BLOCK), 0, st, a, c, n, A, n * B);
+}
+void launch_nucb_glu_bwd(hipStream_t st, const double* zw, const double* zv, const double* dzeta, double* dzw, double* dzv, long n, long A,
+                         int B) {
+  hipLaunchKernelGGL(k_nucb_glu_bwd, dim3(nuc_grid(n * B)), dim3(NUC_BLOCK), 0, st, zw, zv, dzeta, dzw, dzv, n, A, n * B);
+}
+void launch_nucb_layernorm_bwd(hipStream_t st, const double* ln, const double* rstd, const double* dln, double* dh, int n, int D, long A,
+                               int B) {
+  const long total = (long)n * B;
+  hipLaunchKernelGGL(k_nucb_layernorm_bwd, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, ln, rstd, dln, dh, n, D, A, total);
+}
+void launch_nucb_sender_sum_bwd(hipStream_t st, const double* dout, double* din, int n, int w, long A, int B) {
+  const long total = (long)n * n * w * B;
+  hipLaunchKernelGGL(k_nucb_sender_sum_bwd, dim3(nuc_grid(total)), dim3(NUC_BLOCK), 0, st, dout, din, n, w, A, total);
+}
+size_t nucb_attention_bwd_lds_bytes(int n) { return sizeof(double) * (size_t)n * (n + 1); }
+void launch_nucb_attention_bwd(hipStream_t st, const double* q, const double* k, const double* v, const double* P, const double* dO,
+                               double* dq, double* dk, double* dv, int n, int H, int hd, long A, int B) {
+  hipLaunchKernelGGL(k_nucb_attention_bwd, dim3((unsigned)((long)B * H)), dim3(64), nucb_attention_bwd_lds_bytes(n), st, q, k, v, P, dO, dq, dk,
+                     dv, n, H, hd, A);
+}
+// column tiles per workgroup of k_nucb_dx for a panel of k_cols columns and n_out deep: the widest of 4, 2, 1 (no wider than
+// the columns need) whose panel leaves room for two workgroups per CU (80 KB), else the widest that fits the 160 KB of a CU
+// at all; 0: none does
+static inline int nucb_dx_row_stride(int n_out) { return ((n_out + 3) / 4 * 4) | 1; }
+size_t nucb_dx_lds_bytes(int ct, int n_out) { return sizeof(double) * 16 * (size_t)ct * nucb_dx_row_stride(n_out); }
+int nucb_dx_col_tiles(int k_cols, int n_out) {
+  const int need = (k_cols + 15) / 16;
+  for (int ct = 4; ct >= 1; ct >>= 1)
+    if ((ct == 1 || ct / 2 < need) && nucb_dx_lds_bytes(ct, n_out) <= (size_t)80 * 1024) return ct;
+  for (int ct = 4; ct >= 1; ct >>= 1)
+    if ((ct == 1 || ct / 2 < need) && nucb_dx_lds_bytes(ct, n_out) <= (size_t)160 * 1024) return ct;
+  return 0;
+}
+void launch_nucb_dact(hipStream_t st, const double* acts, double* table, const int* act, const long* z, const long* n, int count) {
+  for (int j0 = 0; j0 < count; j0 += NUC_DACT_JOBS) {
+    NucDactJobs J{};
+    long total = 0;
+    J.count = count - j0 < NUC_DACT_JOBS ? count - j0 : NUC_DACT_JOBS;
+    for (int j = 0; j < J.count; ++j) { J.act[j] = act[j0 + j]; J.z[j] = z[j0 + j]; J.n[j] = n[j0 + j]; total += n[j0 + j]; }
+    if (total > 0) hipLaunchKernelGGL(k_nucb_dact, dim3(nuc_grid(total)), dim3(NUC_BLOCK), 0, st, acts, table, J);
+  }
+}
+template <int CT>
+static int nucb_dx_launch(hipStream_t st, const double* dY, const double* dA, const double* W, double* dZ, double* dX, int rows, long M,
+                          int n_in, int n_out, int k_cols, long A) {
+  const size_t lds = nucb_dx_lds_bytes(CT, n_out);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nucb_dx<CT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return -2;
+  const long groups = ((M + 15) / 16 + 3) / 4;
+  const unsigned gx = (unsigned)(groups < 2048 ? groups : 2048);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nucb_dx<CT>), dim3(gx, (unsigned)((k_cols + 16 * CT - 1) / (16 * CT))), dim3(256), lds, st, dY, dA, W, dZ,
+                     dX, rows, M, n_in, n_out, k_cols, nucb_dx_row_stride(n_out), A);
+  return 0;
+}
+int launch_nucb_dx(hipStream_t st, const double* dY, const double* dA, const double* W, double* dZ, double* dX, int rows, int B, int n_in,
+                   int n_out, int k_cols, long A) {
+  const long M = (long)B * rows;
+  switch (nucb_dx_col_tiles(k_cols, n_out)) {
+    case 4: return nucb_dx_launch<4>(st, dY, dA, W, dZ, dX, rows, M, n_in, n_out, k_cols, A);
+    case 2: return nucb_dx_launch<2>(st, dY, dA, W, dZ, dX, rows, M, n_in, n_out, k_cols, A);
+    case 1: return nucb_dx_launch<1>(st, dY, dA, W, dZ, dX, rows, M, n_in, n_out, k_cols, A);
+    default: return -1;
+  }
+}
+template <typename real>
+void launch_nucb_edge_feat_bwd(hipStream_t st, const double* R, double eps, const double* dF, int n, long A, const real* lp, const int32_t* sg,
+                               real* grad_R, int B) {
+  const long total = (long)B * n * 3;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nucb_edge_feat_bwd<real>), dim3(nuc_grid(total)), dim3(NUC_BLOCK), 0, st, R, eps, dF, n, A, lp, sg,
+                     grad_R, total);
+}
+template void launch_nucb_edge_feat_bwd<float>(hipStream_t, const double*, double, const double*, int, long, const float*, const int32_t*,
+                                               float*, int);
+template void launch_nucb_edge_feat_bwd<double>(hipStream_t, const double*, double, const double*, int, long, const double*, const int32_t*,
+                                                double*, int);

@@ -53,7 +53,8 @@ def _ptr(t):
 
 class Engine:
     def __init__(self, spec: AnsatzSpec, hamil: MolecularHamiltonian, params, *, dtype=torch.float32,
-                 device='cuda', norm_eps: Optional[float] = None, lib=None, R=None, compiler=None, nuclear_reverse=False):
+                 device='cuda', norm_eps: Optional[float] = None, lib=None, R=None, compiler=None, nuclear_reverse=False,
+                 nuclear_coords=False):
         """`R` [n_nuc,3]: the geometry this context is compiled for (default: the Hamiltonian's).  It matters only
         for ansatzes with nuclear tokens, whose nuclear stream is folded into the program; every other ansatz
         takes the geometry per call.  `compiler(params) -> Program` replaces the default `compile_program(spec, ...)`
@@ -61,7 +62,10 @@ class Engine:
         any object with `n_determinants` and `nuclei_tokens`.  `nuclear_reverse`: for an ansatz with nuclear tokens, register
         the nuclear stream with the library (dqmc_set_nuclear_stream) and switch on options "attention_reverse" and
         "nuclear_reverse": device updates fold the stream on the device and grad_to_params transposes it, so the
-        walker-summed gradients (log_psi_vjp, orbitals_vjp, pretrain_loss_grad) and the Adam step run."""
+        walker-summed gradients (log_psi_vjp, orbitals_vjp, pretrain_loss_grad) and the Adam step run.  `nuclear_coords` (implies
+        `nuclear_reverse`): option "nuclear_coords" as well, which opens log_psi_grad_coords -- the stream's backward runs per
+        walker, adjoints only, down to R.  `self.nuclear_coords` says whether it is on."""
+        nuclear_reverse = bool(nuclear_reverse) or bool(nuclear_coords)
         self.lib = lib if lib is not None else _lib.load()
         self.spec, self.hamil = spec, hamil
         self.dtype = dtype
@@ -117,6 +121,9 @@ class Engine:
             self._register_nuclear_stream()
             self.set_option('attention_reverse', 1)
             self.set_option('nuclear_reverse', 1)
+        self.nuclear_coords = bool(nuclear_coords) and p.nuclear_stream is not None
+        if self.nuclear_coords:
+            self.set_option('nuclear_coords', 1)
 
     def _register_nuclear_stream(self):
         """dqmc_set_nuclear_stream from Program.nuclear_stream and the current parameters."""
@@ -598,7 +605,9 @@ class Engine:
         """d log|psi(r_b)| / d r and d log|psi(r_b)| / d R per walker from the reverse pass (dqmc_log_psi_grad_coords).
         Returns (sign, logpsi, grad_r [B, N, 3] or None, grad_R [B, n_nuc, 3] or None) in the engine's dtype on its device.
         Walkers with sign 0 or a non-finite log|psi| get zero rows.  Programs with attention ops raise DqmcError (-4) unless
-        option 'attention_reverse' is set to 1 (NeuralNetworkWaveFunction(..., attention_reverse=True))."""
+        option 'attention_reverse' is set to 1 (NeuralNetworkWaveFunction(..., attention_reverse=True)); programs with nuclear
+        tokens need Engine(..., nuclear_coords=True), and their stream's part of grad_R is differentiated at the geometry the
+        context was compiled for.  want_R=False never runs the stream's backward."""
         if not (want_r or want_R):
             raise ValueError('log_psi_grad_coords: want_r and want_R are both False')
         r, R, B = self._walkers(r, R)

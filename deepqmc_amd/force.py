@@ -75,14 +75,15 @@ def Q(r, R, c):
 
 def make_grad_nuc_log_wf(wf):
     """force.py make_grad_nuc_log_wf: f(params, phys_conf) -> d log|psi| / d R per walker, [B, n_nuc, 3] float64.
-    Independent of the Hamiltonian (ECP Hamiltonians included); the programs log_psi_vjp supports."""
+    Independent of the Hamiltonian (ECP Hamiltonians included); the programs log_psi_vjp supports (a TransPsiformer: a wave
+    function made with `nuclear_coords=True`)."""
 
     def grad_nuc_log_wf(params, phys_conf):
         r, R = _split(phys_conf)
         eng = wf.engine(params, R)
         if eng.program.grad_unsupported:
             raise NotImplementedError(f'make_grad_nuc_log_wf: unsupported for this program ({eng.program.grad_unsupported})')
-        if eng.program.nuclear_stream is not None:
+        if eng.program.nuclear_stream is not None and not eng.nuclear_coords:
             raise NotImplementedError(f'make_grad_nuc_log_wf: {eng.program.PER_WALKER_NUCLEAR}')
         return eng.log_psi_grad_coords(r, R, want_r=False)[3].double()
 
@@ -104,7 +105,7 @@ def _estimator(hamil, wf, est, *, takes_rng, needs_energy):
         if nuc:
             if eng.program.grad_unsupported:
                 raise NotImplementedError(f'evaluate_hf_force_{est}: unsupported for this program ({eng.program.grad_unsupported})')
-            if eng.program.nuclear_stream is not None:
+            if eng.program.nuclear_stream is not None and not eng.nuclear_coords:
                 raise NotImplementedError(f'evaluate_hf_force_{est}: {eng.program.PER_WALKER_NUCLEAR}')
             grad_R = eng.log_psi_grad_coords(r, R, want_r=False)[3]
         if needs_energy:

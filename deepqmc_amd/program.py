@@ -113,7 +113,8 @@ class Program:
 
     PER_WALKER_NUCLEAR = ('the nuclear-token stream has no per-walker partials (all walkers share it: one nuclear backward per '
                           'walker); only the walker-summed gradients (log_psi_vjp, orbitals_vjp, pretraining, AdamOptimizer) run '
-                          'with nuclear tokens')
+                          'with nuclear tokens, and with nuclear_coords=True the coordinate calls (log_psi_grad_coords, '
+                          'make_grad_nuc_log_wf, the AC-ZB / AC-ZVQZB forces)')
 
     def unflatten_grad(self, g):
         """Flat gradient over the weight buffer (dqmc_log_psi_vjp) -> haiku tree {module: {leaf: array}}: the transpose of

@@ -30,7 +30,7 @@ from .types import PhysicalConfiguration, Psi
 
 class NeuralNetworkWaveFunction:
     def __init__(self, hamil: MolecularHamiltonian, spec='paulinet', *, dtype=torch.float32, device='cuda',
-                 norm_eps=None, lib=None, attention_reverse=False, nuclear_reverse=False):
+                 norm_eps=None, lib=None, attention_reverse=False, nuclear_reverse=False, nuclear_coords=False):
         """`attention_reverse`: opt in to the reverse pass through attention ops (library option "attention_reverse"), which
         the parameter- and coordinate-gradient entry points below, the force and ECP-force estimators, pretraining,
         `create_loss_fn` and the optimisers of `fit_wf` need for a Psiformer.  Off (the default) those calls fail with
@@ -40,15 +40,20 @@ class NeuralNetworkWaveFunction:
         device and has a backward there (library option "nuclear_reverse"), which opens `log_psi_vjp`, `orbitals_vjp`,
         pretraining, `create_loss_fn` and `fit_wf` with AdamOptimizer / NoOptimizer.  The per-walker modes (log_psi_jacobian,
         log_psi_kfac, log_psi_grad_coords, NaturalGradientOptimizer, KFACOptimizer, forces) stay refused: the stream is shared
-        by all walkers and has no per-walker partials."""
+        by all walkers and has no per-walker partials.
+        `nuclear_coords` (implies `nuclear_reverse` and `attention_reverse`): the stream's backward also runs per walker, adjoints
+        only, down to the nuclear coordinates (library option "nuclear_coords"), which opens `log_psi_grad_coords`,
+        `force.make_grad_nuc_log_wf`, `evaluate_hf_force_ac_zb` / `_ac_zvqzb` and their `fit_wf` monitors.  The Jacobian, KFAC,
+        NaturalGradientOptimizer, KFACOptimizer and the ECP force stay refused."""
         self.hamil = hamil
         if spec == 'transpsiformer':
             self.spec: AnsatzSpec = ANSATZES[spec](hamil.mol.charges)      # atom types of the nuclei embedding
         else:
             self.spec = ANSATZES[spec]() if isinstance(spec, str) else spec
         self.dtype, self.device, self.norm_eps, self._lib = dtype, device, norm_eps, lib
-        self.nuclear_reverse = bool(nuclear_reverse) and bool(self.spec.nuclei_tokens)
-        self.attention_reverse = bool(attention_reverse) or bool(nuclear_reverse)
+        self.nuclear_coords = bool(nuclear_coords) and bool(self.spec.nuclei_tokens)
+        self.nuclear_reverse = (bool(nuclear_reverse) or bool(nuclear_coords)) and bool(self.spec.nuclei_tokens)
+        self.attention_reverse = bool(attention_reverse) or bool(nuclear_reverse) or bool(nuclear_coords)
         self._engines = []       # [(params tree, Engine)], most recently used last (one per electronic state)
         self.max_engines = 8
         self._evictions = 0
@@ -100,7 +105,8 @@ class NeuralNetworkWaveFunction:
             import numpy as np
             R0 = None if gkey is None else np.frombuffer(gkey, np.float64).reshape(self.hamil.n_nuc, 3)
             eng = Engine(self.spec, self.hamil, params, dtype=self.dtype, device=self.device,
-                         norm_eps=self.norm_eps, lib=self._lib, R=R0, nuclear_reverse=self.nuclear_reverse)
+                         norm_eps=self.norm_eps, lib=self._lib, R=R0, nuclear_reverse=self.nuclear_reverse,
+                         nuclear_coords=self.nuclear_coords)
             if self.attention_reverse:      # before any set_kfac_map or graph capture (setting an option bumps the graph epoch)
                 eng.set_option('attention_reverse', 1)
         self._engines.append((params, gkey, eng))
@@ -182,10 +188,10 @@ class NeuralNetworkWaveFunction:
             return prog.unflatten_params(eng.grad_to_params(g))
         return prog.unflatten_grad(g)
 
-    def _per_walker_check(self, name, eng):
+    def _per_walker_check(self, name, eng, coords=False):
         if eng.program.grad_unsupported:
             raise NotImplementedError(f'{name}: unsupported for this program ({eng.program.grad_unsupported})')
-        if eng.program.nuclear_stream is not None:
+        if eng.program.nuclear_stream is not None and not (coords and eng.nuclear_coords):
             raise NotImplementedError(f'{name}: {eng.program.PER_WALKER_NUCLEAR}')
 
     def _orbital_engine(self, name, params, phys_conf):
@@ -260,10 +266,10 @@ class NeuralNetworkWaveFunction:
         """jax.grad of ansatz.apply(.).log with respect to the electron and the nuclear coordinates (reference force.py
         make_grad_log_wf / make_grad_nuc_log_wf), per walker, from the reverse pass (Engine.log_psi_grad_coords): returns
         (Psi(sign, log), grad_r [B, N, 3], grad_R [B, n_nuc, 3]) on the device, in the wave function's dtype.  The same
-        programs as log_psi_vjp are supported."""
+        programs as log_psi_vjp are supported; a TransPsiformer needs `nuclear_coords=True`."""
         r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
         R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
         eng = self.engine(params, R)
-        self._per_walker_check('log_psi_grad_coords', eng)
+        self._per_walker_check('log_psi_grad_coords', eng, coords=True)
         sign, log, gr, gR = eng.log_psi_grad_coords(r, R)
         return Psi(sign, log), gr, gR

@@ -289,6 +289,11 @@ int dqmc_kfac_apply(dqmc_ctx* ctx, double* theta, const double* delta, const dou
  * out_host NULL: returns the size of the buffer in bytes (> 0).  Otherwise `bytes` must be exactly that size (DQMC_E_ARG);
  * DQMC_E_UNSUPPORTED when the context has no such buffer.  Synchronises the stream. */
 int dqmc_debug_read_weights(dqmc_ctx* ctx, int which, void* out_host, size_t bytes);
+/* Timing aid (tools/nuclear_coords_time.py): on the largest linear layer of the nuclear stream's token rows, B walkers, the
+ * batched input-adjoint kernel of option "nuclear_coords" against the reverse pass's float64 LINEAR backward restricted to dX,
+ * alternated `reps` times after a warm-up round.  ms2: the two median times in ms (device events); shape3: {B n_nuc, n_in,
+ * n_out}.  Uses the gradient workspace; synchronises the stream.  DQMC_E_ARG without a folded stream. */
+int dqmc_debug_nuc_dx_time(dqmc_ctx* ctx, int B, int reps, double* ms2, int* shape3);
 /* out2 (host) = {captures, replays} of the context's forward-Laplacian graphs since its creation. */
 int dqmc_graph_counters(dqmc_ctx* ctx, int64_t* out2);
 
@@ -423,7 +428,11 @@ int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logp
  * dqmc_pretrain_loss_grad: grad then also carries the walker-summed gradient of the constant key / value rows and of the
  * folded zeta tables, which dqmc_grad_to_params takes back through the nuclear stream.  The per-walker calls
  * (dqmc_log_psi_jacobian, dqmc_log_psi_kfac, dqmc_log_psi_grad_coords, dqmc_ecp_force, dqmc_set_kfac_map) keep answering
- * DQMC_E_UNSUPPORTED for such programs: the stream is shared by all walkers and has no per-walker partials. */
+ * DQMC_E_UNSUPPORTED for such programs: the stream is shared by all walkers and has no per-walker partials.
+ * Option "nuclear_coords" 1 (it needs a registered stream AND "nuclear_reverse" 1; anything else, and values other than 0 / 1:
+ * DQMC_E_ARG) admits dqmc_log_psi_grad_coords as well: it needs the stream's per-walker ADJOINTS only, which a backward of the
+ * stream batched over the walkers provides (see there).  The other four keep refusing with the same text.  Off (the default)
+ * nothing changes. */
 int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot,
                      double* grad, void* logpsi, int32_t* sign);
 
@@ -474,7 +483,18 @@ int dqmc_log_psi_kfac(dqmc_ctx* ctx, const void* r, const void* R, int B, const 
  * the electrons and nuclei run in a fixed order (no atomics): identical calls are bit-identical, and a chunked call equals
  * an unchunked one bit for bit.  Walkers with sign 0 or a non-finite log|psi| get zero rows.  By translation invariance
  * sum_a grad_R[b][a] = -sum_i grad_r[b][i].  DQMC_E_UNSUPPORTED for ATTENTION programs without
- * option "attention_reverse" and for N > 64, as dqmc_log_psi_vjp. */
+ * option "attention_reverse" and for N > 64, as dqmc_log_psi_vjp.
+ * Programs with a nuclear stream (constant key / value rows) run with option "nuclear_coords" 1.  grad_R then is the sum of two
+ * parts: the electron stream's, differentiated at the R of the call as for every program, and the nuclear stream's -- each
+ * walker's partials of the constant key / value rows and of the zeta tables, summed over the copies of every derived element,
+ * taken back through the stream per walker (float64 in both precisions, adjoints only, a number of launches that does not depend
+ * on B) and through the edge features into R.  The stream's part is differentiated at the REGISTERED geometry
+ * (dqmc_nuc_stream.R), whatever R the call passes: the constants the program reads were folded there.  (Through
+ * NeuralNetworkWaveFunction the two coincide: one context per geometry.)  A call with grad_R == NULL never runs the stream's
+ * backward; one with grad_R refuses with DQMC_E_ARG while the stream's activations are older than the weights (dqmc_set_weights
+ * since the last dqmc_weights_from_params), as dqmc_grad_to_params does, and with DQMC_E_UNSUPPORTED, launching nothing, if a
+ * stream layer's weight panel (16 columns x n_out doubles) does not fit the 160 KB of LDS.  The stream's part of a walker's
+ * row is summed in a fixed order that does not depend on the other walkers of the chunk. */
 int dqmc_log_psi_grad_coords(dqmc_ctx* ctx, const void* r, const void* R, int B, void* grad_r, void* grad_R,
                              void* logpsi, int32_t* sign);
 
