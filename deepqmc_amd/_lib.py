@@ -56,6 +56,7 @@ SIGNATURES = [
     ('dqmc_set_nuclear_stream', c_int, [c_void_p, POINTER(DqmcNucStream)]),
     ('dqmc_weights_from_params', c_int, [c_void_p, c_void_p]),
     ('dqmc_grad_to_params', c_int, [c_void_p, c_void_p, c_void_p]),
+    ('dqmc_jacobian_to_params', c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_size_t]),
     ('dqmc_adam_step', c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_double, c_double, c_double, c_double,
                                c_int64, c_void_p]),
     ('dqmc_apply_update', c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p]),

@@ -158,6 +158,8 @@ struct dqmc_ctx {
   virtual int weights_from_params(const double* theta) = 0;
   virtual int load_weights_device(const double* w64) = 0;
   virtual int grad_to_params(const double* grad_w, double* grad_theta) = 0;
+  virtual int jacobian_to_params(const void* jac, size_t ld_jac, int B, const void* logpsi, const int32_t* sign, void* jac_theta,
+                                 size_t ld_theta) = 0;
   virtual int adam_step(double* theta, double* mu, double* nu, const double* g, size_t n, double lr, double b1, double b2, double eps,
                         int64_t t, double* norms3) = 0;
   virtual int apply_update(double* theta, const double* delta, double scale, double* norms3) = 0;
@@ -668,6 +670,12 @@ int dqmc_grad_to_params(dqmc_ctx* ctx, const double* grad_w, double* grad_theta)
   if (!ctx || !grad_w || !grad_theta) return fail(DQMC_E_ARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   return ctx->grad_to_params(grad_w, grad_theta);
+}
+int dqmc_jacobian_to_params(dqmc_ctx* ctx, const void* jac, size_t ld_jac, int B, const void* logpsi, const int32_t* sign, void* jac_theta,
+                            size_t ld_theta) {
+  if (!ctx || !jac || !logpsi || !sign || !jac_theta) return fail(DQMC_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ctx->jacobian_to_params(jac, ld_jac, B, logpsi, sign, jac_theta, ld_theta);
 }
 int dqmc_adam_step(dqmc_ctx* ctx, double* theta, double* mu, double* nu, const double* grad_theta, size_t n, double lr, double b1,
                    double b2, double eps, int64_t t, double* norms3) {

@@ -14,21 +14,25 @@
   // that sum their partials over the walkers (per_walker false: the Vjp and Orbs modes).  With option "nuclear_coords" as well
   // the Coords mode is admitted (coords true: it needs per-walker ADJOINTS of the stream only, nuc_fold_coords).  Every other
   // mode would need the stream's parameter partials per walker and keeps refusing, as do dqmc_set_kfac_map and dqmc_ecp_force.
+  // With option "nuclear_params" the Jac and Kfac modes, dqmc_set_kfac_map and dqmc_jacobian_to_params are admitted (params true:
+  // the stream's parameter partials per walker, nuc_fold_rows); dqmc_ecp_force keeps refusing.
   // 0: runs, 1: no reverse pass for ATTENTION ops, 2: nuclear tokens, per-walker mode.
-  int attention_refusal(bool per_walker, bool coords = false) const {
+  int attention_refusal(bool per_walker, bool coords = false, bool params = false) const {
     for (const auto& o : ops)
       if (o.kind == DQMC_OP_ATTENTION) {
         if (!attention_reverse) return 1;
         if (dqmc::AttentionOp(o).n_const() > 0) {
           if (!nuclear_reverse || !nuc_set) return 1;
-          if (per_walker && !(coords && nuclear_coords)) return 2;
+          if (per_walker && !(coords && nuclear_coords) && !(params && nuclear_params)) return 2;
         }
       }
     return 0;
   }
-  bool attention_refused(bool per_walker = true, bool coords = false) const { return attention_refusal(per_walker, coords) != 0; }
-  std::string attention_refusal_text(bool per_walker, bool coords = false) const {
-    return attention_refusal(per_walker, coords) == 2
+  bool attention_refused(bool per_walker = true, bool coords = false, bool params = false) const {
+    return attention_refusal(per_walker, coords, params) != 0;
+  }
+  std::string attention_refusal_text(bool per_walker, bool coords = false, bool params = false) const {
+    return attention_refusal(per_walker, coords, params) == 2
                ? "the nuclear-token stream has no per-walker partials (all walkers share it: one nuclear backward per walker); only "
                  "log_psi_vjp, orbitals_vjp and pretrain_loss_grad run with nuclear tokens"
                : "no reverse pass for ATTENTION ops";

@@ -19,9 +19,59 @@
   int kf_max_n = 0, kf_max_da = 0, kf_max_dg = 0, kf_panels = 0;
   size_t kf_state = 0;
   bool kf_set = false;
+  // option "nuclear_params": the stream's own parameters as diagonal elements (their o_bi through nuc_fold_rows, square-summed)
+  bool kf_nuc = false;
+  std::vector<uint8_t> kf_nuc_skip;     // per stream layer: 1 = a module covers it (no diagonal treatment)
+  DevBuf<double> kf_nucG, kf_nucF, kf_nucPart;      // [kf_nuc_cap + 1] arenas, F over theta, the slice sums of k_nucb_dw
+  DevBuf<int32_t> kf_nuc_col;           // d_nuc_col as rest columns
+  long kf_nuc_cap = 0;
+
+  // The stream's elements among the diagonal entries: a stream layer (zetas_bias table) no module covers must consist of entries
+  // with an empty CSR row, and an empty row must belong to one.  Reserves what dqmc_kfac_direction needs of the stream.
+  int set_kfac_map_nuc(const dqmc_kfac_map* hm, const std::vector<uint8_t>& in_module) {
+    auto bad = [&](const std::string& what) { return fail(DQMC_E_ARG, "dqmc_set_kfac_map: " + what); };
+    const long np = (long)pm_n_params, nd = (long)hm->n_diag;
+    std::vector<uint8_t> stream((size_t)np, 0);
+    kf_nuc_skip.assign(nuc_lin.size(), 0);
+    auto claim = [&](long off, long n, bool& any_mod, bool& any_diag) {
+      for (long e = off; e < off + n; ++e) { (in_module[e] ? any_mod : any_diag) = true; if (!in_module[e]) stream[e] = 1; }
+    };
+    bool some = false;
+    for (size_t q = 0; q < nuc_lin.size(); ++q) {
+      bool any_mod = false, any_diag = false;
+      claim(nuc_lin[q].w, (long)nuc_lin[q].n_in * nuc_lin[q].n_out, any_mod, any_diag);
+      if (nuc_lin[q].b >= 0) claim(nuc_lin[q].b, nuc_lin[q].n_out, any_mod, any_diag);
+      if (any_mod && any_diag) return bad("a nuclear-stream layer is covered partly by a module, partly by diagonal entries");
+      kf_nuc_skip[q] = any_mod ? 1 : 0;
+      some = some || any_diag;
+    }
+    if (nuc_ne)
+      for (int sp = 0; sp < 2; ++sp) {
+        bool any_mod = false, any_diag = false;
+        claim(nuc_zbias[sp], (long)nuc_n * nuc_K * nuc_ne, any_mod, any_diag);
+        if (any_mod) return bad("a module covers zetas_bias entries");
+        some = true;
+      }
+    for (long e = 0; e < nd; ++e) {
+      const bool empty = hm->diag_row[e + 1] == hm->diag_row[e];
+      if (stream[hm->diag_pos[e]] && !empty) return bad("a diagonal entry of the nuclear stream lists rest columns (its partials come through the stream)");
+      if (!stream[hm->diag_pos[e]] && empty) return bad("a diagonal entry without rest columns is no parameter of the nuclear stream");
+    }
+    kf_nuc = some;
+    if (!some) return DQMC_OK;
+    std::vector<int32_t> col(nuc_col_h.size());
+    for (size_t k = 0; k < col.size(); ++k) col[k] = (size_t)nuc_col_h[k] < n_weights ? (int32_t)k_rest_pos[nuc_col_h[k]] : -1;
+    const size_t arena = sizeof(double) * nuc_arena;
+    kf_nuc_cap = (long)std::min<size_t>(1024, std::max<size_t>(1, ((size_t)256 << 20) / arena));
+    int rc = kf_nuc_col.upload(col.data(), col.size());
+    if (!rc) rc = kf_nucG.assign(((size_t)kf_nuc_cap + 1) * nuc_arena);
+    if (!rc) rc = kf_nucF.assign((size_t)np);
+    if (!rc) rc = kf_nucPart.assign(nuc_params_part_doubles());
+    return rc;
+  }
 
   int set_kfac_map(const dqmc_kfac_map* hm) override {
-    if (attention_refused()) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: " + attention_refusal_text(true));
+    if (attention_refused(true, false, true)) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: " + attention_refusal_text(true, false, true));
     if (N > dqmc::GRAD_GJ_NMAX) return fail(DQMC_E_UNSUPPORTED, "dqmc_set_kfac_map: more than 64 electrons");
     if (!d_pm_src) return fail(DQMC_E_ARG, "no parameter map set (dqmc_set_param_map)");
     { const int rc = kfac_plan(); if (rc) return rc; }
@@ -87,6 +137,7 @@
     for (int q = 0; q < no; ++q) if (!op_used[q]) return bad("op belongs to no module");
     mat_start[2 * nm] = off;
     const long n_mat = off, nd = (long)hm->n_diag;
+    const std::vector<uint8_t> in_module(covered);
     for (long e = 0; e < nd; ++e) {
       const long pos = hm->diag_pos[e], c0 = hm->diag_row[e], c1 = hm->diag_row[e + 1];
       if (pos < 0 || pos >= np || covered[pos]++) return bad("diagonal element out of range or covered twice");
@@ -108,6 +159,8 @@
     // one device allocation for the tables
     HIP_TRY(hipStreamSynchronize(st));
     kf_set = false;
+    kf_nuc = false;
+    if (nuc_set && grad_att_const() > 0) { const int rc = set_kfac_map_nuc(hm, in_module); if (rc) return rc; }
     const size_t n_cols = nd ? (size_t)hm->diag_row[nd] : 0;
     auto up8 = [](size_t b) { return (b + 15) / 16 * 16; };
     size_t o_mod = 0, o_op = o_mod + up8(sizeof(dqmc::KfMod) * mods.size()), o_inv = o_op + up8(sizeof(dqmc::KfOp) * kops.size()),
@@ -153,8 +206,15 @@
     if (!(damping > 0)) return fail(DQMC_E_ARG, "dqmc_kfac_direction: damping must be positive");
     if (!(ema >= 0 && ema <= 1)) return fail(DQMC_E_ARG, "dqmc_kfac_direction: ema must lie in [0, 1]");
     if (kf_t.n_diag > 0 && !rest) return fail(DQMC_E_ARG, "dqmc_kfac_direction: the diagonal elements need `rest`");
+    if (kf_nuc) {      // sum_b o_bi^2 of the stream's own parameters, from the rest rows through the stream
+      HIP_TRY(hipMemsetAsync(kf_nucF, 0, sizeof(double) * pm_n_params, st));
+      const int rc = nuc_fold_rows<real>("dqmc_kfac_direction", (const real*)rest, (long)k_n_rest, (long)k_n_rest, kf_nuc_col, B, kf_nucG,
+                                         kf_nucG + (size_t)kf_nuc_cap * nuc_arena, kf_nuc_cap, nullptr, 0, kf_nucF, kf_nucPart, &kf_nuc_skip);
+      if (rc) return rc;
+    }
     HIP_TRY(hipMemcpyAsync(delta, g, sizeof(double) * pm_n_params, hipMemcpyDeviceToDevice, st));
     dqmc::KfacDirArgs a{};
+    a.nuc_F = kf_nuc ? kf_nucF.p : nullptr;
     a.t = kf_t;
     a.g = g; a.factors = factors; a.rest = rest; a.n_rest = (long)k_n_rest; a.logpsi = logpsi; a.sign = sign; a.B = B;
     a.state = state; a.first = first ? 1 : 0; a.ema = ema; a.damping = damping;

@@ -22,6 +22,7 @@
   struct NucLin { long w, b; int n_in, n_out, act; size_t z, y; };   // theta offsets (b -1: none); nuc_act offsets of Z and Y (act 0: the same)
   int nuclear_reverse = 0;       // option: the reverse pass admits constant key / value rows in the Vjp and Orbs modes
   int nuclear_coords = 0;        // option: the Coords mode admits them too and carries the stream's part of d log|psi| / dR (nuc_fold_coords)
+  int nuclear_params = 0;        // option: the Jac and Kfac modes admit them, and the stream's parameter partials exist per walker (nuc_fold_rows)
   bool nuc_set = false, nuc_fresh = false;
   std::map<std::pair<long, long>, std::pair<long, long>> nuc_range_of;      // weight range -> derived elements with a copy in it
   int nuc_n = 0, nuc_L = 0, nuc_H = 0, nuc_D = 0, nuc_K = 0, nuc_ne = 0, nuc_n_edge = 0, nuc_n_embed = 0, nuc_n_mlp = 0;
@@ -290,15 +291,19 @@
       }
     dqmc::launch_nucb_dact(st, d_nuc_act, T, act.data(), z.data(), cnt.data(), (int)act.size());
   }
-  // G: the walkers' adjoint arenas, T: nuc_arena doubles of scratch; lp, sg [B]: rows of walkers with sign 0 or a non-finite
-  // log|psi| stay as they are (zero)
-  int nuc_fold_coords(double* G, double* T, int B, const real* lp, const int32_t* sg, real* grad_R) {
+  // The batched adjoint chain both per-walker routes share: from the adjoints of the derived vector (the head of every arena)
+  // down to the edge features' adjoint at G + nuc_o_F.  Afterwards walker b's arena holds the pre-activation adjoint dZ of every
+  // linear layer q at nuc_lin[q].z.  G: the walkers' adjoint arenas, T: nuc_arena doubles of scratch; x_of (or nullptr)
+  // receives, per layer, the offset of its input X in nuc_act.  0, -1 (a weight panel exceeds the LDS) or -2 (HIP error).
+  int nuc_fold_adjoints(double* G, double* T, int B, std::vector<size_t>* x_of) {
     const double* a = d_nuc_act;
     const int n = nuc_n, D = nuc_D;
     const long A = (long)nuc_arena;
     int rc = 0;
     nuc_dact_table(T);
+    if (x_of) x_of->assign(nuc_lin.size(), 0);
     auto lin = [&](const NucLin& m, size_t x_off, int rows, long res_off, int k_cols) {
+      if (x_of) (*x_of)[&m - nuc_lin.data()] = x_off;
       if (!rc) rc = nuc_coords_linear(G, T, B, m, x_off, rows, res_off, k_cols);
     };
     std::vector<size_t> h_off(nuc_L + 1);
@@ -331,9 +336,107 @@
     dqmc::launch_nucb_sender_sum_bwd(st, G + nuc_o_esum, G + nuc_lin[nuc_n_edge - 1].y, n, nuc_lin[nuc_n_edge - 1].n_out, A, B);
     for (int e = nuc_n_edge; e-- > 0;)      // (of the features only the four columns of d carry an adjoint)
       lin(nuc_lin[e], e ? nuc_lin[e - 1].y : nuc_o_F, n * n, -1, e ? nuc_lin[e].n_in : 4);
+    return rc;
+  }
+  // the chain, then through the edge features into R.  lp, sg [B]: rows of walkers with sign 0 or a non-finite log|psi| stay as
+  // they are (zero)
+  int nuc_fold_coords(double* G, double* T, int B, const real* lp, const int32_t* sg, real* grad_R) {
+    const int rc = nuc_fold_adjoints(G, T, B, nullptr);
     if (rc) return rc == -1 ? fail(DQMC_E_UNSUPPORTED, "log_psi_grad_coords: a stream layer's weight panel exceeds the LDS")
                             : fail(DQMC_E_HIP, "nuclear-stream backward launch failed");
-    dqmc::launch_nucb_edge_feat_bwd<real>(st, d_nuc_R, sys.norm_eps, G + nuc_o_F, n, A, lp, sg, grad_R, B);
+    dqmc::launch_nucb_edge_feat_bwd<real>(st, d_nuc_R, sys.norm_eps, G + nuc_o_F, nuc_n, (long)nuc_arena, lp, sg, grad_R, B);
+    return DQMC_OK;
+  }
+
+  // ---- option "nuclear_params": the stream's parameter partials per walker ----
+  // The stream's only parameters are the w / b of its linear layers and the two zetas_bias tables.  With dZ_q[b] from the chain
+  // above and the shared activations X_q of the last fold, walker b's partials are dW_q[b] = X_q^T dZ_q[b], db_q[b] = colsum
+  // dZ_q[b] (k_nucb_dw) and its adjoint of the zeta tables.  nuc_fold_rows gathers each walker's partials of the derived
+  // elements from rows `src` (Jacobian rows over the weight buffer, or `rest` rows through the column table `col`), runs the
+  // chain and then either ADDS the partials to the rows of out [B][ld] in theta order (store) or adds the sum of their squares
+  // over the walkers into F [n_params] (sqF; `part`: the slice sums of the widest layer), in chunks of at most `cap` walkers
+  // whose arenas are G (then T: nuc_arena doubles).  only: per theta element, 1 where sqF is wanted (host, or nullptr: all);
+  // a layer is all or nothing.
+  bool nuc_params_fits() const {
+    if (!nuc_coords_fits()) return false;
+    for (size_t q = 0; q < nuc_lin.size(); ++q)
+      if (!dqmc::nucb_dw_fits((int)q < nuc_n_edge ? nuc_n * nuc_n : nuc_n)) return false;
+    return true;
+  }
+  size_t nuc_params_part_doubles() const {
+    size_t m = 1;
+    for (const auto& l : nuc_lin) m = std::max(m, dqmc::nucb_dw_part_doubles(l.n_in, l.n_out));
+    return m;
+  }
+  int nuc_params_check(const std::string& name) {
+    if (!nuc_fresh)
+      return fail(DQMC_E_ARG, name + ": the nuclear stream's activations are older than the weights (dqmc_set_weights since the last "
+                                     "dqmc_weights_from_params)");
+    if (!nuc_params_fits()) return fail(DQMC_E_UNSUPPORTED, name + ": a nuclear-stream layer exceeds the LDS");
+    return DQMC_OK;
+  }
+  template <class T>
+  int nuc_fold_rows(const std::string& name, const T* src, long stride, long len, const int32_t* col, int B, double* G, double* Tb, long cap,
+                    real* out, long ld, double* sqF, double* part, const std::vector<uint8_t>* skip_lin) {
+    { const int rc = nuc_params_check(name); if (rc) return rc; }
+    const long A = (long)nuc_arena;
+    std::vector<size_t> x_of;
+    for (long b0 = 0; b0 < B; b0 += cap) {
+      const int nb = (int)std::min<long>(cap, B - b0);
+      HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * (size_t)nb * nuc_arena, st));
+      dqmc::launch_nucb_gather<T>(st, src + b0 * stride, stride, 0, len, d_nuc_row, col, 0, (long)nuc_n_derived, G, A, nb);
+      t_begin("nuc_rows_chain", 0);
+      int rc = nuc_fold_adjoints(G, Tb, nb, &x_of);
+      t_end();
+      real* o = out ? out + b0 * ld : nullptr;
+      t_begin("nucb_dw", 0);
+      for (size_t q = 0; q < nuc_lin.size() && !rc; ++q) {
+        if (skip_lin && (*skip_lin)[q]) continue;
+        const NucLin& m = nuc_lin[q];
+        const int rows = (int)q < nuc_n_edge ? nuc_n * nuc_n : nuc_n;
+        if (out) rc = dqmc::launch_nucb_dw_store<real>(st, d_nuc_act + x_of[q], G + m.z, A, rows, m.n_in, m.n_out, nb, o, ld, m.w, m.b);
+        else rc = dqmc::launch_nucb_dw_sqsum(st, d_nuc_act + x_of[q], G + m.z, A, rows, m.n_in, m.n_out, nb, sqF, m.w, m.b, part);
+      }
+      t_end();
+      if (rc) return rc == -1 ? fail(DQMC_E_UNSUPPORTED, name + ": a nuclear-stream layer exceeds the LDS")
+                              : fail(DQMC_E_HIP, "nuclear-stream backward launch failed");
+      if (nuc_ne)
+        for (int s = 0; s < 2; ++s) {
+          const long nz = (long)nuc_n * nuc_K * nuc_ne;
+          if (out) dqmc::launch_nucb_zbias_store<real>(st, G + nuc_zeta_off(s), A, nz, nb, o, ld, nuc_zbias[s]);
+          else dqmc::launch_nucb_zbias_sqsum(st, G + nuc_zeta_off(s), A, nz, nb, sqF, nuc_zbias[s]);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return DQMC_OK;
+  }
+  // dqmc_jacobian_to_params: the per-walker form of grad_to_params.  The arenas come from the gradient workspace under ws_budget.
+  int jacobian_to_params(const void* jac, size_t ld_jac, int B, const void* logpsi, const int32_t* sign, void* jac_theta,
+                         size_t ld_theta) override {
+    const std::string name = "dqmc_jacobian_to_params";
+    if (!d_pm_src) return fail(DQMC_E_ARG, "no parameter map set (dqmc_set_param_map)");
+    if (B < 1) return fail(DQMC_E_ARG, name + ": B must be positive");
+    if (ld_jac < n_weights) return fail(DQMC_E_ARG, name + ": ld_jac must be at least n_weights");
+    if (ld_theta < pm_n_params) return fail(DQMC_E_ARG, name + ": ld_theta must be at least n_params");
+    const bool nuc = nuc_set && grad_att_const() > 0;
+    if (nuc && !nuclear_params)
+      return fail(DQMC_E_UNSUPPORTED, name + ": " + attention_refusal_text(true));
+    if (nuc) { const int rc = nuc_params_check(name); if (rc) return rc; }
+    dqmc::launch_jac_to_params<real>(st, (const real*)jac, (long)ld_jac, d_pm_row, d_pm_col, (const real*)logpsi, sign, (real*)jac_theta,
+                                     (long)ld_theta, (long)pm_n_params, B);
+    last_chunks[0] = 1;
+    if (nuc) {
+      const size_t arena = sizeof(double) * nuc_arena;
+      long cap = (long)((ws_budget > arena ? ws_budget - arena : 0) / arena);
+      cap = cap < 1 ? 1 : cap > B ? B : cap;
+      { const int rc = grad_ws_reserve(arena * ((size_t)cap + 1)); if (rc) return rc; }
+      double* G = reinterpret_cast<double*>(g_ws.p);
+      last_chunks[0] = (int)((B + cap - 1) / cap);
+      const int rc = nuc_fold_rows<real>(name, (const real*)jac, (long)ld_jac, (long)n_weights, d_nuc_col, B, G, G + (size_t)cap * nuc_arena, cap,
+                                         (real*)jac_theta, (long)ld_theta, nullptr, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    HIP_TRY(hipGetLastError());
     return DQMC_OK;
   }
 

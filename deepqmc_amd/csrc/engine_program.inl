@@ -368,6 +368,13 @@
       nuclear_coords = value;
       return DQMC_OK;
     }
+    if (s == "nuclear_params") {
+      if (value != 0 && value != 1) return fail(DQMC_E_ARG, "nuclear_params must be 0 or 1");
+      if (value && (!nuc_set || !nuclear_reverse))
+        return fail(DQMC_E_ARG, "nuclear_params needs a registered nuclear stream (dqmc_set_nuclear_stream) and nuclear_reverse 1");
+      nuclear_params = value;
+      return DQMC_OK;
+    }
     if (s == "ws_budget_mb") { if (value < 1) return fail(DQMC_E_ARG, "ws_budget_mb must be positive"); ws_budget = (size_t)value << 20; return DQMC_OK; }
     if (s == "slogdet_mfma") { slogdet_mfma = value; return DQMC_OK; }
     if (s == "lane_compact") { lane_compact = value != 0; analyse_lanes(); last_B = 0; return DQMC_OK; }

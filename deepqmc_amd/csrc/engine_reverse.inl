@@ -13,7 +13,8 @@
 // What the modes make of an op's per-walker parameter partials:
 //   Vjp     sum_b cot[b] (...) into grad (the cotangent enters at FINAL).
 //   Jac     unit cotangent; row b of jac[B][ld_jac] receives walker b's partials: LINEAR forms its weight blocks per walker
-//           (kernels_jac.inl, no split-K reduction), CONST / ORBITALS / FINAL copy theirs (engine_jac.inl).
+//           (kernels_jac.inl, no split-K reduction), CONST / ORBITALS / FINAL copy theirs (engine_jac.inl), and so does ATTENTION
+//           for its constant key / value rows (option "nuclear_params"; in Kfac they are rest columns).
 //   Kfac    unit cotangent, so every pre-activation adjoint is the dZ1 of G; cot is applied as a per-walker weight where
 //           partials are summed over the walkers into grad.  After each LINEAR backward has formed dZ, the factor kernels
 //           (kernels_kfac.inl) add A_l and G_l; partials of the entries no LINEAR op owns go to `rest` (engine_kfac.inl).
@@ -99,7 +100,9 @@
     if (B < 1) return fail(DQMC_E_ARG, "B must be positive");
     const bool per_walker = q.mode != Rev::Vjp && q.mode != Rev::Orbs;
     const bool coords = q.mode == Rev::Coords;
-    if (attention_refused(per_walker, coords)) return fail(DQMC_E_UNSUPPORTED, name + ": " + attention_refusal_text(per_walker, coords));
+    const bool params = q.mode == Rev::Jac || q.mode == Rev::Kfac;      // (option "nuclear_params": the constant rows' and zeta tables'
+    if (attention_refused(per_walker, coords, params))                  // partials go to their own jac / rest columns, per walker)
+      return fail(DQMC_E_UNSUPPORTED, name + ": " + attention_refusal_text(per_walker, coords, params));
     const bool nuc = coords && nuc_coords_active(q.grad_R != nullptr);
     if (nuc && !nuc_fresh)
       return fail(DQMC_E_ARG, name + ": the nuclear stream's activations are older than the weights (dqmc_set_weights since the last "

@@ -246,6 +246,30 @@ template <typename real>
 void launch_nucb_edge_feat_bwd(hipStream_t st, const double* R, double eps, const double* dF, int n, long A, const real* lp, const int32_t* sg,
                                real* grad_R, int B);
 
+// Option "nuclear_params" (engine_nuc.inl: nuc_fold_rows): per-walker parameter partials of one stream layer on the float64 MFMA,
+// dW_b = X^T dZ_b (X [rows][n_in] shared, dZ_b [rows][n_out] at dZ + b * A) and db_b = colsum dZ_b (b_off -1: no bias).  The
+// X^T tile of a workgroup lives in the LDS: -1, launching nothing, when 16 x pad4(rows) doubles exceed it (nucb_dw_fits); -2 on
+// a HIP error.  store: ADDS walker b's partials to row b of out [B][ld] at w_off / b_off (theta order).  sqsum: F[w_off + e] +=
+// sum_b dW_b[e]^2 (F over theta), the walkers in NUCB_DW_SLICES contiguous slices whose sums meet in ascending order through
+// part (nucb_dw_part_doubles doubles); no per-walker rows, no atomics.
+constexpr int NUCB_DW_SLICES = 8;
+bool nucb_dw_fits(int rows);
+size_t nucb_dw_lds_bytes(int rows);
+size_t nucb_dw_part_doubles(int n_in, int n_out);
+template <typename real>
+int launch_nucb_dw_store(hipStream_t st, const double* X, const double* dZ, long A, int rows, int n_in, int n_out, int B, real* out, long ld,
+                         long w_off, long b_off);
+int launch_nucb_dw_sqsum(hipStream_t st, const double* X, const double* dZ, long A, int rows, int n_in, int n_out, int B, double* F,
+                         long w_off, long b_off, double* part);
+// the zeta tables' bias: walker b's partial is its adjoint of the table (dzeta + b * A, n entries)
+template <typename real>
+void launch_nucb_zbias_store(hipStream_t st, const double* dzeta, long A, long n, int B, real* out, long ld, long off);
+void launch_nucb_zbias_sqsum(hipStream_t st, const double* dzeta, long A, long n, int B, double* F, long off);
+// jt[b][p] = sum of jac[b][col] over the copies of parameter element p (CSR row / col, ascending), zero rows for invalid walkers
+template <typename real>
+void launch_jac_to_params(hipStream_t st, const real* jac, long ld_jac, const int32_t* row, const int32_t* col, const real* lp,
+                          const int32_t* sg, real* jt, long ld_t, long n_params, int B);
+
 // ---- kernel_attention_mfma.hip: contractions on MFMA, float32 and float64 (head_dim % 16 == 0, <= 64 queries / keys) ----
 template <typename real> size_t attention_mfma_lds_bytes(int N, int hd, int n_const);
 template <typename real> bool attention_mfma_supported(int N, int hd, int n_const);
@@ -647,6 +671,7 @@ struct KfacDirArgs {
   long n_params;
   int max_n, max_da, max_dg, n_panels;
   const int* active;          // host, [n_panels + 1]: matrices that have panel k (a prefix of mats)
+  const double* nuc_F;        // [n_params] or nullptr: sum_b o_bi^2 of the diagonal entries with an empty CSR row (the nuclear stream's)
 };
 // delta must already hold a copy of g; `real` is the type of rest and logpsi
 template <typename real> void launch_kfac_direction(hipStream_t st, const KfacDirArgs& a);

@@ -88,7 +88,7 @@ template <typename real>
 __global__ void __launch_bounds__(256) k_kf_diag(KfTables t, const real* __restrict__ rest, long n_rest, int B,
                                                  const double* __restrict__ scal, const double* __restrict__ g,
                                                  double* __restrict__ state_diag, int first, double ema, double damping,
-                                                 double* __restrict__ delta) {
+                                                 double* __restrict__ delta, const double* __restrict__ nuc_F) {
   __shared__ double red[4][64];
   const int le = threadIdx.x & 63, q = threadIdx.x >> 6;
   const long e = (long)blockIdx.x * 64 + le;
@@ -101,6 +101,7 @@ __global__ void __launch_bounds__(256) k_kf_diag(KfTables t, const real* __restr
       for (long c = c0; c < c1; ++c) o += (double)rest[(long)b * n_rest + t.diag_col[c]];
       s += o * o;
     }
+    if (nuc_F && c1 == c0) s = q == 0 ? nuc_F[t.diag_pos[e]] : 0.0;      // (the nuclear stream's own parameters: k_nucb_dw summed the squares)
   }
   red[q][le] = s;
   __syncthreads();
@@ -359,7 +360,7 @@ void launch_kfac_direction(hipStream_t st, const KfacDirArgs& a) {
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_kf_count<real>), dim3(1), dim3(OPT_BLOCK), 0, st, (const real*)a.logpsi, a.sign, a.B, a.scal);
   if (t.n_diag > 0)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_kf_diag<real>), dim3((unsigned)((t.n_diag + 63) / 64)), dim3(256), 0, st, t, (const real*)a.rest,
-                       a.n_rest, a.B, (const double*)a.scal, a.g, a.state + t.n_mat_elems, a.first, a.ema, a.damping, a.delta);
+                       a.n_rest, a.B, (const double*)a.scal, a.g, a.state + t.n_mat_elems, a.first, a.ema, a.damping, a.delta, a.nuc_F);
   if (t.n_mod > 0) {
     const int ng = opt_grid(t.n_mat_elems);
     hipLaunchKernelGGL(k_kf_assemble, dim3(ng), dim3(OPT_BLOCK), 0, st, t, a.factors, (const double*)a.scal, a.state, a.first, a.ema);

@@ -464,6 +464,113 @@ __global__ void __launch_bounds__(NUC_BLOCK) k_nucb_edge_feat_bwd(const double* 
   grad_R[idx] += (real)acc;
 }
 
+// ---- option "nuclear_params": the stream's parameter partials per walker (engine_nuc.inl: nuc_fold_rows) ----
+// dW_b[i][o] = sum_r X[r][i] dZ_b[r][o] (i < n_in) and, as row n_in of the same product against a column of ones, the bias
+// partial db_b[o] = sum_r dZ_b[r][o], on v_mfma_f64_16x16x4_f64.  X [rows][n_in] is shared by the walkers, walker b's dZ
+// [rows][n_out] lives at dZ + b * A (its adjoint arena).  The contraction runs over the rows, zero-padded to a multiple of 4.
+// A workgroup of four waves stages the tile X^T[16 blockIdx.x ..][:] in the LDS once (row stride S, odd, zeros beyond rows and
+// n_in, ones in the bias row) and walks over its slice of the walkers, blockIdx.z of gridDim.z contiguous slices; wave wv owns
+// the 16 output columns of tile 4 blockIdx.y + wv.  A walker's tile is a sum in the fixed order of the MFMA's k-steps and does
+// not depend on the other walkers.  Two epilogues:
+//   SQ false  the tile is ADDED to row b of out [B][ld] at w_off + i n_out + o (theta order), the bias row at b_off + o;
+//   SQ true   the squares of the tile's elements are summed over the slice's walkers in ascending order and written to
+//             part[blockIdx.z][E], E = (n_in + 1) n_out (the bias row last): no per-walker row exists, nothing is added
+//             concurrently; k_nucb_sqsum combines the slices in ascending order.
+template <bool SQ, typename real>
+__global__ void __launch_bounds__(256) k_nucb_dw(const double* __restrict__ X, const double* __restrict__ dZ, long A, int rows, int n_in,
+                                                 int n_out, int has_bias, int B, int S, real* __restrict__ out, long ld, long w_off,
+                                                 long b_off, double* __restrict__ part) {
+  typedef Mfma<double>::acc_t acc_t;
+  HIP_DYNAMIC_SHARED(char, nucb_smem)
+  double* Xs = reinterpret_cast<double*>(nucb_smem);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
+  const int i0 = blockIdx.x * 16, rows4 = (rows + 3) / 4 * 4;
+  for (int e = threadIdx.x; e < 16 * S; e += 256) {
+    const int c = e / S, r = e - c * S, i = i0 + c;
+    double x = 0.0;
+    if (r < rows) x = i < n_in ? X[(long)r * n_in + i] : (i == n_in && has_bias) ? 1.0 : 0.0;
+    Xs[e] = x;
+  }
+  __syncthreads();
+  const int o = (blockIdx.y * 4 + wv) * 16 + l15;
+  if ((blockIdx.y * 4 + wv) * 16 >= n_out) return;      // (uniform over the wave; no barrier follows)
+  const int per = (B + (int)gridDim.z - 1) / (int)gridDim.z;
+  const int b_lo = (int)blockIdx.z * per, b_hi = b_lo + per < B ? b_lo + per : B;
+  double sq[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = b_lo; b < b_hi; ++b) {
+    const double* z = dZ + (long)b * A;
+    acc_t acc = acc_t{0, 0, 0, 0};
+    for (int k0 = 0; k0 < rows4; k0 += 4) {
+      const int r = k0 + l4;
+      const double bv = (r < rows && o < n_out) ? z[(long)r * n_out + o] : 0.0;
+      acc = Mfma<double>::run(Xs[l15 * S + r], bv, acc);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (SQ) {
+        sq[j] += acc[j] * acc[j];
+      } else {
+        const int i = i0 + Mfma<double>::row_of(lane, j);
+        if (o < n_out) {
+          if (i < n_in) out[(long)b * ld + w_off + (long)i * n_out + o] += (real)acc[j];
+          else if (i == n_in && has_bias) out[(long)b * ld + b_off + o] += (real)acc[j];
+        }
+      }
+    }
+  }
+  if constexpr (SQ) {
+    const long E = (long)(n_in + 1) * n_out;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = i0 + Mfma<double>::row_of(lane, j);
+      if (o < n_out && i <= n_in) part[(long)blockIdx.z * E + (long)i * n_out + o] = sq[j];
+    }
+  }
+}
+// F[w_off + e] += sum_z part[z][e] (e < n_in n_out), F[b_off + e - n_in n_out] likewise for the bias row, z ascending
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_sqsum(const double* __restrict__ part, int nz, int n_in, int n_out, int has_bias,
+                                                          double* __restrict__ F, long w_off, long b_off) {
+  const long e = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  const long nw = (long)n_in * n_out, E = nw + n_out;
+  if (e >= (has_bias ? E : nw)) return;
+  double s = 0.0;
+  for (int z = 0; z < nz; ++z) s += part[(long)z * E + e];
+  F[e < nw ? w_off + e : b_off + (e - nw)] += s;
+}
+// the zeta tables' bias: walker b's partial is its adjoint of the table, dzeta + b * A.  SQ false: out[b][off + e] += it;
+// SQ true: F[off + e] += the sum of its squares over the walkers, ascending
+template <bool SQ, typename real>
+__global__ void __launch_bounds__(NUC_BLOCK) k_nucb_zbias(const double* __restrict__ dzeta, long A, long n, int B, real* __restrict__ out,
+                                                          long ld, long off, double* __restrict__ F) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if constexpr (SQ) {
+    if (idx >= n) return;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) { const double v = dzeta[(long)b * A + idx]; s += v * v; }
+    F[off + idx] += s;
+  } else {
+    if (idx >= n * B) return;
+    const long b = idx / n, e = idx - b * n;
+    out[b * ld + off + e] += (real)dzeta[b * A + e];
+  }
+}
+// Row b of jt [B][ld_t] = the transpose of the packing applied to row b of jac [B][ld_jac]: element p sums its copies
+// jac[b][col], ascending, in the context's precision.  Rows of walkers with sign 0 or a non-finite log|psi| are zero.
+template <typename real>
+__global__ void __launch_bounds__(NUC_BLOCK) k_jac_to_params(const real* __restrict__ jac, long ld_jac, const int32_t* __restrict__ row,
+                                                             const int32_t* __restrict__ col, const real* __restrict__ lp,
+                                                             const int32_t* __restrict__ sg, real* __restrict__ jt, long ld_t, long n_params,
+                                                             long total) {
+  const long idx = (long)blockIdx.x * NUC_BLOCK + threadIdx.x;
+  if (idx >= total) return;
+  const long b = idx / n_params, p = idx - b * n_params;
+  const double l = (double)lp[b];
+  real s = 0;
+  if (sg[b] != 0 && l - l == 0)
+    for (int32_t k = row[p]; k < row[p + 1]; ++k) s += jac[b * ld_jac + col[k]];
+  jt[b * ld_t + p] = s;
+}
+
 void launch_nuc_edge_feat(hipStream_t st, const double* R, const int32_t* types, double eps, double* F, int n) {
   hipLaunchKernelGGL(k_nuc_edge_feat, dim3(nuc_grid((long)n * n)), dim3(NUC_BLOCK), 0, st, R, types, eps, F, n);
 }
@@ -606,3 +713,59 @@ template void launch_nucb_edge_feat_bwd<float>(hipStream_t, const double*, doubl
                                                float*, int);
 template void launch_nucb_edge_feat_bwd<double>(hipStream_t, const double*, double, const double*, int, long, const double*, const int32_t*,
                                                 double*, int);
+
+static inline int nucb_dw_row_stride(int rows) { return ((rows + 3) / 4 * 4) | 1; }
+size_t nucb_dw_lds_bytes(int rows) { return sizeof(double) * 16 * (size_t)nucb_dw_row_stride(rows); }
+bool nucb_dw_fits(int rows) { return nucb_dw_lds_bytes(rows) <= (size_t)160 * 1024; }
+int nucb_dw_slices(int B) { return B < NUCB_DW_SLICES ? B : NUCB_DW_SLICES; }
+size_t nucb_dw_part_doubles(int n_in, int n_out) { return (size_t)NUCB_DW_SLICES * (size_t)(n_in + 1) * n_out; }
+template <bool SQ, typename real>
+static int nucb_dw_launch(hipStream_t st, const double* X, const double* dZ, long A, int rows, int n_in, int n_out, int has_bias, int B,
+                          real* out, long ld, long w_off, long b_off, double* part) {
+  const size_t lds = nucb_dw_lds_bytes(rows);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nucb_dw<SQ, real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return -2;
+  const dim3 grid((unsigned)((n_in + (has_bias ? 1 : 0) + 15) / 16), (unsigned)((n_out + 63) / 64), (unsigned)nucb_dw_slices(B));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nucb_dw<SQ, real>), grid, dim3(256), lds, st, X, dZ, A, rows, n_in, n_out, has_bias, B,
+                     nucb_dw_row_stride(rows), out, ld, w_off, b_off, part);
+  return 0;
+}
+template <typename real>
+int launch_nucb_dw_store(hipStream_t st, const double* X, const double* dZ, long A, int rows, int n_in, int n_out, int B, real* out, long ld,
+                         long w_off, long b_off) {
+  if (!nucb_dw_fits(rows)) return -1;
+  return nucb_dw_launch<false, real>(st, X, dZ, A, rows, n_in, n_out, b_off >= 0 ? 1 : 0, B, out, ld, w_off, b_off, nullptr);
+}
+template int launch_nucb_dw_store<float>(hipStream_t, const double*, const double*, long, int, int, int, int, float*, long, long, long);
+template int launch_nucb_dw_store<double>(hipStream_t, const double*, const double*, long, int, int, int, int, double*, long, long, long);
+int launch_nucb_dw_sqsum(hipStream_t st, const double* X, const double* dZ, long A, int rows, int n_in, int n_out, int B, double* F,
+                         long w_off, long b_off, double* part) {
+  if (!nucb_dw_fits(rows)) return -1;
+  const int hb = b_off >= 0 ? 1 : 0;
+  const int rc = nucb_dw_launch<true, double>(st, X, dZ, A, rows, n_in, n_out, hb, B, nullptr, 0, w_off, b_off, part);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_nucb_sqsum, dim3(nuc_grid((long)(n_in + 1) * n_out)), dim3(NUC_BLOCK), 0, st, part, nucb_dw_slices(B), n_in, n_out, hb,
+                     F, w_off, b_off);
+  return 0;
+}
+template <typename real>
+void launch_nucb_zbias_store(hipStream_t st, const double* dzeta, long A, long n, int B, real* out, long ld, long off) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nucb_zbias<false, real>), dim3(nuc_grid(n * B)), dim3(NUC_BLOCK), 0, st, dzeta, A, n, B, out, ld, off,
+                     nullptr);
+}
+template void launch_nucb_zbias_store<float>(hipStream_t, const double*, long, long, int, float*, long, long);
+template void launch_nucb_zbias_store<double>(hipStream_t, const double*, long, long, int, double*, long, long);
+void launch_nucb_zbias_sqsum(hipStream_t st, const double* dzeta, long A, long n, int B, double* F, long off) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nucb_zbias<true, double>), dim3(nuc_grid(n)), dim3(NUC_BLOCK), 0, st, dzeta, A, n, B, nullptr, 0, off, F);
+}
+template <typename real>
+void launch_jac_to_params(hipStream_t st, const real* jac, long ld_jac, const int32_t* row, const int32_t* col, const real* lp,
+                          const int32_t* sg, real* jt, long ld_t, long n_params, int B) {
+  const long total = n_params * B;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_jac_to_params<real>), dim3(nuc_grid(total)), dim3(NUC_BLOCK), 0, st, jac, ld_jac, row, col, lp, sg, jt,
+                     ld_t, n_params, total);
+}
+template void launch_jac_to_params<float>(hipStream_t, const float*, long, const int32_t*, const int32_t*, const float*, const int32_t*, float*,
+                                          long, long, int);
+template void launch_jac_to_params<double>(hipStream_t, const double*, long, const int32_t*, const int32_t*, const double*, const int32_t*,
+                                           double*, long, long, int);

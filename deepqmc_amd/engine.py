@@ -54,7 +54,7 @@ def _ptr(t):
 class Engine:
     def __init__(self, spec: AnsatzSpec, hamil: MolecularHamiltonian, params, *, dtype=torch.float32,
                  device='cuda', norm_eps: Optional[float] = None, lib=None, R=None, compiler=None, nuclear_reverse=False,
-                 nuclear_coords=False):
+                 nuclear_coords=False, nuclear_params=False):
         """`R` [n_nuc,3]: the geometry this context is compiled for (default: the Hamiltonian's).  It matters only
         for ansatzes with nuclear tokens, whose nuclear stream is folded into the program; every other ansatz
         takes the geometry per call.  `compiler(params) -> Program` replaces the default `compile_program(spec, ...)`
@@ -64,8 +64,11 @@ class Engine:
         "nuclear_reverse": device updates fold the stream on the device and grad_to_params transposes it, so the
         walker-summed gradients (log_psi_vjp, orbitals_vjp, pretrain_loss_grad) and the Adam step run.  `nuclear_coords` (implies
         `nuclear_reverse`): option "nuclear_coords" as well, which opens log_psi_grad_coords -- the stream's backward runs per
-        walker, adjoints only, down to R.  `self.nuclear_coords` says whether it is on."""
-        nuclear_reverse = bool(nuclear_reverse) or bool(nuclear_coords)
+        walker, adjoints only, down to R.  `self.nuclear_coords` says whether it is on.  `nuclear_params` (implies
+        `nuclear_reverse`, independent of `nuclear_coords`): option "nuclear_params", which opens log_psi_jacobian, log_psi_kfac,
+        jacobian_to_params and the KFAC tables -- the stream's parameter partials are formed per walker.  `self.nuclear_params`
+        says whether it is on (set_option('nuclear_params', ...) keeps it and Program.nuclear_params current)."""
+        nuclear_reverse = bool(nuclear_reverse) or bool(nuclear_coords) or bool(nuclear_params)
         self.lib = lib if lib is not None else _lib.load()
         self.spec, self.hamil = spec, hamil
         self.dtype = dtype
@@ -124,6 +127,9 @@ class Engine:
         self.nuclear_coords = bool(nuclear_coords) and p.nuclear_stream is not None
         if self.nuclear_coords:
             self.set_option('nuclear_coords', 1)
+        self.nuclear_params = False
+        if nuclear_params and p.nuclear_stream is not None:
+            self.set_option('nuclear_params', 1)
 
     def _register_nuclear_stream(self):
         """dqmc_set_nuclear_stream from Program.nuclear_stream and the current parameters."""
@@ -282,6 +288,27 @@ class Engine:
         self._ensure_param_map()
         out = torch.empty(self.program.n_params(), dtype=torch.float64, device=self.device)
         self._check(self.lib.dqmc_grad_to_params(self._ctx, g.data_ptr(), out.data_ptr()))
+        return out
+
+    def jacobian_to_params(self, J, logpsi, sign, out=None):
+        """Per-walker Jacobian over the weight buffer (log_psi_jacobian, with the logpsi and sign of that call) -> [B, n_params]
+        in the engine's dtype on its device: row b is the transpose of the packing applied to J[b], the per-walker form of
+        grad_to_params (dqmc_jacobian_to_params).  Without a nuclear stream it equals Program.unflatten_jacobian(J); with one
+        (nuclear_params=True) the stream's parameter partials of every walker are added on the device.  Rows of invalid
+        walkers are zero.  `out`: a preallocated contiguous [B, n_params] tensor."""
+        if not isinstance(J, torch.Tensor) or J.dim() != 2 or J.dtype != self.dtype or J.device.type != self.device.type or \
+                J.shape[1] != self.program.weights.size or J.stride(1) != 1 or J.stride(0) < J.shape[1]:
+            raise DqmcError(f"'J' must be a [B, {self.program.weights.size}] {self.dtype} tensor on {self.device} with unit column stride")
+        B = J.shape[0]
+        self._arg('logpsi', logpsi, self.dtype, (B,))
+        self._arg('sign', sign, torch.int32, (B,))
+        self._ensure_param_map()
+        n = self.program.n_params()
+        if out is None:
+            out = torch.empty(B, n, dtype=self.dtype, device=self.device)
+        self._arg('out', out, self.dtype, (B, n))
+        self._check(self.lib.dqmc_jacobian_to_params(self._ctx, J.data_ptr(), J.stride(0), B, logpsi.data_ptr(), sign.data_ptr(),
+                                                     out.data_ptr(), n))
         return out
 
     def adam_step(self, theta, mu, nu, grad_theta, *, lr, b1=0.9, b2=0.999, eps=1e-8, t=1, norms=None):
@@ -938,6 +965,8 @@ class Engine:
     def set_option(self, name: str, value: int):
         self._check(self.lib.dqmc_set_option(self._ctx, name.encode(), int(value)))
         self._options[name] = int(value)      # (what the caller chose: apply(return_mos=True) restores it)
+        if name == 'nuclear_params':          # (Program.kfac_blocks and the package's gates read it)
+            self.nuclear_params = self.program.nuclear_params = bool(value)
 
     def get_option(self, name: str, default: int) -> int:
         """The value last set through set_option (the library has no getter), else `default`."""

@@ -315,6 +315,9 @@ def _kfac_directions_tree(ansatz, params, r, Rs, loss, cots, stats, state, dampi
     for s, cot in enumerate(cots):
         pc, eng = _state_conf(ansatz, params[s], r, Rs, s)
         prog = eng.program
+        if prog.nuclear_stream is not None:      # (the stream's diagonal elements are formed on the device only: flat=True)
+            raise NotImplementedError(f'compute_energy_loss_and_kfac(flat=False): {prog.PER_WALKER_NUCLEAR}; the tree path stays '
+                                      'refused with nuclear_params=True, use flat=True')
         rr = pc.r if hasattr(pc, 'r') else pc
         RR = pc.R if hasattr(pc, 'R') else None
         sign, logpsi, g, factors, rest = eng.log_psi_kfac(rr, cot.to(eng.dtype).to(eng.device).contiguous(), RR)

@@ -68,10 +68,10 @@ class _Optimizer:
         return [self.ansatz.engine(p, Rs[0]) for p in params]
 
     def _refuse_nuclear_stream(self, params, batch):
-        """The optimisers that need per-walker partials of log|psi| (Jacobian rows, KFAC factors) cannot take a program whose
-        nuclear-token stream is shared by all walkers."""
+        """The optimisers that need per-walker partials of log|psi| (Jacobian rows, KFAC factors) take a program whose
+        nuclear-token stream is shared by all walkers only with nuclear_params=True (the stream's partials per walker)."""
         for eng in self._engines(params, batch[0] if batch is not None else None):
-            if eng.program.nuclear_stream is not None:
+            if eng.program.nuclear_stream is not None and not eng.nuclear_params:
                 raise NotImplementedError(f'{type(self).__name__}: {eng.program.PER_WALKER_NUCLEAR}')
 
     @staticmethod

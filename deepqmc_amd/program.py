@@ -110,11 +110,16 @@ class Program:
     # nuclear_gnn_head) are part of grad_leaves without a copy in the weight buffer; the transpose of the fold exists on the
     # device only (Engine.grad_to_params).
     nuclear_stream: Optional[dict] = None
+    # library option "nuclear_params" of the context this program was compiled for (Engine.set_option keeps it current): the
+    # stream's parameter partials exist per walker, on the device
+    nuclear_params: bool = False
 
     PER_WALKER_NUCLEAR = ('the nuclear-token stream has no per-walker partials (all walkers share it: one nuclear backward per '
                           'walker); only the walker-summed gradients (log_psi_vjp, orbitals_vjp, pretraining, AdamOptimizer) run '
                           'with nuclear tokens, and with nuclear_coords=True the coordinate calls (log_psi_grad_coords, '
-                          'make_grad_nuc_log_wf, the AC-ZB / AC-ZVQZB forces)')
+                          'make_grad_nuc_log_wf, the AC-ZB / AC-ZVQZB forces); nuclear_params=True forms the stream\'s parameter '
+                          'partials per walker on the device and opens log_psi_jacobian, log_psi_kfac, NaturalGradientOptimizer and '
+                          'KFACOptimizer')
 
     def unflatten_grad(self, g):
         """Flat gradient over the weight buffer (dqmc_log_psi_vjp) -> haiku tree {module: {leaf: array}}: the transpose of
@@ -200,7 +205,8 @@ class Program:
         if self.grad_unsupported:
             raise NotImplementedError(f'unflatten_jacobian: unsupported for this program ({self.grad_unsupported})')
         if self.nuclear_stream is not None:
-            raise NotImplementedError(f'unflatten_jacobian: {self.PER_WALKER_NUCLEAR}')
+            raise NotImplementedError(f'unflatten_jacobian: {self.PER_WALKER_NUCLEAR}; the per-walker transpose of the '
+                                      'nuclear-stream fold runs on the device only: use Engine.jacobian_to_params(J, logpsi, sign)')
         import torch
         if J.dim() != 2 or J.shape[1] != self.grad_src.size:
             raise ValueError(f'Jacobian of shape {tuple(J.shape)} for a weight buffer of {self.grad_src.size}')
@@ -247,7 +253,7 @@ class Program:
         diagonal treatment."""
         if self.grad_unsupported:
             raise NotImplementedError(f'kfac_blocks: unsupported for this program ({self.grad_unsupported})')
-        if self.nuclear_stream is not None:
+        if self.nuclear_stream is not None and not self.nuclear_params:
             raise NotImplementedError(f'kfac_blocks: {self.PER_WALKER_NUCLEAR}')
         lay = self.kfac_layout()
         by_mod: Dict[str, list] = {}

@@ -30,7 +30,8 @@ from .types import PhysicalConfiguration, Psi
 
 class NeuralNetworkWaveFunction:
     def __init__(self, hamil: MolecularHamiltonian, spec='paulinet', *, dtype=torch.float32, device='cuda',
-                 norm_eps=None, lib=None, attention_reverse=False, nuclear_reverse=False, nuclear_coords=False):
+                 norm_eps=None, lib=None, attention_reverse=False, nuclear_reverse=False, nuclear_coords=False,
+                 nuclear_params=False):
         """`attention_reverse`: opt in to the reverse pass through attention ops (library option "attention_reverse"), which
         the parameter- and coordinate-gradient entry points below, the force and ECP-force estimators, pretraining,
         `create_loss_fn` and the optimisers of `fit_wf` need for a Psiformer.  Off (the default) those calls fail with
@@ -44,7 +45,12 @@ class NeuralNetworkWaveFunction:
         `nuclear_coords` (implies `nuclear_reverse` and `attention_reverse`): the stream's backward also runs per walker, adjoints
         only, down to the nuclear coordinates (library option "nuclear_coords"), which opens `log_psi_grad_coords`,
         `force.make_grad_nuc_log_wf`, `evaluate_hf_force_ac_zb` / `_ac_zvqzb` and their `fit_wf` monitors.  The Jacobian, KFAC,
-        NaturalGradientOptimizer, KFACOptimizer and the ECP force stay refused."""
+        NaturalGradientOptimizer, KFACOptimizer and the ECP force stay refused.
+        `nuclear_params` (implies `nuclear_reverse` and `attention_reverse`; independent of `nuclear_coords`): the stream's
+        parameter partials are formed per walker on the device (library option "nuclear_params"), which opens `log_psi_jacobian`
+        (through Engine.jacobian_to_params), `log_psi_kfac`, `compute_energy_loss_and_natgrad`,
+        `compute_energy_loss_and_kfac(flat=True)`, NaturalGradientOptimizer and KFACOptimizer.  In the KFAC direction the
+        stream's own parameters (nuclei_embedding, nuclear_gnn_head) are diagonal elements.  The ECP force stays refused."""
         self.hamil = hamil
         if spec == 'transpsiformer':
             self.spec: AnsatzSpec = ANSATZES[spec](hamil.mol.charges)      # atom types of the nuclei embedding
@@ -52,8 +58,9 @@ class NeuralNetworkWaveFunction:
             self.spec = ANSATZES[spec]() if isinstance(spec, str) else spec
         self.dtype, self.device, self.norm_eps, self._lib = dtype, device, norm_eps, lib
         self.nuclear_coords = bool(nuclear_coords) and bool(self.spec.nuclei_tokens)
-        self.nuclear_reverse = (bool(nuclear_reverse) or bool(nuclear_coords)) and bool(self.spec.nuclei_tokens)
-        self.attention_reverse = bool(attention_reverse) or bool(nuclear_reverse) or bool(nuclear_coords)
+        self.nuclear_params = bool(nuclear_params) and bool(self.spec.nuclei_tokens)
+        self.nuclear_reverse = (bool(nuclear_reverse) or bool(nuclear_coords) or bool(nuclear_params)) and bool(self.spec.nuclei_tokens)
+        self.attention_reverse = bool(attention_reverse) or bool(nuclear_reverse) or bool(nuclear_coords) or bool(nuclear_params)
         self._engines = []       # [(params tree, Engine)], most recently used last (one per electronic state)
         self.max_engines = 8
         self._evictions = 0
@@ -106,7 +113,7 @@ class NeuralNetworkWaveFunction:
             R0 = None if gkey is None else np.frombuffer(gkey, np.float64).reshape(self.hamil.n_nuc, 3)
             eng = Engine(self.spec, self.hamil, params, dtype=self.dtype, device=self.device,
                          norm_eps=self.norm_eps, lib=self._lib, R=R0, nuclear_reverse=self.nuclear_reverse,
-                         nuclear_coords=self.nuclear_coords)
+                         nuclear_coords=self.nuclear_coords, nuclear_params=self.nuclear_params)
             if self.attention_reverse:      # before any set_kfac_map or graph capture (setting an option bumps the graph epoch)
                 eng.set_option('attention_reverse', 1)
         self._engines.append((params, gkey, eng))
@@ -191,7 +198,7 @@ class NeuralNetworkWaveFunction:
     def _per_walker_check(self, name, eng, coords=False):
         if eng.program.grad_unsupported:
             raise NotImplementedError(f'{name}: unsupported for this program ({eng.program.grad_unsupported})')
-        if eng.program.nuclear_stream is not None and not (coords and eng.nuclear_coords):
+        if eng.program.nuclear_stream is not None and not (eng.nuclear_coords if coords else eng.nuclear_params):
             raise NotImplementedError(f'{name}: {eng.program.PER_WALKER_NUCLEAR}')
 
     def _orbital_engine(self, name, params, phys_conf):
@@ -240,13 +247,14 @@ class NeuralNetworkWaveFunction:
         """The per-walker rows of the Jacobian that log_psi_vjp contracts: returns (Psi(sign, log), Jp) with
         Jp[b] = d log|psi(r_b)| / d params as a [B, n_params] tensor on the device, in the wave function's dtype, columns in
         the program's grad_leaves order (eng.program.leaf_slices / unflatten_params map them back onto the tree).  The same
-        programs as log_psi_vjp are supported."""
+        programs as log_psi_vjp are supported; a TransPsiformer needs `nuclear_params=True` and takes the device route
+        (Engine.jacobian_to_params: the stream's parameter partials are formed per walker there)."""
         r = phys_conf.r if isinstance(phys_conf, PhysicalConfiguration) else phys_conf
         R = phys_conf.R if isinstance(phys_conf, PhysicalConfiguration) else None
         eng = self.engine(params, R)
         self._per_walker_check('log_psi_jacobian', eng)          # before the B x n_weights allocation
         sign, log, J = eng.log_psi_jacobian(r, R)
-        Jp = eng.program.unflatten_jacobian(J)
+        Jp = eng.jacobian_to_params(J, log, sign) if eng.program.nuclear_stream is not None else eng.program.unflatten_jacobian(J)
         del J
         return Psi(sign, log), Jp
 
@@ -260,7 +268,7 @@ class NeuralNetworkWaveFunction:
         eng = self.engine(params, R)
         self._per_walker_check('log_psi_kfac', eng)
         sign, log, g, factors, rest = eng.log_psi_kfac(r, cotangent, R)
-        return Psi(sign, log), eng.program.unflatten_grad(g), factors, rest
+        return Psi(sign, log), self._grad_tree(eng, g), factors, rest
 
     def log_psi_grad_coords(self, params, phys_conf):
         """jax.grad of ansatz.apply(.).log with respect to the electron and the nuclear coordinates (reference force.py

@@ -221,6 +221,20 @@ int dqmc_weights_from_params(dqmc_ctx* ctx, const double* theta);
 /* The transpose of the packing: grad_theta[e] = sum over j with src[j] == e of grad_w[j] (double[n_weights], what
  * dqmc_log_psi_vjp writes), in ascending j.  No atomics: identical calls give bit-identical results. */
 int dqmc_grad_to_params(dqmc_ctx* ctx, const double* grad_w, double* grad_theta);
+/* The per-walker form of dqmc_grad_to_params.  jac: real[B][ld_jac] as dqmc_log_psi_jacobian wrote it for B walkers, with the
+ * logpsi / sign of that call (all device memory, the context's precision).  Row b of jac_theta (real[B][ld_theta], ld_theta >=
+ * n_params; columns beyond n_params are left alone) receives the transpose of the packing applied to row b of jac: element e is
+ * the sum of jac[b][j] over the entries j with src[j] == e, in ascending j, in the context's precision.  Rows of walkers with
+ * sign 0 or a non-finite log|psi| are zero.  Works for every program with a parameter map.  With a nuclear stream (option
+ * "nuclear_params" 1, else DQMC_E_UNSUPPORTED) each walker's partials of the derived vector are gathered from its row (ascending
+ * entry order), taken back through the stream for all walkers of a chunk at once (float64, the chunk's arenas come from the
+ * gradient workspace under "ws_budget_mb") and the stream's parameter partials -- dW = X^T dZ and db = colsum dZ of every linear
+ * layer on the float64 MFMA, the walker's adjoint of the zeta tables for zetas_bias_* -- are ADDED to the row.  A walker's row
+ * does not depend on the other walkers; identical calls are bit-identical.  DQMC_E_ARG while the stream's activations are older
+ * than the weights (as dqmc_grad_to_params), DQMC_E_UNSUPPORTED, launching nothing, if a stream layer does not fit the LDS (its
+ * 16 x n_out weight panel, or 16 x rows of its transposed input). */
+int dqmc_jacobian_to_params(dqmc_ctx* ctx, const void* jac, size_t ld_jac, int B, const void* logpsi, const int32_t* sign,
+                            void* jac_theta, size_t ld_theta);
 /* optax.adam over the flat vectors, in place: with t the 1-based count of this step,
  *   mu = b1 mu + (1 - b1) g, nu = b2 nu + (1 - b2) g^2, theta += -lr (mu / (1 - b1^t)) / (sqrt(nu / (1 - b2^t)) + eps),
  * followed by dqmc_weights_from_params(theta).  n must be the map's n_params.  norms3: double[3] or NULL, receives the
@@ -258,6 +272,12 @@ int dqmc_apply_update(dqmc_ctx* ctx, double* theta, const double* delta, double 
  * logpsi, sign exactly as dqmc_log_psi_kfac wrote them for B walkers (rest and logpsi in the context's precision; n_v is
  * counted from sign and logpsi on the device); state as above, read unless first != 0, and written; damping > 0;
  * delta double[n_params] and dot[1] = <delta, grad_theta> are written.
+ * With a nuclear stream (option "nuclear_params"): the parameter elements of the stream that no module covers -- w / b of its
+ * linear layers, zetas_bias_* -- are listed in diag_pos with an EMPTY CSR row (they have no copy in the weight buffer);
+ * dqmc_set_kfac_map recognises them from the stream descriptor (an empty row anywhere else, or a row with columns there, is
+ * DQMC_E_ARG) and allocates the arenas of the stream's batched backward.  dqmc_kfac_direction forms their o_bi from the rest rows
+ * (the constant rows' and zeta tables' partials) through the stream, F_ii = sum_b o_bi^2 / n_v without ever storing a per-walker
+ * row, with the same EMA, and delta_i = g_i / (F_ii + damping).  Kronecker factors of the stream's own layers are not formed.
  * dqmc_kfac_apply: theta += -lr coeff delta with coeff = min(1, sqrt(norm_constraint / (lr^2 dot[0]))) -- the norm
  * constraint of kfac_jax with momentum 0; coeff = 1 when norm_constraint <= 0 or dot[0] <= 0 -- evaluated on the device,
  * then dqmc_weights_from_params(theta).  norms4: double[4] or NULL = the 2-norms of theta before the step, of delta and of
@@ -432,7 +452,13 @@ int dqmc_psi_grad(dqmc_ctx* ctx, const void* r, const void* R, int B, void* logp
  * Option "nuclear_coords" 1 (it needs a registered stream AND "nuclear_reverse" 1; anything else, and values other than 0 / 1:
  * DQMC_E_ARG) admits dqmc_log_psi_grad_coords as well: it needs the stream's per-walker ADJOINTS only, which a backward of the
  * stream batched over the walkers provides (see there).  The other four keep refusing with the same text.  Off (the default)
- * nothing changes. */
+ * nothing changes.
+ * Option "nuclear_params" 1 (the same conditions and errors; independent of "nuclear_coords") admits dqmc_log_psi_jacobian,
+ * dqmc_log_psi_kfac and dqmc_set_kfac_map: the Jacobian and KFAC modes then write each walker's partials of the constant key /
+ * value rows and of the zeta tables into those entries' own jac resp. rest columns, dqmc_jacobian_to_params takes a Jacobian's
+ * rows back through the stream per walker, and dqmc_kfac_direction treats the stream's own parameters as diagonal elements (see
+ * there).  dqmc_ecp_force keeps refusing, and dqmc_log_psi_grad_coords does unless "nuclear_coords" is on as well.  Off (the
+ * default) nothing changes. */
 int dqmc_log_psi_vjp(dqmc_ctx* ctx, const void* r, const void* R, int B, const void* cot,
                      double* grad, void* logpsi, int32_t* sign);
 
